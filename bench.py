@@ -15,7 +15,10 @@ occupancy votes so that every replica prunes identically.
 `--gpus N` without a torch.distributed environment re-executes itself under `torch.distributed.run` with N ranks on
 127.0.0.1 (the driver launches the N ranks itself; both ways end in the same code).
 
-Prints ONE JSON line on rank 0 (see the contract in the task description): metric/value/unit, ms_per_step, plus
+Prints ONE JSON line on rank 0: metric/value/unit, ms_per_step, dtype, higher_is_better.  A plain run sets up, warms up, times
+--steps steps and prints that line; `--dump-outputs DIR` writes what the last timed step computed as .npy files before it prints
+(dump_outputs).  `--full` adds the extras below (each `--no-...` option still drops its own):
+  steady_state -- STEADY_STEPS more steps after a timed region shorter than that
   roofline     -- HBM-roofline fraction of the dominant kernel, its duration measured live with HIP events on
                   the launch stream during the timed region (algorithmic bytes per sample: DESIGN.md section 4)
   cpu_baseline -- the CPU oracle (port of the reference path; the reference has no CPU path) timed on this box's
@@ -24,7 +27,9 @@ Prints ONE JSON line on rank 0 (see the contract in the task description): metri
                   reference's fox photographs at dataset.factor 2 (ExpRunner::Train: adaptive ray batch, octree
                   subdivision / pruning at the milestones), its test-view PSNR by the reference's definition, and then the
                   same full train step timed in that state (pruned 1e5-node octree, trained table, rays of 5..400
-                  samples, rho > 1) with its own dominant-kernel line.
+                  samples, rho > 1) with its own dominant-kernel line; then the PSNR study (psnr_numerics_ab).
+  other_configs -- (rank 0, N=1 only) BASELINE configs 3-5 as short runs of this script with --full, in their own processes.
+  scatter_counters -- the kernel library's hash-scatter counters over the whole process.
 """
 import argparse
 import json
@@ -257,7 +262,7 @@ def other_configs(args):
     for tag, extra in (("llff", ["--preset", "llff"]), ("nerf-360", ["--preset", "nerf-360"]),
                        ("wanjinyou_big_log2_20", ["--preset", "wanjinyou_big", "--log2", "20"]),
                        ("wanjinyou_big_log2_22", ["--preset", "wanjinyou_big", "--log2", "22"])):
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.other_steps), "--warmup", "10", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", str(args.other_steps), "--warmup", "10", "--no-cpu-baseline",
                "--no-converged", "--no-steady", "--other-configs", "0"] + extra
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
@@ -399,6 +404,32 @@ def _scatter_counters():
             "largest_slice_sum_of_abs_addends": float(np.array(c[2], np.int32).view(np.float32))}
 
 
+DUMP_TABLE_SAMPLE = 1 << 21  # hash-table entries written by --dump-outputs (8 MiB of fp32): the whole table of 2^19 x 16 x 2 is 64 MiB
+
+
+def dump_outputs(out_dir, runner, last, n_marched, n_meaningful):
+    """--dump-outputs: what the last timed step computed, as a caller of train_step receives it -- its loss terms, its sample
+    count (with the marched / meaningful samples of all timed steps: a step's own survivor count is still on the device when
+    it returns), the parameters and octree its update left behind -- one float32 / float64 .npy file each (~9 MiB at the default
+    preset).  The hash table is sampled at DUMP_TABLE_SAMPLE positions drawn from a fixed seed, so two runs with the same
+    arguments compare entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    st = runner.states()  # checkpoint order: [2] visit counts, [4] table, [8] field MLP, [9] colour MLP, [10] appearance embeddings
+    table = st[4].reshape(-1)
+    if table.numel() > DUMP_TABLE_SAMPLE:
+        pos = np.sort(np.random.default_rng(0).integers(0, table.numel(), DUMP_TABLE_SAMPLE))
+        table = table[torch.from_numpy(pos).to(table.device)]
+    nodes = runner.tree_nodes().cpu().numpy().view(NODE_DT)
+    out = {"loss": np.array([float(last["loss"])]), "mse": np.array([float(last["mse"])]),
+           "sample_counts": np.array([last["n_rays"], last["n_samples"], n_marched, n_meaningful], np.float64),
+           "hash_table_sample": table.float().cpu().numpy(), "field_mlp": st[8].float().cpu().numpy(),
+           "color_mlp": st[9].float().cpu().numpy(), "app_emb": st[10].float().cpu().numpy(),
+           "octree_visit_counts": st[2].double().cpu().numpy(),
+           "octree_nodes": np.concatenate([nodes["center"], nodes["side_len"][:, None], nodes["trans_idx"][:, None]], 1).astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -437,6 +468,10 @@ def main():
     ap.add_argument("--dp-buckets", type=int, default=0, help="data-parallel runs: table all-reduce in that many buckets (0 = the host's default, 4; 1 = one all-reduce)")
     ap.add_argument("--dp-overlap", type=int, default=-1, help="data-parallel runs: 1 pipelined / 0 blocking gradient exchange; -1 = default (pipelined)")
     ap.add_argument("--diag-no-nan-check", action="store_true", help="diagnostic only: drop the per-step gradient finiteness check")
+    ap.add_argument("--full", action="store_true", help="also measure the extras of the line (steady_state, roofline, cpu_baseline, "
+                    "converged + PSNR study, other_configs, scatter_counters); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy "
+                    "(dump_outputs)")
     args = ap.parse_args()
 
     if args.psnr_worker > 0:
@@ -475,6 +510,9 @@ def main():
         sys.exit("bench.py needs an MI355X: the hot path has no CPU implementation")
     dev = "cuda:%d" % local_rank
     torch.cuda.set_device(dev)
+    # the steps' random draws (march noise, background colours, edge samples) are keyed by the default generator's seed
+    # (host/KeyedDraws.h), which is drawn afresh in every process unless set: the same arguments give the same inputs
+    torch.manual_seed(2022)
 
     import f2_nerf_amd  # noqa: F401
     from f2_nerf_amd import runtime
@@ -532,7 +570,8 @@ def main():
     for i in range(args.warmup):
         step(i)
     host = runtime.host()
-    if rank == 0:
+    kernel_timing = rank == 0 and args.full  # (the roofline's HIP events ride in the timed steps of a --full run only)
+    if kernel_timing:
         host.ExpRunner.enable_kernel_timing([DOMINANT, "field_mlp_prepass", "field_fwd_cached", "field_fwd", "field_bwd",
                                              "shade_fwd", "shade_bwd"])
     c0 = runner.counters()  # (flushes)
@@ -543,8 +582,9 @@ def main():
     if args.marker_pause:
         time.sleep(0.3)
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        step(args.warmup + i)
+        last = step(args.warmup + i)
     runner.flush()  # the last step's survivor count / flags (and, data-parallel, its all-reduce + Adam) belong to the timed region
     barrier()
     elapsed = time.perf_counter() - t0
@@ -563,13 +603,17 @@ def main():
                    "note": "per rank, per step: dp_exchange_ms = first table bucket started -> flat small-gradient buffer reduced, on the "
                            "communicator's stream (its waits for the scatter's later buckets included); dp_wait_ms = what the compute stream "
                            "waited for that exchange at the top of the next step (the part of it the step did not hide)"}
-    timing = host.ExpRunner.collect_kernel_timing() if rank == 0 else {}
-    host.ExpRunner.disable_kernel_timing()
+    timing = {}
+    if kernel_timing:
+        timing = host.ExpRunner.collect_kernel_timing()
+        host.ExpRunner.disable_kernel_timing()
+    if args.dump_outputs and rank == 0 and last is not None:  # (before the steady-state steps of --full move the state on)
+        dump_outputs(args.dump_outputs, runner, last, n_marched, n_meaningful)
 
     # A short timed region (the driver's 20 steps = 22 ms) sits on the first iterations of a fresh scene; the steady state of
     # this workload is reported next to it: STEADY_STEPS more steps, no kernel timers inside, same barrier bracket (every rank).
     steady = None
-    if args.steps < STEADY_STEPS and not args.no_steady:
+    if args.full and args.steps < STEADY_STEPS and not args.no_steady:
         cs0 = runner.counters()
         barrier()
         ts0 = time.perf_counter()
@@ -664,7 +708,7 @@ def main():
                                                     "pulls a 128-byte line across the fabric (2^20; 2^22 before round 4's slice-binned gather: "
                                                     "profiles/r03_big22_pmc_tcc.csv, profiles/r04_binned_gather.txt)"}
         cpu_baseline = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 env = dict(os.environ, F2N_ORACLE_OMP="1")
                 out = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "baseline.py")], capture_output=True,
@@ -673,7 +717,7 @@ def main():
             except Exception as e:  # the baseline is a reported extra, never the thing measured
                 cpu_baseline = {"error": str(e)[:200]}
         converged = None
-        if world == 1 and not args.no_converged and scene_name == "ngp_fox":
+        if world == 1 and args.full and not args.no_converged and scene_name == "ngp_fox":
             try:
                 converged = converged_leg(args, st, dev)
             except Exception as e:  # reported next to the headline, never instead of it
@@ -685,7 +729,7 @@ def main():
                 except Exception as e:
                     converged["psnr_numerics_ab"] = {"error": str(e)[:300]}
         others = None
-        if world == 1 and args.other_configs and args.preset == "wanjinyou" and args.log2 in (0, 19) and not args.no_converged:
+        if world == 1 and args.full and args.other_configs and args.preset == "wanjinyou" and args.log2 in (0, 19) and not args.no_converged:
             try:
                 torch.cuda.empty_cache()
                 others = other_configs(args)
@@ -714,7 +758,7 @@ def main():
             "data_parallel": dp_diag,
             "other_configs": others,
             # whole process so far (timed steps, converged leg, other configs): 0 atomic records = every hash-gradient sum was order-free
-            "scatter_counters": _scatter_counters(),
+            "scatter_counters": _scatter_counters() if args.full else None,
             # buffers are sized for the worst case on purpose (1024 sample slots per ray, scatter queues): what that costs of 288 GB
             "peak_hbm_gib": {"allocated": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
                              "reserved_by_allocator": round(torch.cuda.max_memory_reserved() / 2 ** 30, 2),

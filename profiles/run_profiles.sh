@@ -17,7 +17,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-converged $BENCH_EXTRA"
+BENCH="python $ROOT/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-converged $BENCH_EXTRA"
 for k in $PASSES; do
   case $k in
     stats) timeout ${PASS_TIMEOUT:-200} rocprofv3 --kernel-trace --stats -d $OUT/stats -- $BENCH > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/stats.err ;;

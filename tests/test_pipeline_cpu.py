@@ -160,14 +160,16 @@ def test_early_stop_prefix_and_adam():
         np.testing.assert_allclose(p, pt.detach().numpy(), rtol=2e-6, atol=1e-7)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/confs"), reason="needs the reference's confs/ directory")
 @pytest.mark.parametrize("name", ["wanjinyou", "wanjinyou_big", "llff", "nerf-360", "free"])
-def test_presets_equal_the_reference_config_files(name):
-    """config.PRESETS / GROUP_DEFAULTS are data copied by hand from the reference's confs/ so that the GPU box (which has no
-    /root/reference) can run them: here they are tied to the files themselves, composed hydra-style from confs/ in place."""
+def test_presets_equal_the_reference_config_files(name, tmp_path):
+    """config.PRESETS / GROUP_DEFAULTS are data copied by hand from the reference's confs/: here they are tied to those files,
+    composed hydra-style by config.compose_yaml and recorded in tests/golden/reference_confs.json (tests/golden/make_confs.py)."""
+    import json
+    import yaml
     import f2_nerf_amd  # noqa: F401
     from f2_nerf_amd import config
-    want = config.compose_yaml("/root/reference/confs", name)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_confs.json")) as f:
+        want = json.load(f)[name]
     got = config.preset(name)
     def norm(flat):  # (PyYAML reads `1e-1` as a string; the C++ host parses the strings, so compare the values)
         out = {}
@@ -183,11 +185,20 @@ def test_presets_equal_the_reference_config_files(name):
     for group in ("train", "dataset", "renderer", "pts_sampler", "field", "shader"):
         assert norm(config.flatten({group: want[group]})) == norm(config.flatten({group: got[group]})), (name, group)
     assert want["mode"] == got["mode"] == "train" and want["is_continue"] == got["is_continue"]
-    # the launcher's argument handling (scripts/run.py's hydra overrides)
+    # the launcher's argument handling (scripts/run.py's hydra overrides), on a confs/ directory laid out as the reference's:
+    # one file per group under <group>/<option>.yaml, named by the experiment file's `defaults:` list
+    groups = ("train", "dataset", "renderer", "pts_sampler", "field", "shader")
+    root = {k: v for k, v in want.items() if k not in groups}
+    root["defaults"] = [{g: name + "_" + g} for g in groups] + ["_self_"]
+    for g in groups:
+        (tmp_path / g).mkdir()
+        (tmp_path / g / (name + "_" + g + ".yaml")).write_text(yaml.safe_dump(want[g]))
+    (tmp_path / (name + ".yaml")).write_text(yaml.safe_dump(root))
     from f2_nerf_amd import run
-    n, d, ov = run.parse_args(["--config-name=%s" % name, "--config-dir=/root/reference/confs", "case_name=ngp_fox", "+work_dir=/tmp/x",
+    n, d, ov = run.parse_args(["--config-name=%s" % name, "--config-dir=%s" % tmp_path, "case_name=ngp_fox", "+work_dir=/tmp/x",
                                "train.end_iter=100"])
     cfg = config.compose_yaml(d, n, ov)
+    assert {g: cfg[g] for g in groups if g != "train"} == {g: want[g] for g in groups if g != "train"}
     assert cfg["case_name"] == "ngp_fox" and cfg["work_dir"] == "/tmp/x" and cfg["train"]["end_iter"] == 100
 
 

@@ -811,8 +811,9 @@ def test_speculative_training_equals_sampling_after_the_update_on_the_emulator(r
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # what the driver runs at the end of a round, on the emulated stack: __graft_entry__.smoke() as it stands, and bench.py's main path
-# (two warm-up and three timed steps of 64-ray batches on a 2^14 table; no converged leg, no CPU baseline, no other configs) -- the
-# JSON line's fields and arithmetic, the two-deep pipeline's arguments, the kernel timers' bookkeeping.  Not a measurement of anything.
+# (two warm-up and three timed steps of 64-ray batches on a 2^14 table; with --full but no converged leg, no CPU baseline, no other
+# configs) -- the JSON line's fields and arithmetic, the two-deep pipeline's arguments, the kernel timers' bookkeeping -- and its plain
+# run with --dump-outputs.  Not a measurement of anything.
 # ---------------------------------------------------------------------------------------------------------------------------------
 def test_smoke_on_the_emulator(rt, monkeypatch, capsys):
     import __graft_entry__ as entry
@@ -830,7 +831,7 @@ def test_bench_main_path_on_the_emulator(rt, monkeypatch, capsys):
     # (the dominant call -- the gather of the large-batch path, what `roofline` is about -- is issued from 32768 samples per step on:
     # ~400 rays of the fresh fox scene, half a minute per step here: only with WEMU_FULL=1)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--rays", "400" if _FULL else "64", "--log2", "14", "--no-converged",
-                                      "--no-cpu-baseline", "--no-steady", "--other-configs", "0"])
+                                      "--no-cpu-baseline", "--no-steady", "--other-configs", "0", "--full"])
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
     bench.main()
@@ -844,6 +845,39 @@ def test_bench_main_path_on_the_emulator(rt, monkeypatch, capsys):
     if rf is not None:
         assert rf["bound"] == "hbm" and rf["peak"] == 8000.0 and rf["unit"] == "GB/s" and rf["launches"] == 3 and rf["bytes_per_sample"] == 592
         assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-4 and rf["traffic"] is None  # (no counter file for this table size)
+
+
+def test_plain_bench_run_and_its_outputs_on_the_emulator(rt, monkeypatch, capsys, tmp_path):
+    """bench.py without --full: the headline only (no steady-state region, no roofline, no CPU baseline, no converged leg, no other
+    configs, no scatter counters), and --dump-outputs: what the last timed step computed, as float32 / float64 .npy files well under
+    64 MB, identical from one run with the same arguments to the next."""
+    import json
+    import bench
+    monkeypatch.setattr(torch.cuda, "max_memory_allocated", lambda *a, **k: 0)
+    monkeypatch.setattr(torch.cuda, "max_memory_reserved", lambda *a, **k: 0)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    dumps = []
+    for run in range(2):
+        dumps.append(tmp_path / ("run%d" % run))
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--rays", "64", "--log2", "14",
+                                          "--dump-outputs", str(dumps[-1])])
+        bench.main()
+        line = json.loads([x for x in capsys.readouterr().out.splitlines() if x.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["unit"] == "ray-samples/s" and line["dtype"] == "f16"
+        assert line["value"] > 0 and abs(line["value"] - line["config"]["meaningful_samples_per_step"] * 3 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]
+        for key in ("steady_state", "roofline", "cpu_baseline", "converged", "other_configs", "scatter_counters", "training_representative"):
+            assert line[key] is None, key
+    names = sorted(p.name for p in dumps[0].iterdir())
+    assert names == sorted(p.name for p in dumps[1].iterdir())
+    assert {"loss.npy", "mse.npy", "sample_counts.npy", "hash_table_sample.npy", "field_mlp.npy", "color_mlp.npy"} <= set(names)
+    assert sum((dumps[0] / n).stat().st_size for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(dumps[0] / n), np.load(dumps[1] / n)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0, n
+        assert a.shape == b.shape and np.array_equal(a, b), n
+    loss, counts = np.load(dumps[0] / "loss.npy"), np.load(dumps[0] / "sample_counts.npy")
+    assert np.isfinite(loss).all() and counts[0] == 64 and counts[2] >= counts[3] > 0
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
