@@ -729,3 +729,52 @@ def composite_train(n_rays, se, f0, f0_stride, dt, t, rgb, bg, gt, var_w, disp_w
 def nonfinite_flags(n_a, a, n_b, b, flags, mirror=None):
     _ck(lib().f2n_nonfinite_flags_ex(_stream(), _i(n_a), _p(a, "f32", True), _i(n_b), _p(b, "f32", True), _p(flags, "i32"),
                                      _mapped(mirror)), "f2n_nonfinite_flags_ex")
+
+
+# ---------------------------------------------------------------- world-space queries and meshes
+def _lo3(lo):
+    return (_f * 3)(*(float(v) for v in lo))
+
+
+def oct_locate_warp(n, pts_world, tree_nodes, transes, out_pts, out_anchors):
+    """World points -> (warped points, anchors (trans_idx, leaf, 0) or (-1, -1, 0)) by octree descent (f2n_oct_locate_warp)."""
+    _ck(lib().f2n_oct_locate_warp(_stream(), _i(n), _p(pts_world, "f32"), _p(tree_nodes, "u8"), _p(transes, "u8"), _p(out_pts, "f32"),
+                                  _p(out_anchors, "i32")), "f2n_oct_locate_warp")
+
+
+def oct_locate_warp_grid(lo, step, nx, ny, nz, first_z, n_z, tree_nodes, transes, out_pts, out_anchors):
+    """The same for the grid points lo + step * (ix, iy, iz), iz in [first_z, first_z + n_z), x fastest."""
+    _ck(lib().f2n_oct_locate_warp_grid(_stream(), _lo3(lo), _f(step), _i(nx), _i(ny), _i(nz), _i(first_z), _i(n_z), _p(tree_nodes, "u8"),
+                                       _p(transes, "u8"), _p(out_pts, "f32"), _p(out_anchors, "i32")), "f2n_oct_locate_warp_grid")
+
+
+def located_compact(n, anchors, pts_warped, counts, start_end, total, out_pts, out_vol, out_src=None):
+    _ck(lib().f2n_located_compact(_stream(), _i(n), _p(anchors, "i32"), _p(pts_warped, "f32"), _p(counts, "i32"), _p(start_end, "i32"),
+                                  _p(total, "i32"), _p(out_pts, "f32"), _p(out_vol, "i32"), _p(out_src, "i32", True)),
+        "f2n_located_compact")
+
+
+def density_scatter(n, anchors, start_end, f0, density):
+    _ck(lib().f2n_density_scatter(_stream(), _i(n), _p(anchors, "i32"), _p(start_end, "i32"), _p(f0, "f32"), _p(density, "f32")),
+        "f2n_density_scatter")
+
+
+def mesh_from_grid(grid, level, lo=(0.0, 0.0, 0.0), step=1.0):
+    """Marching-tetrahedra iso-surface of a float32 grid [nz, ny, nx] (f2n_mesh_count -> f2n_mesh_emit): (verts [V,3], faces [F,3]).
+    Reads back the two totals only (they size the outputs)."""
+    nz, ny, nx = (int(v) for v in grid.shape)
+    dev = grid.device
+    n, c = nx * ny * nz, (nx - 1) * (ny - 1) * (nz - 1)
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    vc, vse = torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 2), dtype=torch.int32, device=dev)
+    fc, fse = torch.empty(c, dtype=torch.int32, device=dev), torch.empty((c, 2), dtype=torch.int32, device=dev)
+    totals = torch.empty(2, dtype=torch.int32, device=dev)
+    _ck(lib().f2n_mesh_count(_stream(), _i(nx), _i(ny), _i(nz), _p(grid, "f32"), _f(level), _p(mask, "u8"), _p(vc, "i32"), _p(vse, "i32"),
+                             _p(fc, "i32"), _p(fse, "i32"), _p(totals, "i32")), "f2n_mesh_count")
+    nv, nf = (int(v) for v in totals.cpu())
+    verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    if nv or nf:
+        _ck(lib().f2n_mesh_emit(_stream(), _i(nx), _i(ny), _i(nz), _p(grid, "f32"), _f(level), _lo3(lo), _f(step), _p(mask, "u8"),
+                                _p(vse, "i32"), _p(fse, "i32"), _p(verts, "f32"), _p(faces, "i32")), "f2n_mesh_emit")
+    return verts, faces

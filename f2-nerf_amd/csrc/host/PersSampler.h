@@ -134,6 +134,9 @@ class PersSampler : public PtsSampler {
   bool MaintenanceDueAt(int iter) const;  // ... of iteration `iter`
   SampleResultFlex FinishSamples(PendingSamples& p);
   std::tuple<Tensor, Tensor> GetEdgeSamples(int n_pts) override;
+  // world points [n,3] -> (warped [n,3], anchors [n,3] = (trans_idx, leaf, 0); (-1, -1, 0) where no listed leaf holds the point)
+  // (f2n_oct_locate_warp; RendererQuery.cpp)
+  std::tuple<Tensor, Tensor> LocatePoints(const Tensor& world);
   void UpdateOctNodes(const SampleResultFlex& sample_result, const Tensor& sampled_weights,
                       const Tensor& sampled_alpha) override;
   // UpdateOctNodes split for the training step: early stop + votes in one launch, then the rest (exchange, stats, maintenance)

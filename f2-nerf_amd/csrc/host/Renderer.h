@@ -64,6 +64,16 @@ struct RenderFront {
   bool consumed_deferred = false;
 };
 
+// The implicit grid of Renderer::DensityGrid: point (ix, iy, iz) = lo + step * i (f2n_oct_locate_warp_grid), n[k] points along axis k.
+// step = (longest side of the box) / res, so that the longest side has res cells; n[k] = round(extent_k / step) + 1 (at least 2).
+struct GridSpec {
+  float lo[3];
+  float step;
+  int n[3];
+};
+// Iso-surface of any float32 grid [nz, ny, nx] (f2n_mesh_count / f2n_mesh_emit): (verts [V,3] f32, faces [F,3] int32)
+std::tuple<Tensor, Tensor> MeshFromGrid(const Tensor& grid, float level, const float lo[3], float step);
+
 struct TrainOutputs {
   Tensor losses;  // device [8]: loss, color, var, disp, tv, mse, 0, 0 (f2n_train_loss)
   Tensor colors;
@@ -264,6 +274,17 @@ class Renderer : public Pipe {
   // forward + ExpRunner::Train's loss + backward into the gradient buffers, without the autograd tape
   TrainOutputs TrainForwardBackward(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds, const Tensor& gt_colors,
                                     const Tensor& emb_idx, float var_w, float disp_w, float tv_w);
+
+  // World-space density (RendererQuery.cpp): exp(f0 - 3) at world points [n,3], exactly 0 where no listed leaf holds the point;
+  // on the grid of MakeGridSpec as [nz, ny, nx] (x fastest), in z-slabs of at most density_slab_points_ points; and the
+  // iso-surface of that grid at `level`.  Free of side effects on training (no keyed draws, no occupancy votes, the pre-pass
+  // feature cache kept); the caller flushes a streaming step first (ExpRunner::FinishPending).
+  Tensor QueryDensity(const Tensor& world);
+  Tensor DensityGrid(const std::vector<float>& lo, const std::vector<float>& hi, int res);
+  std::tuple<Tensor, Tensor> ExtractMesh(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level);
+  static GridSpec MakeGridSpec(const std::vector<float>& lo, const std::vector<float>& hi, int res);
+  Tensor DensityOfLocated(const Tensor& warped, const Tensor& anchors);
+  int64_t density_slab_points_ = int64_t(1) << 22;
 
   int LoadStates(const std::vector<Tensor>& states, int idx) override;
   std::vector<Tensor> States() override;

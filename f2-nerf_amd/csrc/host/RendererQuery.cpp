@@ -1,0 +1,117 @@
+// World-space density queries and iso-surface extraction (csrc/octree.hip; include/f2n_abi.h, "World-space queries and meshes").
+// None of this is on the training path: the queries draw nothing from the keyed streams, touch no occupancy statistics and leave
+// the pre-pass feature cache of Hash3DAnchored (prepass_x_) as they found it.  Callers flush a streaming step first
+// (ExpRunner::FinishPending, as SaveCheckpoint does).
+#include <cmath>
+
+#include "Renderer.h"
+
+namespace f2n {
+
+std::tuple<Tensor, Tensor> PersSampler::LocatePoints(const Tensor& world) {
+  torch::NoGradGuard g;
+  Tensor w = world.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  const int64_t n = w.size(0);
+  TORCH_CHECK(n <= INT32_MAX, "too many points");
+  Tensor warped = torch::empty({n, 3}, DevF32()), anchors = torch::empty({n, 3}, DevI32());
+  auto& o = *pers_octree_;
+  F2N_CALL(f2n_oct_locate_warp(CurStream(), (int) n, F32P(w), VoidP(o.tree_nodes_gpu_), VoidP(o.pers_trans_gpu_), F32P(warped),
+                               I32P(anchors)));
+  return {warped, anchors};
+}
+
+Tensor Renderer::DensityOfLocated(const Tensor& warped, const Tensor& anchors) {
+  torch::NoGradGuard g;
+  auto* field = static_cast<Hash3DAnchored*>(scene_field_.get());
+  const int64_t n = anchors.size(0);
+  Tensor density = torch::empty({n}, DevF32());
+  if (n == 0) return density;
+  Tensor counts = torch::empty({n}, DevI32()), se = torch::empty({n, 2}, DevI32()), total = torch::empty({1}, DevI32());
+  Tensor cpts = torch::empty({n, 3}, DevF32()), cvol = torch::empty({n}, DevI32());
+  F2N_CALL(f2n_located_compact(CurStream(), (int) n, I32P(anchors), F32P(warped), I32P(counts), I32P(se), I32P(total), F32P(cpts),
+                               I32P(cvol), nullptr));
+  // The field kernels take their row count from the host: the one read-back of a query (the densities stay on the device)
+  const int m = total.item<int>();
+  Tensor f0 = torch::zeros({1}, DevF32());
+  if (m > 0) {
+    Tensor keep = field->prepass_x_;  // a batch sampled ahead may still be served from this cache
+    f0 = field->QueryDensityPreAct(cpts.narrow(0, 0, m), cvol.narrow(0, 0, m), /*keep_features=*/false);
+    field->prepass_x_ = keep;
+  }
+  F2N_CALL(f2n_density_scatter(CurStream(), (int) n, I32P(anchors), I32P(se), F32P(f0), F32P(density)));
+  return density;
+}
+
+Tensor Renderer::QueryDensity(const Tensor& world) {
+  auto* sampler = static_cast<PersSampler*>(pts_sampler_.get());
+  auto located = sampler->LocatePoints(world);
+  return DensityOfLocated(std::get<0>(located), std::get<1>(located));
+}
+
+GridSpec Renderer::MakeGridSpec(const std::vector<float>& lo, const std::vector<float>& hi, int res) {
+  TORCH_CHECK(lo.size() == 3 && hi.size() == 3, "lo / hi must have three coordinates");
+  TORCH_CHECK(res >= 1 && res <= 1024, "resolution must be in [1, 1024]");
+  GridSpec s;
+  float ext[3], longest = 0.f;
+  for (int k = 0; k < 3; k++) {
+    ext[k] = hi[k] - lo[k];
+    TORCH_CHECK(ext[k] > 0.f && std::isfinite(ext[k]), "empty or invalid box");
+    longest = std::max(longest, ext[k]);
+    s.lo[k] = lo[k];
+  }
+  s.step = longest / (float) res;
+  for (int k = 0; k < 3; k++) s.n[k] = std::max(2, (int) std::lround(ext[k] / s.step) + 1);
+  return s;
+}
+
+Tensor Renderer::DensityGrid(const std::vector<float>& lo, const std::vector<float>& hi, int res) {
+  torch::NoGradGuard g;
+  const GridSpec s = MakeGridSpec(lo, hi, res);
+  const int nx = s.n[0], ny = s.n[1], nz = s.n[2];
+  const int64_t plane = (int64_t) nx * ny;
+  // z-slabs of at most density_slab_points_ points: the gather's plane workspace ([8][n][4] h16, 64 B per point) and the
+  // compaction buffers stay bounded at any resolution
+  const int slab_z = (int) std::max<int64_t>(1, std::min<int64_t>(nz, density_slab_points_ / plane));
+  Tensor out = torch::empty({nz, ny, nx}, DevF32());
+  auto& o = *static_cast<PersSampler*>(pts_sampler_.get())->pers_octree_;
+  const int64_t cap = plane * slab_z;
+  Tensor warped = torch::empty({cap, 3}, DevF32()), anchors = torch::empty({cap, 3}, DevI32());
+  for (int z0 = 0; z0 < nz; z0 += slab_z) {
+    const int n_z = std::min(slab_z, nz - z0);
+    const int64_t n = plane * n_z;
+    Tensor w = warped.narrow(0, 0, n), a = anchors.narrow(0, 0, n);
+    F2N_CALL(f2n_oct_locate_warp_grid(CurStream(), s.lo, s.step, nx, ny, nz, z0, n_z, VoidP(o.tree_nodes_gpu_), VoidP(o.pers_trans_gpu_),
+                                      F32P(w), I32P(a)));
+    out.narrow(0, z0, n_z).view({-1}).copy_(DensityOfLocated(w, a));
+  }
+  return out;
+}
+
+std::tuple<Tensor, Tensor> MeshFromGrid(const Tensor& grid, float level, const float lo[3], float step) {
+  torch::NoGradGuard g;
+  Tensor gr = grid.to(torch::kCUDA, torch::kFloat32).contiguous();
+  TORCH_CHECK(gr.dim() == 3, "grid must be [nz, ny, nx]");
+  const int nz = (int) gr.size(0), ny = (int) gr.size(1), nx = (int) gr.size(2);
+  if (nx < 2 || ny < 2 || nz < 2) return {torch::empty({0, 3}, DevF32()), torch::empty({0, 3}, DevI32())};
+  const int64_t n_corners = (int64_t) nx * ny * nz, n_cells = (int64_t) (nx - 1) * (ny - 1) * (nz - 1);
+  Tensor mask = torch::empty({n_corners}, torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA));
+  Tensor vc = torch::empty({n_corners}, DevI32()), vse = torch::empty({n_corners, 2}, DevI32());
+  Tensor fc = torch::empty({n_cells}, DevI32()), fse = torch::empty({n_cells, 2}, DevI32()), totals = torch::empty({2}, DevI32());
+  F2N_CALL(f2n_mesh_count(CurStream(), nx, ny, nz, F32P(gr), level, mask.data_ptr<uint8_t>(), I32P(vc), I32P(vse), I32P(fc), I32P(fse),
+                          I32P(totals)));
+  Tensor t = totals.cpu();  // the two totals: the only read-back (they size the outputs)
+  const int64_t nv = t.data_ptr<int32_t>()[0], nf = t.data_ptr<int32_t>()[1];
+  Tensor verts = torch::empty({nv, 3}, DevF32()), faces = torch::empty({nf, 3}, DevI32());
+  if (nv > 0 || nf > 0)
+    F2N_CALL(f2n_mesh_emit(CurStream(), nx, ny, nz, F32P(gr), level, lo, step, mask.data_ptr<uint8_t>(), I32P(vse), I32P(fse),
+                           F32P(verts), I32P(faces)));
+  return {verts, faces};
+}
+
+std::tuple<Tensor, Tensor> Renderer::ExtractMesh(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level) {
+  const GridSpec s = MakeGridSpec(lo, hi, res);
+  Tensor grid = DensityGrid(lo, hi, res);
+  return MeshFromGrid(grid, level, s.lo, s.step);
+}
+
+}  // namespace f2n

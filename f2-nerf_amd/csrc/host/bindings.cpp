@@ -99,6 +99,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readonly("n_images", &Dataset::n_images_)
       .def_readonly("height", &Dataset::height_)
       .def_readonly("width", &Dataset::width_);
+  // the implicit grid of ExpRunner.density_grid: (step, nx, ny, nz), point (ix, iy, iz) = lo + step * i (no device needed)
+  m.def("grid_spec", [](const std::vector<float>& lo, const std::vector<float>& hi, int res) {
+    GridSpec s = Renderer::MakeGridSpec(lo, hi, res);
+    return py::make_tuple(s.step, s.n[0], s.n[1], s.n[2]);
+  });
+  // iso-surface of any float32 grid [nz, ny, nx] by marching tetrahedra (f2n_mesh_count / f2n_mesh_emit): (verts, faces)
+  m.def("mesh_from_grid",
+        [](const Tensor& grid, float level, const std::vector<float>& lo, float step) {
+          TORCH_CHECK(lo.size() == 3, "lo must have three coordinates");
+          auto t = MeshFromGrid(grid, level, lo.data(), step);
+          return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
+        },
+        py::arg("grid"), py::arg("level"), py::arg("lo") = std::vector<float>{0.f, 0.f, 0.f}, py::arg("step") = 1.f);
   m.def("dp_set_table_buckets", [](int n) { DataParallel::table_buckets = n; });  // table all-reduce buckets of the next attach (A/B)
   // data-parallel replicas draw stream `rank` of every keyed purpose (KeyedDraws.h; the native attach sets it itself)
   m.def("dp_set_replica", [](int rank) { KeyedUniforms::SetReplica(rank); });
@@ -250,6 +263,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              r.sync_.pipelined = true;
            })
       .def("flush", [](ExpRunner& r) { py::gil_scoped_release no_gil; r.FinishPending(); })
+      // world-space queries of the scene (Renderer::QueryDensity & co.): a streaming step is flushed first, as save_checkpoint does
+      .def("locate_points",  // world [n,3] -> [warped [n,3], anchors [n,3] = (trans_idx, leaf, 0) or (-1, -1, 0)]
+           [](ExpRunner& r, const Tensor& world) {
+             py::gil_scoped_release no_gil;
+             r.FinishPending();
+             auto t = SamplerOf(r)->LocatePoints(world);
+             return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
+           })
+      .def("query_density",  // world [n,3] -> density [n] = exp(f0 - 3), exactly 0 where no leaf holds the point
+           [](ExpRunner& r, const Tensor& world) {
+             py::gil_scoped_release no_gil;
+             r.FinishPending();
+             return r.renderer_->QueryDensity(world);
+           })
+      .def("density_grid",  // [nz, ny, nx] densities on the grid of grid_spec(lo, hi, res)
+           [](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res) {
+             py::gil_scoped_release no_gil;
+             r.FinishPending();
+             return r.renderer_->DensityGrid(lo, hi, res);
+           },
+           py::arg("lo"), py::arg("hi"), py::arg("res"))
+      .def("extract_mesh",  // (verts [V,3] f32 in the scene's normalised frame, faces [F,3] int32) of the density grid at `level`
+           [](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res, float level) {
+             py::gil_scoped_release no_gil;
+             r.FinishPending();
+             auto t = r.renderer_->ExtractMesh(lo, hi, res, level);
+             return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
+           },
+           py::arg("lo"), py::arg("hi"), py::arg("res"), py::arg("level"))
+      .def_property("density_slab_points",  // points per z-slab of density_grid (bounds its workspaces)
+                    [](ExpRunner& r) { return r.renderer_->density_slab_points_; },
+                    [](ExpRunner& r, int64_t n) { r.renderer_->density_slab_points_ = std::max<int64_t>(1, n); })
       .def("attach_data_parallel",  // native RCCL exchanges, issued from C++ inside TrainStep (DataParallel.h); collective
            [](ExpRunner& r, int rank, int world, const py::bytes& unique_id, bool overlap, bool hooks_for_one_rank) {
              std::string s = unique_id;

@@ -17,6 +17,7 @@
 //                             subtrees, summed along the ancestor chain, where a subdivided leaf counts 9 nodes.
 // Trees have at most a few 1e5 nodes and <= 24 levels; every kernel is one thread per node with an ancestor walk.
 #include "f2n_dev.h"
+#include "rows_dev.h"  // (F2N_DENSITY_SHIFT: the world-space queries at the end)
 
 #define F2N_INIT_NODE_STAT 1000  // PersSampler.h:10
 
@@ -263,3 +264,368 @@ int f2n_oct_subdivide(void* stream, int n_nodes, const void* nodes, const int32_
 }
 
 }  // extern "C"
+
+// =====================================================================================================================
+// World-space queries of a trained scene and iso-surface extraction (include/f2n_abi.h, "World-space queries and meshes").
+//   locate:  a world point -> the octree leaf that holds it (the descent the ray walk of PersSampler.cu:54-152 never makes
+//            for a single point) -> its perspective warp (f2n_warp), in the anchor layout of GetSamples
+//   density: count -> f2n_segment_scan -> compact of the non-empty points, and the scatter of exp(f0 - 3) back to every point
+//   mesh:    marching tetrahedra on the Kuhn split of every grid cell (six tetrahedra around the (0,0,0)-(1,1,1) diagonal)
+// =====================================================================================================================
+
+#define F2N_OCT_MAX_DEPTH 32  // a descent longer than this is a corrupt tree: the point is reported empty
+
+namespace {
+
+// Single roundings that the compiler may not contract into an FMA.  (The CPU emulation of tests/wave_emul/ has no __f*_rn
+// intrinsics; it compiles with -ffp-contract=off like the product, so the plain operators are the same operations there.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define F2N_ADD_RN(a, b) __fadd_rn(a, b)
+#define F2N_SUB_RN(a, b) __fsub_rn(a, b)
+#define F2N_MUL_RN(a, b) __fmul_rn(a, b)
+#define F2N_DIV_RN(a, b) __fdiv_rn(a, b)
+#else
+#define F2N_ADD_RN(a, b) ((a) + (b))
+#define F2N_SUB_RN(a, b) ((a) - (b))
+#define F2N_MUL_RN(a, b) ((a) * (b))
+#define F2N_DIV_RN(a, b) ((a) / (b))
+#endif
+
+// The grid point of index (ix, iy, iz): lo + step * i with two roundings, never contracted into an FMA, so that float32 numpy
+// (lo + np.float32(step) * np.float32(i)) restates it bit for bit.
+__device__ __forceinline__ float grid_coord(float lo, float step, int i) { return F2N_ADD_RN(lo, F2N_MUL_RN(step, (float) i)); }
+
+// Leaf of the point p, or -1 when p lies outside the root cube, in a missing child slot, or in a leaf with trans_idx < 0
+// (exactly the nodes the ray walk never lists).  *trans receives the leaf's trans_idx.
+__device__ __forceinline__ int oct_locate(const F2nTreeNode* __restrict__ nodes, const float p[3], int* trans) {
+  const F2nTreeNode& root = nodes[0];
+  const float h = root.side_len * .5f;
+#pragma unroll
+  for (int k = 0; k < 3; k++)
+    if (!(p[k] >= root.center[k] - h && p[k] <= root.center[k] + h)) return -1;  // (NaN: empty as well)
+  int u = 0;
+  for (int depth = 0; depth < F2N_OCT_MAX_DEPTH; depth++) {
+    const F2nTreeNode& nd = nodes[u];
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < 8; c++) any |= nd.childs[c] >= 0;
+    if (!any) {  // a node with no children is a leaf (PersSampler.cu:98-110)
+      *trans = nd.trans_idx;
+      return nd.trans_idx >= 0 ? u : -1;
+    }
+    // child slot order of ConstructTreeNode (PersSampler.cpp:397-401): 4 * (x >= cx) + 2 * (y >= cy) + (z >= cz)
+    const int st = 4 * (int) (p[0] >= nd.center[0]) + 2 * (int) (p[1] >= nd.center[1]) + (int) (p[2] >= nd.center[2]);
+    int ch = nd.childs[0];  // (selected without indexing the record by a run-time value held in registers)
+#pragma unroll
+    for (int c = 1; c < 8; c++) ch = st == c ? nd.childs[c] : ch;
+    if (ch < 0) return -1;
+    u = ch;
+  }
+  return -1;
+}
+
+template <bool GRID>
+__global__ void __launch_bounds__(256) oct_locate_warp_kernel(int n, const float* __restrict__ pts_world, float lo0, float lo1, float lo2,
+                                                              float step, int nx, int ny, int first_z,
+                                                              const F2nTreeNode* __restrict__ nodes,
+                                                              const F2nTransInfo* __restrict__ transes, float* __restrict__ out_pts,
+                                                              int32_t* __restrict__ out_anchors) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float p[3];
+  if (GRID) {
+    const int64_t plane = (int64_t) nx * ny;
+    const int iz = first_z + (int) (i / plane);
+    const int64_t r = i % plane;
+    p[0] = grid_coord(lo0, step, (int) (r % nx));
+    p[1] = grid_coord(lo1, step, (int) (r / nx));
+    p[2] = grid_coord(lo2, step, iz);
+  } else {
+    p[0] = pts_world[i * 3 + 0];
+    p[1] = pts_world[i * 3 + 1];
+    p[2] = pts_world[i * 3 + 2];
+  }
+  int trans = -1;
+  const int leaf = oct_locate(nodes, p, &trans);
+  float w[3] = {0.f, 0.f, 0.f};
+  if (leaf >= 0) f2n_warp(transes + trans, p, w);
+  out_pts[i * 3 + 0] = w[0];
+  out_pts[i * 3 + 1] = w[1];
+  out_pts[i * 3 + 2] = w[2];
+  out_anchors[i * 3 + 0] = leaf >= 0 ? trans : -1;
+  out_anchors[i * 3 + 1] = leaf;
+  out_anchors[i * 3 + 2] = 0;
+}
+
+__global__ void __launch_bounds__(256) located_count_kernel(int n, const int32_t* __restrict__ anchors, int32_t* __restrict__ counts) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) counts[i] = anchors[i * 3] >= 0 ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(256) located_compact_kernel(int n, const int32_t* __restrict__ anchors, const float* __restrict__ pts,
+                                                             const int32_t* __restrict__ start_end, float* __restrict__ out_pts,
+                                                             int32_t* __restrict__ out_vol, int32_t* __restrict__ out_src) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int vol = anchors[i * 3];
+  if (vol < 0) return;
+  const int64_t k = start_end[i * 2];
+  out_pts[k * 3 + 0] = pts[i * 3 + 0];
+  out_pts[k * 3 + 1] = pts[i * 3 + 1];
+  out_pts[k * 3 + 2] = pts[i * 3 + 2];
+  out_vol[k] = vol;
+  if (out_src != nullptr) out_src[k] = (int32_t) i;
+}
+
+__global__ void __launch_bounds__(256) density_scatter_kernel(int n, const int32_t* __restrict__ anchors, const int32_t* __restrict__ start_end,
+                                                             const float* __restrict__ f0, float* __restrict__ density) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  density[i] = anchors[i * 3] >= 0 ? expf(f0[start_end[i * 2]] - F2N_DENSITY_SHIFT) : 0.f;  // TruncExp(f0 - 3), Renderer.cpp:101-104
+}
+
+// ---- marching tetrahedra ------------------------------------------------------------------------------------------------
+// Corner offsets are 3-bit masks (x = 1, y = 2, z = 4).  Tetrahedron t of a cell, for the axis order (a, b, c) of row t:
+// (0, a, a|b, 7).  Its orientation is the parity of the axis permutation.
+__constant__ int8_t c_tet_axes[6][3] = {{1, 2, 4}, {1, 4, 2}, {2, 1, 4}, {2, 4, 1}, {4, 1, 2}, {4, 2, 1}};
+__constant__ int8_t c_tet_even[6] = {1, 0, 0, 1, 1, 0};
+// Edge type of an offset mask: +x, +y, +z, +xy, +xz, +yz, +xyz = 0..6 (-1: mask 0)
+__constant__ int8_t c_edge_type[8] = {-1, 0, 1, 3, 2, 4, 5, 6};
+// Case of a tetrahedron by its inside mask (bit v: tet vertex v is inside): {kind, i, j, k, l, flip}.  kind 1: one corner i alone
+// on its side (inside or outside), j < k < l the others -> triangle (ij, ik, il); kind 3: i < j inside, k < l outside -> triangles
+// (ik, il, jl), (ik, jl, jk).  flip: those triangles face inward on a positively oriented tetrahedron and are reversed (second and
+// third vertex swapped); a negatively oriented one reverses once more.  (Derived from the geometry of the (0, x, x|y, 7) tet.)
+__constant__ int8_t c_tet_case[16][6] = {
+    {0, 0, 1, 2, 3, 0},  // 0000
+    {1, 0, 1, 2, 3, 0},  // 0001
+    {1, 1, 0, 2, 3, 1},  // 0010
+    {3, 0, 1, 2, 3, 0},  // 0011
+    {1, 2, 0, 1, 3, 0},  // 0100
+    {3, 0, 2, 1, 3, 1},  // 0101
+    {3, 1, 2, 0, 3, 0},  // 0110
+    {1, 3, 0, 1, 2, 0},  // 0111
+    {1, 3, 0, 1, 2, 1},  // 1000
+    {3, 0, 3, 1, 2, 0},  // 1001
+    {3, 1, 3, 0, 2, 1},  // 1010
+    {1, 2, 0, 1, 3, 1},  // 1011
+    {3, 2, 3, 0, 1, 0},  // 1100
+    {1, 1, 0, 2, 3, 0},  // 1101
+    {1, 0, 1, 2, 3, 1},  // 1110
+    {0, 0, 1, 2, 3, 0},  // 1111
+};
+__constant__ int8_t c_tri_count[4] = {0, 1, 1, 2};
+
+__device__ __forceinline__ int64_t corner_index(int x, int y, int z, int nx, int ny) { return ((int64_t) z * ny + y) * nx + x; }
+
+// Vertex count pass: bit t of edge_mask[c] = edge of type t from corner c to a corner inside the grid crosses the level.
+__global__ void __launch_bounds__(256) mesh_vert_count_kernel(int nx, int ny, int nz, const float* __restrict__ g, float level,
+                                                             uint8_t* __restrict__ edge_mask, int32_t* __restrict__ counts) {
+  const int64_t c = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= (int64_t) nx * ny * nz) return;
+  const int x = (int) (c % nx), y = (int) ((c / nx) % ny), z = (int) (c / ((int64_t) nx * ny));
+  const bool in0 = g[c] > level;
+  uint32_t m = 0;
+#pragma unroll
+  for (int o = 1; o < 8; o++) {
+    const int dx = o & 1, dy = (o >> 1) & 1, dz = (o >> 2) & 1;
+    if (x + dx >= nx || y + dy >= ny || z + dz >= nz) continue;
+    const bool in1 = g[corner_index(x + dx, y + dy, z + dz, nx, ny)] > level;
+    if (in0 != in1) m |= 1u << c_edge_type[o];
+  }
+  edge_mask[c] = (uint8_t) m;
+  counts[c] = __popc(m);
+}
+
+__device__ __forceinline__ int cell_mask(int x, int y, int z, int nx, int ny, const float* __restrict__ g, float level) {
+  int m = 0;
+#pragma unroll
+  for (int o = 0; o < 8; o++)
+    m |= (g[corner_index(x + (o & 1), y + ((o >> 1) & 1), z + ((o >> 2) & 1), nx, ny)] > level ? 1 : 0) << o;
+  return m;  // bit o: cell corner of offset o is inside
+}
+
+__device__ __forceinline__ int tet_inside(int cm, int t) {
+  const int a = c_tet_axes[t][0], ab = a | c_tet_axes[t][1];
+  return ((cm >> 0) & 1) | (((cm >> a) & 1) << 1) | (((cm >> ab) & 1) << 2) | (((cm >> 7) & 1) << 3);
+}
+
+__global__ void __launch_bounds__(256) mesh_face_count_kernel(int nx, int ny, int nz, const float* __restrict__ g, float level,
+                                                             int32_t* __restrict__ counts) {
+  const int cx = nx - 1, cy = ny - 1;
+  const int64_t c = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= (int64_t) cx * cy * (nz - 1)) return;
+  const int x = (int) (c % cx), y = (int) ((c / cx) % cy), z = (int) (c / ((int64_t) cx * cy));
+  const int cm = cell_mask(x, y, z, nx, ny, g, level);
+  int n = 0;
+  if (cm != 0 && cm != 255)
+    for (int t = 0; t < 6; t++) n += c_tri_count[c_tet_case[tet_inside(cm, t)][0]];
+  counts[c] = n;
+}
+
+__global__ void __launch_bounds__(256) mesh_vert_emit_kernel(int nx, int ny, int nz, const float* __restrict__ g, float level, float lo0,
+                                                            float lo1, float lo2, float step, const uint8_t* __restrict__ edge_mask,
+                                                            const int32_t* __restrict__ start_end, float* __restrict__ verts) {
+  const int64_t c = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= (int64_t) nx * ny * nz) return;
+  const uint32_t m = edge_mask[c];
+  if (m == 0) return;
+  const int x = (int) (c % nx), y = (int) ((c / nx) % ny), z = (int) (c / ((int64_t) nx * ny));
+  const float ga = g[c];
+  const float pa[3] = {grid_coord(lo0, step, x), grid_coord(lo1, step, y), grid_coord(lo2, step, z)};
+  int64_t v = start_end[c * 2];
+#pragma unroll
+  for (int o = 1; o < 8; o++) {
+    const int t = c_edge_type[o];
+    if (!((m >> t) & 1)) continue;
+    // (the loop over o visits types 0, 1, 3, 2, 4, 5, 6: the slot is the rank of t among the set bits, not the visit order)
+    const int64_t slot = v + __popc(m & ((1u << t) - 1u));
+    const int dx = o & 1, dy = (o >> 1) & 1, dz = (o >> 2) & 1;
+    const float gb = g[corner_index(x + dx, y + dy, z + dz, nx, ny)];
+    const float s = F2N_DIV_RN(F2N_SUB_RN(level, ga), F2N_SUB_RN(gb, ga));
+    const float pb[3] = {grid_coord(lo0, step, x + dx), grid_coord(lo1, step, y + dy), grid_coord(lo2, step, z + dz)};
+#pragma unroll
+    for (int k = 0; k < 3; k++) verts[slot * 3 + k] = F2N_ADD_RN(pa[k], F2N_MUL_RN(s, F2N_SUB_RN(pb[k], pa[k])));
+  }
+}
+
+// id of the vertex on the edge between cell corners of offsets oa and ob (one dominates the other on a Kuhn tetrahedron)
+__device__ __forceinline__ int32_t edge_vertex(int x, int y, int z, int nx, int ny, int oa, int ob, const uint8_t* __restrict__ edge_mask,
+                                               const int32_t* __restrict__ start_end) {
+  const int lo = (oa & ob) == oa ? oa : ob;
+  const int t = c_edge_type[oa ^ ob];
+  const int64_t c = corner_index(x + (lo & 1), y + ((lo >> 1) & 1), z + ((lo >> 2) & 1), nx, ny);
+  return start_end[c * 2] + __popc((uint32_t) edge_mask[c] & ((1u << t) - 1u));
+}
+
+__global__ void __launch_bounds__(256) mesh_face_emit_kernel(int nx, int ny, int nz, const float* __restrict__ g, float level,
+                                                            const uint8_t* __restrict__ edge_mask, const int32_t* __restrict__ vert_se,
+                                                            const int32_t* __restrict__ face_se, int32_t* __restrict__ faces) {
+  const int cx = nx - 1, cy = ny - 1;
+  const int64_t c = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= (int64_t) cx * cy * (nz - 1)) return;
+  if (face_se[c * 2] == face_se[c * 2 + 1]) return;
+  const int x = (int) (c % cx), y = (int) ((c / cx) % cy), z = (int) (c / ((int64_t) cx * cy));
+  const int cm = cell_mask(x, y, z, nx, ny, g, level);
+  int64_t f = face_se[c * 2];
+  for (int t = 0; t < 6; t++) {
+    const int a = c_tet_axes[t][0], ab = a | c_tet_axes[t][1];
+    const int mask = tet_inside(cm, t);
+    const int kind = c_tet_case[mask][0];
+    if (kind == 0) continue;
+    // tet vertex v -> cell corner offset (0, a, a|b, 7), without a private array
+    auto off = [a, ab](int v) { return v == 0 ? 0 : v == 1 ? a : v == 2 ? ab : 7; };
+    const int oi = off(c_tet_case[mask][1]), oj = off(c_tet_case[mask][2]), ok = off(c_tet_case[mask][3]),
+              ol = off(c_tet_case[mask][4]);
+    const bool flip = (c_tet_case[mask][5] != 0) != (c_tet_even[t] == 0);
+    int32_t tri[2][3];
+    int n_tri = 1;
+    if (kind == 1) {
+      tri[0][0] = edge_vertex(x, y, z, nx, ny, oi, oj, edge_mask, vert_se);
+      tri[0][1] = edge_vertex(x, y, z, nx, ny, oi, ok, edge_mask, vert_se);
+      tri[0][2] = edge_vertex(x, y, z, nx, ny, oi, ol, edge_mask, vert_se);
+    } else {
+      const int32_t vik = edge_vertex(x, y, z, nx, ny, oi, ok, edge_mask, vert_se);
+      const int32_t vil = edge_vertex(x, y, z, nx, ny, oi, ol, edge_mask, vert_se);
+      const int32_t vjl = edge_vertex(x, y, z, nx, ny, oj, ol, edge_mask, vert_se);
+      const int32_t vjk = edge_vertex(x, y, z, nx, ny, oj, ok, edge_mask, vert_se);
+      tri[0][0] = vik; tri[0][1] = vil; tri[0][2] = vjl;
+      tri[1][0] = vik; tri[1][1] = vjl; tri[1][2] = vjk;
+      n_tri = 2;
+    }
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      if (q >= n_tri) break;
+      faces[f * 3 + 0] = tri[q][0];
+      faces[f * 3 + 1] = flip ? tri[q][2] : tri[q][1];
+      faces[f * 3 + 2] = flip ? tri[q][1] : tri[q][2];
+      f++;
+    }
+  }
+}
+
+}  // namespace
+
+int f2n_oct_locate_warp(void* stream, int n, const float* pts_world, const void* tree_nodes, const void* transes, float* out_pts_warped,
+                        int32_t* out_anchors) {
+  if (n < 0 || (n > 0 && (pts_world == nullptr || tree_nodes == nullptr || transes == nullptr || out_pts_warped == nullptr ||
+                          out_anchors == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  hipLaunchKernelGGL(oct_locate_warp_kernel<false>, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, pts_world, 0.f, 0.f,
+                     0.f, 0.f, 1, 1, 0, (const F2nTreeNode*) tree_nodes, (const F2nTransInfo*) transes, out_pts_warped, out_anchors);
+  return f2n_launch_status();
+}
+
+int f2n_oct_locate_warp_grid(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int first_z, int n_z,
+                             const void* tree_nodes, const void* transes, float* out_pts_warped, int32_t* out_anchors) {
+  if (lo == nullptr || nx <= 0 || ny <= 0 || nz <= 0 || first_z < 0 || n_z < 0 || first_z + (int64_t) n_z > nz) return F2N_ERR_INVALID_ARG;
+  const int64_t n = (int64_t) nx * ny * n_z;
+  if (n > 0x7fffffff) return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  if (tree_nodes == nullptr || transes == nullptr || out_pts_warped == nullptr || out_anchors == nullptr) return F2N_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(oct_locate_warp_kernel<true>, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, (int) n, nullptr, lo[0],
+                     lo[1], lo[2], step, nx, ny, first_z, (const F2nTreeNode*) tree_nodes, (const F2nTransInfo*) transes, out_pts_warped,
+                     out_anchors);
+  return f2n_launch_status();
+}
+
+int f2n_located_compact(void* stream, int n, const int32_t* anchors, const float* pts_warped, int32_t* counts, int32_t* start_end,
+                        int32_t* total, float* out_pts, int32_t* out_vol, int32_t* out_src) {
+  if (n < 0 || anchors == nullptr || pts_warped == nullptr || counts == nullptr || start_end == nullptr || total == nullptr ||
+      out_pts == nullptr || out_vol == nullptr)
+    return F2N_ERR_INVALID_ARG;
+  if (n > 0) {
+    hipLaunchKernelGGL(located_count_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, anchors, counts);
+    int e = f2n_launch_status();
+    if (e != F2N_OK) return e;
+  }
+  int e = f2n_segment_scan(stream, n, counts, start_end, total);
+  if (e != F2N_OK || n == 0) return e;
+  hipLaunchKernelGGL(located_compact_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, anchors, pts_warped,
+                     start_end, out_pts, out_vol, out_src);
+  return f2n_launch_status();
+}
+
+int f2n_density_scatter(void* stream, int n, const int32_t* anchors, const int32_t* start_end, const float* f0, float* density) {
+  if (n < 0 || (n > 0 && (anchors == nullptr || start_end == nullptr || density == nullptr))) return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  hipLaunchKernelGGL(density_scatter_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, anchors, start_end, f0,
+                     density);
+  return f2n_launch_status();
+}
+
+static bool mesh_dims_ok(int nx, int ny, int nz) {
+  return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t) nx * ny * nz <= 0x7fffffff;
+}
+
+int f2n_mesh_count(void* stream, int nx, int ny, int nz, const float* grid, float level, uint8_t* edge_mask, int32_t* vert_counts,
+                   int32_t* vert_start_end, int32_t* face_counts, int32_t* face_start_end, int32_t* totals) {
+  if (!mesh_dims_ok(nx, ny, nz) || grid == nullptr || edge_mask == nullptr || vert_counts == nullptr || vert_start_end == nullptr ||
+      face_counts == nullptr || face_start_end == nullptr || totals == nullptr)
+    return F2N_ERR_INVALID_ARG;
+  const int64_t n_corners = (int64_t) nx * ny * nz, n_cells = (int64_t) (nx - 1) * (ny - 1) * (nz - 1);
+  hipLaunchKernelGGL(mesh_vert_count_kernel, dim3(f2n_div_up(n_corners, 256)), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, grid, level,
+                     edge_mask, vert_counts);
+  int e = f2n_launch_status();
+  if (e != F2N_OK) return e;
+  hipLaunchKernelGGL(mesh_face_count_kernel, dim3(f2n_div_up(n_cells, 256)), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, grid, level,
+                     face_counts);
+  if ((e = f2n_launch_status()) != F2N_OK) return e;
+  if ((e = f2n_segment_scan(stream, (int) n_corners, vert_counts, vert_start_end, totals)) != F2N_OK) return e;
+  return f2n_segment_scan(stream, (int) n_cells, face_counts, face_start_end, totals + 1);
+}
+
+int f2n_mesh_emit(void* stream, int nx, int ny, int nz, const float* grid, float level, const float* lo /*host [3]*/, float step,
+                  const uint8_t* edge_mask, const int32_t* vert_start_end, const int32_t* face_start_end, float* verts, int32_t* faces) {
+  if (!mesh_dims_ok(nx, ny, nz) || grid == nullptr || lo == nullptr || edge_mask == nullptr || vert_start_end == nullptr ||
+      face_start_end == nullptr || verts == nullptr || faces == nullptr)
+    return F2N_ERR_INVALID_ARG;
+  const int64_t n_corners = (int64_t) nx * ny * nz, n_cells = (int64_t) (nx - 1) * (ny - 1) * (nz - 1);
+  hipLaunchKernelGGL(mesh_vert_emit_kernel, dim3(f2n_div_up(n_corners, 256)), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, grid, level,
+                     lo[0], lo[1], lo[2], step, edge_mask, vert_start_end, verts);
+  int e = f2n_launch_status();
+  if (e != F2N_OK) return e;
+  hipLaunchKernelGGL(mesh_face_emit_kernel, dim3(f2n_div_up(n_cells, 256)), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, grid, level,
+                     edge_mask, vert_start_end, face_start_end, faces);
+  return f2n_launch_status();
+}

@@ -12,7 +12,8 @@
     (split.npy)} -- the reference's layout (Dataset.cpp:16-146); NormalizeScene, bounds relaxation and the 8th-image test split
     are applied as there; images are decoded with PIL and kept resident in HBM.
   * modes (ExpRunner::Execute): train (ExpRunner::Train with checkpoints every save_freq and the final TestImages),
-    test (TestImages of the latest checkpoint), render_path (RenderPath over poses_render.npy).  Image files are written with
+    test (TestImages of the latest checkpoint), render_path (RenderPath over poses_render.npy), extract_mesh (with is_continue:
+    <exp>/meshes/<iter>_<res>.ply, the density iso-surface in the data set's world frame; mesh.py).  Image files are written with
     PIL; everything per-ray runs in the C++/HIP host (there is no Python in the training loop: ExpRunner::Train).
   * data-parallel training (the reference is single-GPU): launched as N ranks -- `python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 -m f2_nerf_amd.run ...` -- every rank builds the same scene from the same seed, the
@@ -197,6 +198,9 @@ def main(argv=None):
         elif mode == "render_all":  # ExpRunner::RenderAllImages (ExpRunner.cpp:295-299): every image of the data set, as VisualizeImage writes it
             for idx in range(int(ds.n_images)):
                 save_png(os.path.join(exp_dir, "images", "%d_%d.png" % (runner.iter_step, idx)), runner.visualize_image(ds, idx))
+        elif mode == "extract_mesh":  # no reference counterpart: <exp>/meshes/<iter>_<res>.ply (mesh.py; options mesh.*)
+            from . import mesh
+            mesh.extract(runner, cfg, sc, exp_dir)
         else:
             raise ValueError("unknown mode: %s" % mode)
     finally:

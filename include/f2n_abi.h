@@ -815,6 +815,51 @@ int f2n_nonfinite_flags(void* stream, int n_a, const float* a, int n_b, const fl
 int f2n_nonfinite_flags_ex(void* stream, int n_a, const float* a, int n_b, const float* b, int32_t* flags /*[3]*/,
                            int32_t* mirror /*mapped host [3] or NULL*/);
 
+/* ---------------------------------------------------------------------------------------------------
+ * World-space queries and meshes (additive; the ABI version is unchanged).  csrc/octree.hip.
+ * ------------------------------------------------------------------------------------------------- */
+/* Fills the seam the reference leaves empty: Field::Query(coords) is `CHECK(false) << "Not implemented"` (Field/Field.h:14).
+ * Point location: descend from node 0 (PersSampler.cpp:82), child slot st = 4 (x >= cx) + 2 (y >= cy) + (z >= cz) (the offset order
+ * of ConstructTreeNode, :397-401), stop at a node with no children.  A point is EMPTY when it lies outside the root cube (closed
+ * bounds), falls into a child slot that is -1, or reaches a leaf with trans_idx < 0 -- exactly the nodes
+ * FindRayOctreeIntersectionKernel never lists (PersSampler.cu:54-152).  Non-empty: out_pts_warped = f2n_warp(transes[trans_idx], p),
+ * anchors = (trans_idx, leaf, 0), the layout of f2n_ray_march_fill.  Empty: warped (0, 0, 0), anchors (-1, -1, 0). */
+int f2n_oct_locate_warp(void* stream, int n, const float* pts_world /*[n,3]*/, const void* tree_nodes, const void* transes,
+                        float* out_pts_warped /*[n,3]*/, int32_t* out_anchors /*[n,3]*/);
+/* The same for the points of an implicit grid: point (ix, iy, iz), iz in [first_z, first_z + n_z), is lo[k] + step * (float) i_k
+ * (rounded twice, never an FMA), rows x fastest: output row (iz - first_z) * nx * ny + iy * nx + ix.  lo is HOST data.
+ * No reference counterpart (the reference has no grid query). */
+int f2n_oct_locate_warp_grid(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int first_z, int n_z,
+                             const void* tree_nodes, const void* transes, float* out_pts_warped /*[nx*ny*n_z,3]*/,
+                             int32_t* out_anchors /*[nx*ny*n_z,3]*/);
+/* Compaction of the non-empty located points, count -> f2n_segment_scan -> fill: counts[i] = (anchors[i,0] >= 0), start_end from the
+ * scan, total[0] = their number; point i goes to row start_end[i,0] of out_pts / out_vol (= trans_idx) / out_src (= i, or NULL).
+ * No reference counterpart. */
+int f2n_located_compact(void* stream, int n, const int32_t* anchors /*[n,3]*/, const float* pts_warped /*[n,3]*/, int32_t* counts /*[n]*/,
+                        int32_t* start_end /*[n,2]*/, int32_t* total /*[1]*/, float* out_pts /*[n,3]*/, int32_t* out_vol /*[n]*/,
+                        int32_t* out_src /*[n] or NULL*/);
+/* density[i] = exp(f0[start_end[i,0]] - 3) for the non-empty points (TruncExp of Renderer.cpp:101-104), exactly 0 for the empty ones;
+ * f0 = the field's density pre-activation of the compacted points.  No reference counterpart. */
+int f2n_density_scatter(void* stream, int n, const int32_t* anchors /*[n,3]*/, const int32_t* start_end /*[n,2]*/, const float* f0,
+                        float* density /*[n]*/);
+/* Iso-surface of ANY float32 grid g [nz, ny, nx] (x fastest) by marching tetrahedra on the Kuhn split (six tetrahedra per cell
+ * around its (0,0,0)-(1,1,1) diagonal; no ambiguous case, watertight).  No reference counterpart (the reference ships no mesh export).
+ *   A corner is inside iff g > level.  Every crossing edge gets ONE vertex, owned by its lower corner; the edge is one of the 7 types
+ *   {+x, +y, +z, +xy, +xz, +yz, +xyz} = 0..6.  Vertex order: (owner corner index, type).  Face order: (cell index, tet 0..5 for the
+ *   axis orders xyz, xzy, yxz, yzx, zxy, zyx, triangle).  Tet vertices are numbered 0..3 along (0, a, a|b, 7).  One corner i alone on
+ *   its side, j < k < l the others: triangle (ij, ik, il); corners i < j inside, k < l outside: triangles (ik, il, jl), (ik, jl, jk)
+ *   -- each with its second and third vertex swapped where needed so that its normal points from inside to outside.
+ *   Position p_a + t (p_b - p_a), t = (level - g_a) / (g_b - g_a), a = the lower endpoint, p = lo + step * index as above.
+ * f2n_mesh_count: edge_mask [N] (bit t: the edge of type t crosses), the per-corner vertex counts and per-cell face counts and their
+ *   scans (N = nx*ny*nz corners, C = (nx-1)(ny-1)(nz-1) cells); totals[0] = vertices, totals[1] = faces -- the only values a caller
+ *   needs on the host (to size the outputs).
+ * f2n_mesh_emit: verts [totals[0],3] f32, faces [totals[1],3] int32.  lo is HOST data. */
+int f2n_mesh_count(void* stream, int nx, int ny, int nz, const float* grid, float level, uint8_t* edge_mask /*[N]*/,
+                   int32_t* vert_counts /*[N]*/, int32_t* vert_start_end /*[N,2]*/, int32_t* face_counts /*[C]*/,
+                   int32_t* face_start_end /*[C,2]*/, int32_t* totals /*[2]*/);
+int f2n_mesh_emit(void* stream, int nx, int ny, int nz, const float* grid, float level, const float* lo /*host [3]*/, float step,
+                  const uint8_t* edge_mask, const int32_t* vert_start_end, const int32_t* face_start_end, float* verts, int32_t* faces);
+
 #ifdef __cplusplus
 }
 #endif
