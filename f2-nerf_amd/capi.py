@@ -778,3 +778,53 @@ def mesh_from_grid(grid, level, lo=(0.0, 0.0, 0.0), step=1.0):
         _ck(lib().f2n_mesh_emit(_stream(), _i(nx), _i(ny), _i(nz), _p(grid, "f32"), _f(level), _lo3(lo), _f(step), _p(mask, "u8"),
                                 _p(vse, "i32"), _p(fse, "i32"), _p(verts, "f32"), _p(faces, "i32")), "f2n_mesh_emit")
     return verts, faces
+
+
+def radiance_scatter(n, anchors, start_end, f0, rgb_rows, density, rgb):
+    """density_scatter with a colour: rows of the compacted (f0, rgb) back to every point, zeros for the empty ones."""
+    _ck(lib().f2n_radiance_scatter(_stream(), _i(n), _p(anchors, "i32"), _p(start_end, "i32"), _p(f0, "f32", True),
+                                   _p(rgb_rows, "f32", True), _p(density, "f32"), _p(rgb, "f32")), "f2n_radiance_scatter")
+
+
+def grid_normals(grid, pts, lo=(0.0, 0.0, 0.0), step=1.0):
+    """Unit normals [n,3] at pts [n,3] from the gradient of a float32 grid [nz, ny, nx] (f2n_grid_normals)."""
+    nz, ny, nx = (int(v) for v in grid.shape)
+    n = int(pts.shape[0])
+    out = torch.empty((n, 3), dtype=torch.float32, device=grid.device)
+    _ck(lib().f2n_grid_normals(_stream(), _i(n), _p(pts, "f32", n == 0), _p(grid, "f32"), _i(nx), _i(ny), _i(nz), _lo3(lo), _f(step),
+                               _p(out, "f32", n == 0)), "f2n_grid_normals")
+    return out
+
+
+def mesh_components(faces, n_verts, with_rounds=False):
+    """labels [V] int32: the smallest vertex index of every vertex's connected component (f2n_mesh_components; synchronises)."""
+    nf = int(faces.shape[0])
+    labels = torch.empty(int(n_verts), dtype=torch.int32, device=faces.device)
+    changed = torch.zeros(1, dtype=torch.int32, device=faces.device)
+    rounds = ctypes.c_int(0)
+    _ck(lib().f2n_mesh_components(_stream(), _i(n_verts), _i(nf), _p(faces, "i32", nf == 0), _p(labels, "i32", n_verts == 0),
+                                  _p(changed, "i32"), ctypes.byref(rounds)), "f2n_mesh_components")
+    return (labels, rounds.value) if with_rounds else labels
+
+
+def mesh_filter_components(verts, faces, min_faces):
+    """The mesh without its components of fewer than min_faces faces, order kept: (verts, faces, vert_src).  min_faces <= 1: the input.
+    Reads back the two totals only (they size the outputs)."""
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    dev = verts.device
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    if min_faces <= 1:
+        return verts, faces, torch.arange(nv, dtype=torch.int32, device=dev)
+    labels = mesh_components(faces, nv)
+    comp, vkeep, vse, fkeep, fse, totals = i32(nv), i32(nv), i32(nv, 2), i32(nf), i32(nf, 2), i32(2)
+    _ck(lib().f2n_mesh_filter_count(_stream(), _i(nv), _i(nf), _p(faces, "i32", nf == 0), _p(labels, "i32", nv == 0), _i(min_faces),
+                                    _p(comp, "i32", nv == 0), _p(vkeep, "i32", nv == 0), _p(vse, "i32", nv == 0), _p(fkeep, "i32", nf == 0),
+                                    _p(fse, "i32", nf == 0), _p(totals, "i32")), "f2n_mesh_filter_count")
+    kv, kf = (int(v) for v in totals.cpu())
+    ov = torch.empty((kv, 3), dtype=torch.float32, device=dev)
+    src, of = i32(kv), i32(kf, 3)
+    if kv or kf:
+        _ck(lib().f2n_mesh_filter_emit(_stream(), _i(nv), _i(nf), _p(verts, "f32"), _p(faces, "i32", nf == 0), _p(vkeep, "i32"),
+                                       _p(vse, "i32"), _p(fkeep, "i32", nf == 0), _p(fse, "i32", nf == 0), _p(ov, "f32", kv == 0),
+                                       _p(src, "i32", kv == 0), _p(of, "i32", kf == 0)), "f2n_mesh_filter_emit")
+    return ov, of, src

@@ -73,6 +73,17 @@ struct GridSpec {
 };
 // Iso-surface of any float32 grid [nz, ny, nx] (f2n_mesh_count / f2n_mesh_emit): (verts [V,3] f32, faces [F,3] int32)
 std::tuple<Tensor, Tensor> MeshFromGrid(const Tensor& grid, float level, const float lo[3], float step);
+// Unit normals [n,3] at pts [n,3] from the gradient of any float32 grid [nz, ny, nx] (f2n_grid_normals): -grad / |grad|, 0 where flat
+Tensor GridNormals(const Tensor& grid, const Tensor& pts, const float lo[3], float step);
+// labels [V] int32: the smallest vertex index of every vertex's connected component (f2n_mesh_components); *rounds: labelling rounds
+Tensor MeshComponents(const Tensor& faces, int64_t n_verts, int* rounds = nullptr);
+// The mesh without the components of fewer than min_faces faces, order kept (f2n_mesh_filter_count / _emit): (verts, faces re-indexed,
+// vert_src [V'] int32 = the original index of every kept vertex).  min_faces <= 1: the input itself and the identity.
+std::tuple<Tensor, Tensor, Tensor> MeshFilterComponents(const Tensor& verts, const Tensor& faces, int min_faces);
+
+struct MeshAttrs {  // Renderer::ExtractMeshAttrs; normals / colors are undefined unless asked for
+  Tensor verts, faces, normals, colors;
+};
 
 struct TrainOutputs {
   Tensor losses;  // device [8]: loss, color, var, disp, tv, mse, 0, 0 (f2n_train_loss)
@@ -284,6 +295,14 @@ class Renderer : public Pipe {
   std::tuple<Tensor, Tensor> ExtractMesh(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level);
   static GridSpec MakeGridSpec(const std::vector<float>& lo, const std::vector<float>& hi, int res);
   Tensor DensityOfLocated(const Tensor& warped, const Tensor& anchors);
+  // (density [n], rgb [n,3]) at world points seen from the UNIT directions dirs [n,3] (not normalised here): the density of
+  // QueryDensity, bit for bit, and the shader's colour for the point's field features without appearance embedding -- what
+  // RenderForward computes per sample; zeros where no listed leaf holds the point.  The same side-effect contract as QueryDensity.
+  std::tuple<Tensor, Tensor> QueryRadiance(const Tensor& world, const Tensor& dirs);
+  // ExtractMesh, then: the components of fewer than min_component_faces faces removed, normals of the surviving vertices from
+  // the same density grid, colours = the radiance at each vertex seen along its inward normal ((0, 0, -1) where the normal is 0)
+  MeshAttrs ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
+                             bool normals, bool colors);
   int64_t density_slab_points_ = int64_t(1) << 22;
 
   int LoadStates(const std::vector<Tensor>& states, int idx) override;

@@ -1,4 +1,4 @@
-// World-space density queries and iso-surface extraction (csrc/octree.hip; include/f2n_abi.h, "World-space queries and meshes").
+// World-space density and radiance queries, iso-surface extraction and mesh attributes (csrc/octree.hip; include/f2n_abi.h, "World-space queries and meshes").
 // None of this is on the training path: the queries draw nothing from the keyed streams, touch no occupancy statistics and leave
 // the pre-pass feature cache of Hash3DAnchored (prepass_x_) as they found it.  Callers flush a streaming step first
 // (ExpRunner::FinishPending, as SaveCheckpoint does).
@@ -46,6 +46,49 @@ Tensor Renderer::QueryDensity(const Tensor& world) {
   auto* sampler = static_cast<PersSampler*>(pts_sampler_.get());
   auto located = sampler->LocatePoints(world);
   return DensityOfLocated(std::get<0>(located), std::get<1>(located));
+}
+
+std::tuple<Tensor, Tensor> Renderer::QueryRadiance(const Tensor& world, const Tensor& dirs) {
+  torch::NoGradGuard g;
+  auto* sampler = static_cast<PersSampler*>(pts_sampler_.get());
+  auto* field = static_cast<Hash3DAnchored*>(scene_field_.get());
+  auto* shader = static_cast<SHShader*>(shader_.get());
+  auto located = sampler->LocatePoints(world);
+  const Tensor& warped = std::get<0>(located);
+  const Tensor& anchors = std::get<1>(located);
+  const int64_t n = anchors.size(0);
+  Tensor d = dirs.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  TORCH_CHECK(d.size(0) == n, "one view direction per point");
+  Tensor density = torch::empty({n}, DevF32()), rgb = torch::empty({n, 3}, DevF32());
+  if (n == 0) return {density, rgb};
+  Tensor counts = torch::empty({n}, DevI32()), se = torch::empty({n, 2}, DevI32()), total = torch::empty({1}, DevI32());
+  Tensor cpts = torch::empty({n, 3}, DevF32()), cvol = torch::empty({n}, DevI32()), csrc = torch::empty({n}, DevI32());
+  F2N_CALL(f2n_located_compact(CurStream(), (int) n, I32P(anchors), F32P(warped), I32P(counts), I32P(se), I32P(total), F32P(cpts),
+                               I32P(cvol), I32P(csrc)));
+  const int m = total.item<int>();  // (the pre-pass takes its row count from the host, as in DensityOfLocated)
+  Tensor f0 = torch::zeros({1}, DevF32()), crgb = torch::zeros({1, 3}, DevF32());
+  if (m > 0) {
+    Tensor keep = field->prepass_x_;  // a batch sampled ahead may still be served from this cache
+    Tensor p = cpts.narrow(0, 0, m), v = cvol.narrow(0, 0, m);
+    Tensor cdirs = d.index_select(0, csrc.narrow(0, 0, m)).contiguous();  // the directions travel with their points
+    if (FusedPathOk()) {
+      f0 = field->QueryDensityPreAct(p, v, /*keep_features=*/true);
+      TORCH_CHECK(field->prepass_x_.defined(), "no pre-pass feature cache for this query");
+      crgb = torch::empty({m, 3}, DevF32());
+      Tensor f0_again = torch::empty({m}, DevF32());  // (the fused launch writes its own copy; the density comes from the pre-pass)
+      F2N_CALL(f2n_field_shade_fwd_dyn(CurStream(), m, I32P(total), nullptr, VoidP(field->prepass_x_), VoidP(field->mlp_->params_h_),
+                                       F32P(cdirs), nullptr, nullptr, VoidP(shader->mlp_->params_h_), F32P(f0_again), nullptr, nullptr,
+                                       F32P(crgb)));
+    } else {  // network shapes without fused kernels: op by op, as Render()
+      f0 = field->QueryDensityPreAct(p, v, /*keep_features=*/false);
+      Tensor feat = field->AnchoredQuery(p, v);
+      Tensor none = torch::empty({0}, DevF32());
+      crgb = shader->QueryFromField(feat, cdirs, none, torch::empty({0}, DevI32()), nullptr).to(torch::kFloat32).contiguous();
+    }
+    field->prepass_x_ = keep;
+  }
+  F2N_CALL(f2n_radiance_scatter(CurStream(), (int) n, I32P(anchors), I32P(se), F32P(f0), F32P(crgb), F32P(density), F32P(rgb)));
+  return {density, rgb};
 }
 
 GridSpec Renderer::MakeGridSpec(const std::vector<float>& lo, const std::vector<float>& hi, int res) {
@@ -112,6 +155,75 @@ std::tuple<Tensor, Tensor> Renderer::ExtractMesh(const std::vector<float>& lo, c
   const GridSpec s = MakeGridSpec(lo, hi, res);
   Tensor grid = DensityGrid(lo, hi, res);
   return MeshFromGrid(grid, level, s.lo, s.step);
+}
+
+Tensor GridNormals(const Tensor& grid, const Tensor& pts, const float lo[3], float step) {
+  torch::NoGradGuard g;
+  Tensor gr = grid.to(torch::kCUDA, torch::kFloat32).contiguous();
+  TORCH_CHECK(gr.dim() == 3 && gr.size(0) >= 2 && gr.size(1) >= 2 && gr.size(2) >= 2, "grid must be [nz, ny, nx] with at least 2 points per axis");
+  TORCH_CHECK(gr.numel() <= INT32_MAX && step > 0.f, "grid too large or step not positive");
+  Tensor p = pts.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  const int64_t n = p.size(0);
+  TORCH_CHECK(n <= INT32_MAX, "too many points");
+  Tensor out = torch::empty({n, 3}, DevF32());
+  F2N_CALL(f2n_grid_normals(CurStream(), (int) n, F32P(p), F32P(gr), (int) gr.size(2), (int) gr.size(1), (int) gr.size(0), lo, step,
+                            F32P(out)));
+  return out;
+}
+
+Tensor MeshComponents(const Tensor& faces, int64_t n_verts, int* rounds) {
+  torch::NoGradGuard g;
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  TORCH_CHECK(n_verts >= 0 && n_verts <= INT32_MAX && f.size(0) <= INT32_MAX, "mesh too large");
+  Tensor labels = torch::empty({n_verts}, DevI32()), changed = torch::zeros({1}, DevI32());
+  F2N_CALL(f2n_mesh_components(CurStream(), (int) n_verts, (int) f.size(0), I32P(f), I32P(labels), I32P(changed), rounds));
+  return labels;
+}
+
+std::tuple<Tensor, Tensor, Tensor> MeshFilterComponents(const Tensor& verts, const Tensor& faces, int min_faces) {
+  torch::NoGradGuard g;
+  Tensor v = verts.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  const int64_t nv = v.size(0), nf = f.size(0);
+  TORCH_CHECK(nv <= INT32_MAX && nf <= INT32_MAX, "mesh too large");
+  if (min_faces <= 1) return {v, f, torch::arange(nv, DevI32())};
+  Tensor labels = MeshComponents(f, nv);
+  Tensor comp = torch::empty({nv}, DevI32()), vkeep = torch::empty({nv}, DevI32()), vse = torch::empty({nv, 2}, DevI32());
+  Tensor fkeep = torch::empty({nf}, DevI32()), fse = torch::empty({nf, 2}, DevI32()), totals = torch::empty({2}, DevI32());
+  F2N_CALL(f2n_mesh_filter_count(CurStream(), (int) nv, (int) nf, I32P(f), I32P(labels), min_faces, I32P(comp), I32P(vkeep), I32P(vse),
+                                 I32P(fkeep), I32P(fse), I32P(totals)));
+  Tensor t = totals.cpu();  // the two totals: they size the outputs
+  const int64_t kv = t.data_ptr<int32_t>()[0], kf = t.data_ptr<int32_t>()[1];
+  Tensor ov = torch::empty({kv, 3}, DevF32()), src = torch::empty({kv}, DevI32()), of = torch::empty({kf, 3}, DevI32());
+  if (kv > 0 || kf > 0)
+    F2N_CALL(f2n_mesh_filter_emit(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), I32P(vkeep), I32P(vse), I32P(fkeep), I32P(fse),
+                                  F32P(ov), I32P(src), I32P(of)));
+  return {ov, of, src};
+}
+
+MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level,
+                                     int min_component_faces, bool normals, bool colors) {
+  torch::NoGradGuard g;
+  const GridSpec s = MakeGridSpec(lo, hi, res);
+  Tensor grid = DensityGrid(lo, hi, res);
+  MeshAttrs out;
+  std::tie(out.verts, out.faces) = MeshFromGrid(grid, level, s.lo, s.step);
+  if (min_component_faces > 1) {
+    auto kept = MeshFilterComponents(out.verts, out.faces, min_component_faces);
+    out.verts = std::get<0>(kept);
+    out.faces = std::get<1>(kept);
+  }
+  if (!normals && !colors) return out;
+  Tensor nrm = GridNormals(grid, out.verts, s.lo, s.step);
+  if (normals) out.normals = nrm;
+  if (colors) {
+    // a vertex colour is the radiance AT the vertex seen along the inward normal (by a viewer in front of the surface)
+    Tensor flat = (nrm == 0).all(1, /*keepdim=*/true);
+    Tensor fallback = torch::tensor({0.f, 0.f, -1.f}, DevF32()).view({1, 3});
+    Tensor dirs = torch::where(flat, fallback, -nrm).contiguous();
+    out.colors = std::get<1>(QueryRadiance(out.verts, dirs));  // (the shader's range: [-1e-3, 1 + 1e-3]; mesh.write_ply clips)
+  }
+  return out;
 }
 
 }  // namespace f2n

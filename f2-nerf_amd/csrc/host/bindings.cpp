@@ -112,6 +112,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
         },
         py::arg("grid"), py::arg("level"), py::arg("lo") = std::vector<float>{0.f, 0.f, 0.f}, py::arg("step") = 1.f);
+  // unit normals [n,3] at pts [n,3] from the gradient of any float32 grid [nz, ny, nx] (f2n_grid_normals)
+  m.def("grid_normals",
+        [](const Tensor& grid, const Tensor& pts, const std::vector<float>& lo, float step) {
+          TORCH_CHECK(lo.size() == 3, "lo must have three coordinates");
+          return GridNormals(grid, pts, lo.data(), step);
+        },
+        py::arg("grid"), py::arg("pts"), py::arg("lo") = std::vector<float>{0.f, 0.f, 0.f}, py::arg("step") = 1.f);
+  // labels [V] int32 = the smallest vertex index of every vertex's connected component (f2n_mesh_components);
+  // with_rounds: (labels, number of labelling rounds)
+  m.def("mesh_components",
+        [](const Tensor& faces, int64_t n_verts, bool with_rounds) -> py::object {
+          int rounds = 0;
+          Tensor labels = MeshComponents(faces, n_verts, &rounds);
+          if (with_rounds) return py::make_tuple(labels, rounds);
+          return py::cast(labels);
+        },
+        py::arg("faces"), py::arg("n_verts"), py::arg("with_rounds") = false);
+  // the mesh without its components of fewer than min_faces faces, order kept: [verts, faces, vert_src]
+  m.def("mesh_filter_components",
+        [](const Tensor& verts, const Tensor& faces, int min_faces) {
+          auto t = MeshFilterComponents(verts, faces, min_faces);
+          return std::vector<Tensor>{std::get<0>(t), std::get<1>(t), std::get<2>(t)};
+        },
+        py::arg("verts"), py::arg("faces"), py::arg("min_faces"));
   m.def("dp_set_table_buckets", [](int n) { DataParallel::table_buckets = n; });  // table all-reduce buckets of the next attach (A/B)
   // data-parallel replicas draw stream `rank` of every keyed purpose (KeyedDraws.h; the native attach sets it itself)
   m.def("dp_set_replica", [](int rank) { KeyedUniforms::SetReplica(rank); });
@@ -292,6 +316,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
            },
            py::arg("lo"), py::arg("hi"), py::arg("res"), py::arg("level"))
+      .def("query_radiance",  // world [n,3], unit dirs [n,3] -> [density [n] (= query_density), rgb [n,3]]; zeros for empty points
+           [](ExpRunner& r, const Tensor& world, const Tensor& dirs) {
+             py::gil_scoped_release no_gil;
+             r.FinishPending();
+             auto t = r.renderer_->QueryRadiance(world, dirs);
+             return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
+           },
+           py::arg("world"), py::arg("dirs"))
+      .def("extract_mesh_attrs",  // extract_mesh + floater removal, normals from the density grid, colours along the inward normal
+           [](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
+              bool normals, bool colors) {
+             MeshAttrs a;
+             {
+               py::gil_scoped_release no_gil;
+               r.FinishPending();
+               a = r.renderer_->ExtractMeshAttrs(lo, hi, res, level, min_component_faces, normals, colors);
+             }
+             py::dict d;
+             d["verts"] = a.verts;
+             d["faces"] = a.faces;
+             if (normals) d["normals"] = a.normals;
+             if (colors) d["colors"] = a.colors;
+             return d;
+           },
+           py::arg("lo"), py::arg("hi"), py::arg("res"), py::arg("level"), py::arg("min_component_faces") = 0, py::arg("normals") = true,
+           py::arg("colors") = true)
       .def_property("density_slab_points",  // points per z-slab of density_grid (bounds its workspaces)
                     [](ExpRunner& r) { return r.renderer_->density_slab_points_; },
                     [](ExpRunner& r, int64_t n) { r.renderer_->density_slab_points_ = std::max<int64_t>(1, n); })

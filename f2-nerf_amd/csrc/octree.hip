@@ -629,3 +629,268 @@ int f2n_mesh_emit(void* stream, int nx, int ny, int nz, const float* grid, float
                      edge_mask, vert_start_end, face_start_end, faces);
   return f2n_launch_status();
 }
+
+// =====================================================================================================================
+// Mesh attributes (include/f2n_abi.h, "World-space queries and meshes"): radiance at world points, normals from the density
+// grid, connected components of a triangle mesh and the removal of the small ones.
+//   radiance:   the scatter of the compacted (f0, rgb) rows back to every queried point, zeros for the empty ones
+//   normals:    one thread per point: central differences at the eight corners of the point's cell, blended trilinearly
+//   components: a parent array over the vertices; every face hooks the larger roots of its vertices under the smallest
+//               (atomicMin), a pointer-jumping pass flattens the trees, rounds repeat until a round hooks nothing.
+//               parent[v] <= v at all times and a parent is always a vertex of the same component, so the fixpoint --
+//               every vertex points at the smallest index of its component -- does not depend on the schedule.
+//   filter:     face counts per label -> keep flags -> f2n_segment_scan -> emit, order preserving
+// =====================================================================================================================
+namespace {
+
+__global__ void __launch_bounds__(256) radiance_scatter_kernel(int n, const int32_t* __restrict__ anchors, const int32_t* __restrict__ start_end,
+                                                              const float* __restrict__ f0, const float* __restrict__ rgb_rows,
+                                                              float* __restrict__ density, float* __restrict__ rgb) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool hit = anchors[i * 3] >= 0;
+  const int64_t k = hit ? start_end[i * 2] : 0;
+  density[i] = hit ? expf(f0[k] - F2N_DENSITY_SHIFT) : 0.f;  // (the expression of density_scatter_kernel: the same bits)
+#pragma unroll
+  for (int c = 0; c < 3; c++) rgb[i * 3 + c] = hit ? rgb_rows[k * 3 + c] : 0.f;
+}
+
+// Component `axis` of the corner gradient G at corner (x, y, z): central difference over 2 step in the interior, the one-sided
+// difference over step on the two border planes of that axis.
+__device__ __forceinline__ float corner_gradient(const float* __restrict__ g, int x, int y, int z, int nx, int ny, int nz, int axis,
+                                                 float step) {
+  const int i = axis == 0 ? x : axis == 1 ? y : z;
+  const int n = axis == 0 ? nx : axis == 1 ? ny : nz;
+  const int64_t stride = axis == 0 ? 1 : axis == 1 ? (int64_t) nx : (int64_t) nx * ny;
+  const int64_t c = corner_index(x, y, z, nx, ny);
+  if (i == 0) return F2N_DIV_RN(F2N_SUB_RN(g[c + stride], g[c]), step);
+  if (i == n - 1) return F2N_DIV_RN(F2N_SUB_RN(g[c], g[c - stride]), step);
+  return F2N_DIV_RN(F2N_SUB_RN(g[c + stride], g[c - stride]), F2N_MUL_RN(2.f, step));
+}
+
+__device__ __forceinline__ float lerp_rn(float a, float b, float f) {  // a (1 - f) + b f, four roundings
+  return F2N_ADD_RN(F2N_MUL_RN(a, F2N_SUB_RN(1.f, f)), F2N_MUL_RN(b, f));
+}
+
+__global__ void __launch_bounds__(256) grid_normals_kernel(int n, const float* __restrict__ pts, const float* __restrict__ g, int nx, int ny,
+                                                          int nz, float lo0, float lo1, float lo2, float step, float* __restrict__ out) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float lo[3] = {lo0, lo1, lo2};
+  const int dim[3] = {nx, ny, nz};
+  int c[3];
+  float f[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    float u = F2N_DIV_RN(F2N_SUB_RN(pts[i * 3 + k], lo[k]), step);
+    u = fminf(fmaxf(u, 0.f), (float) (dim[k] - 1));  // (NaN -> 0: the cell stays inside the grid whatever the point)
+    const int cell = (int) floorf(u);
+    c[k] = cell < dim[k] - 2 ? cell : dim[k] - 2;
+    f[k] = F2N_SUB_RN(u, (float) c[k]);
+  }
+  float grad[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    float G[8];
+#pragma unroll
+    for (int o = 0; o < 8; o++)
+      G[o] = corner_gradient(g, c[0] + (o & 1), c[1] + ((o >> 1) & 1), c[2] + ((o >> 2) & 1), nx, ny, nz, k, step);
+    // along x, then y, then z
+    const float y0 = lerp_rn(lerp_rn(G[0], G[1], f[0]), lerp_rn(G[2], G[3], f[0]), f[1]);
+    const float y1 = lerp_rn(lerp_rn(G[4], G[5], f[0]), lerp_rn(G[6], G[7], f[0]), f[1]);
+    grad[k] = lerp_rn(y0, y1, f[2]);
+  }
+  const float len = sqrtf(F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(grad[0], grad[0]), F2N_MUL_RN(grad[1], grad[1])), F2N_MUL_RN(grad[2], grad[2])));
+  const bool ok = len > 0.f && len < __builtin_huge_valf();  // (false for NaN as well)
+#pragma unroll
+  for (int k = 0; k < 3; k++) out[i * 3 + k] = ok ? -F2N_DIV_RN(grad[k], len) : 0.f;
+}
+
+// ---- connected components ----------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) comp_init_kernel(int n_verts, int32_t* parent) {
+  const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n_verts) parent[v] = (int32_t) v;
+}
+
+// Root of v.  Other threads lower parents while this one walks: every value read is an ancestor-or-self of a smaller or equal
+// index in the same component, and the walk strictly descends, so it ends at a vertex that was a root when it was read.
+__device__ __forceinline__ int comp_root(const int32_t* parent, int v) {
+  for (;;) {
+    const int p = __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (p == v) return v;
+    v = p;
+  }
+}
+
+__device__ __forceinline__ bool face_in_range(const int32_t* __restrict__ faces, int64_t f, int n_verts, int* a, int* b, int* c) {
+  *a = faces[f * 3 + 0];
+  *b = faces[f * 3 + 1];
+  *c = faces[f * 3 + 2];
+  return *a >= 0 && *a < n_verts && *b >= 0 && *b < n_verts && *c >= 0 && *c < n_verts;
+}
+
+__global__ void __launch_bounds__(256) comp_hook_kernel(int n_faces, int n_verts, const int32_t* __restrict__ faces, int32_t* parent,
+                                                       int32_t* changed) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  int a, b, c;
+  if (!face_in_range(faces, f, n_verts, &a, &b, &c)) return;
+  const int ra = comp_root(parent, a), rb = comp_root(parent, b), rc = comp_root(parent, c);
+  const int mab = ra < rb ? ra : rb, m = mab < rc ? mab : rc;
+  if (ra == m && rb == m && rc == m) return;
+  // (a root that another face has hooked in the meantime keeps the smaller of the two parents; the link this face wanted is
+  // found missing by the next round, which is why rounds repeat until none hooks)
+  if (ra != m) atomicMin(parent + ra, m);
+  if (rb != m) atomicMin(parent + rb, m);
+  if (rc != m) atomicMin(parent + rc, m);
+  *changed = 1;  // (benign race: every writer stores 1)
+}
+
+__global__ void __launch_bounds__(256) comp_jump_kernel(int n_verts, int32_t* parent) {
+  const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_verts) return;
+  const int r = comp_root(parent, (int) v);
+  if (r != (int) v) __hip_atomic_store(parent + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- removal of small components -----------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) comp_size_kernel(int n_faces, int n_verts, const int32_t* __restrict__ faces,
+                                                       const int32_t* __restrict__ labels, int32_t* comp_faces) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  int a, b, c, l = -1;
+  if (f < n_faces && face_in_range(faces, f, n_verts, &a, &b, &c)) l = labels[a];
+  bool todo = l >= 0 && l < n_verts;
+  // One atomic per distinct label of a wave, not per face: neighbouring faces share their component, and a scene's main surface
+  // would otherwise send millions of adds to one address (measured: 387 ms of a 256^3 extraction).
+  const int lane = threadIdx.x & 63;
+  for (;;) {
+    const unsigned long long rem = __ballot(todo);
+    if (rem == 0) break;
+    const int leader = __ffsll((long long) rem) - 1;
+    const int l0 = __shfl(l, leader);
+    const bool same = todo && l == l0;
+    const unsigned long long m = __ballot(same);
+    if (lane == leader) atomicAdd(comp_faces + l0, (int32_t) __popcll(m));
+    todo = todo && !same;
+  }
+}
+
+__global__ void __launch_bounds__(256) comp_keep_kernel(int n_faces, int n_verts, const int32_t* __restrict__ faces,
+                                                       const int32_t* __restrict__ labels, const int32_t* __restrict__ comp_faces,
+                                                       int min_faces, int32_t* vert_keep, int32_t* __restrict__ face_keep) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  int a, b, c;
+  bool keep = false;
+  if (face_in_range(faces, f, n_verts, &a, &b, &c)) {
+    const int l = labels[a];
+    keep = l >= 0 && l < n_verts && comp_faces[l] >= min_faces;
+  }
+  face_keep[f] = keep ? 1 : 0;
+  if (keep) vert_keep[a] = vert_keep[b] = vert_keep[c] = 1;  // (benign race: every writer stores 1)
+}
+
+__global__ void __launch_bounds__(256) filter_vert_emit_kernel(int n_verts, const float* __restrict__ verts, const int32_t* __restrict__ vert_keep,
+                                                              const int32_t* __restrict__ vert_se, float* __restrict__ out_verts,
+                                                              int32_t* __restrict__ vert_src) {
+  const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_verts || vert_keep[v] == 0) return;
+  const int64_t k = vert_se[v * 2];
+#pragma unroll
+  for (int c = 0; c < 3; c++) out_verts[k * 3 + c] = verts[v * 3 + c];
+  vert_src[k] = (int32_t) v;
+}
+
+__global__ void __launch_bounds__(256) filter_face_emit_kernel(int n_faces, const int32_t* __restrict__ faces, const int32_t* __restrict__ face_keep,
+                                                              const int32_t* __restrict__ face_se, const int32_t* __restrict__ vert_se,
+                                                              int32_t* __restrict__ out_faces) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces || face_keep[f] == 0) return;  // (a kept face has its three indices in range: comp_keep_kernel)
+  const int64_t k = face_se[f * 2];
+#pragma unroll
+  for (int c = 0; c < 3; c++) out_faces[k * 3 + c] = vert_se[(int64_t) faces[f * 3 + c] * 2];
+}
+
+}  // namespace
+
+int f2n_radiance_scatter(void* stream, int n, const int32_t* anchors, const int32_t* start_end, const float* f0, const float* rgb_rows,
+                         float* density, float* rgb) {
+  if (n < 0 || (n > 0 && (anchors == nullptr || start_end == nullptr || density == nullptr || rgb == nullptr))) return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  hipLaunchKernelGGL(radiance_scatter_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, anchors, start_end, f0,
+                     rgb_rows, density, rgb);
+  return f2n_launch_status();
+}
+
+int f2n_grid_normals(void* stream, int n, const float* pts, const float* grid, int nx, int ny, int nz, const float* lo /*host [3]*/,
+                     float step, float* out) {
+  if (n < 0 || !mesh_dims_ok(nx, ny, nz) || lo == nullptr || !(step > 0.f) || (n > 0 && (pts == nullptr || grid == nullptr || out == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  hipLaunchKernelGGL(grid_normals_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, pts, grid, nx, ny, nz, lo[0],
+                     lo[1], lo[2], step, out);
+  return f2n_launch_status();
+}
+
+#define F2N_COMP_MAX_ROUNDS 4096  // (a mesh takes a handful; a round that hooks lowers a parent, so the loop ends in any case)
+int f2n_mesh_components(void* stream, int n_verts, int n_faces, const int32_t* faces, int32_t* labels, int32_t* changed, int* rounds) {
+  if (n_verts < 0 || n_faces < 0 || (n_verts > 0 && labels == nullptr) || (n_faces > 0 && (faces == nullptr || changed == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (rounds != nullptr) *rounds = 0;
+  if (n_verts == 0) return F2N_OK;
+  hipStream_t st = (hipStream_t) stream;
+  hipLaunchKernelGGL(comp_init_kernel, dim3(f2n_div_up(n_verts, 256)), dim3(256), 0, st, n_verts, labels);
+  int e = f2n_launch_status();
+  if (e != F2N_OK || n_faces == 0) return e;
+  for (int round = 1; round <= F2N_COMP_MAX_ROUNDS; round++) {
+    if (hipMemsetAsync(changed, 0, sizeof(int32_t), st) != hipSuccess) return f2n_launch_status();
+    hipLaunchKernelGGL(comp_hook_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, st, n_faces, n_verts, faces, labels, changed);
+    hipLaunchKernelGGL(comp_jump_kernel, dim3(f2n_div_up(n_verts, 256)), dim3(256), 0, st, n_verts, labels);
+    if ((e = f2n_launch_status()) != F2N_OK) return e;
+    int32_t flag = 0;
+    if (hipMemcpyAsync(&flag, changed, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return f2n_launch_status();
+    if (rounds != nullptr) *rounds = round;
+    if (flag == 0) return F2N_OK;  // nothing hooked: the jump behind the previous round has flattened every tree
+  }
+  return F2N_ERR_UNSUPPORTED;
+}
+
+int f2n_mesh_filter_count(void* stream, int n_verts, int n_faces, const int32_t* faces, const int32_t* labels, int min_faces,
+                          int32_t* comp_faces, int32_t* vert_keep, int32_t* vert_start_end, int32_t* face_keep, int32_t* face_start_end,
+                          int32_t* totals) {
+  if (n_verts < 0 || n_faces < 0 || totals == nullptr ||
+      (n_verts > 0 && (labels == nullptr || comp_faces == nullptr || vert_keep == nullptr || vert_start_end == nullptr)) ||
+      (n_faces > 0 && (n_verts == 0 || faces == nullptr || face_keep == nullptr || face_start_end == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t) stream;
+  if (n_verts > 0 && (hipMemsetAsync(comp_faces, 0, sizeof(int32_t) * (size_t) n_verts, st) != hipSuccess ||
+                      hipMemsetAsync(vert_keep, 0, sizeof(int32_t) * (size_t) n_verts, st) != hipSuccess))
+    return f2n_launch_status();
+  int e;
+  if (n_faces > 0) {
+    const dim3 grid(f2n_div_up(n_faces, 256)), block(256);
+    hipLaunchKernelGGL(comp_size_kernel, grid, block, 0, st, n_faces, n_verts, faces, labels, comp_faces);
+    hipLaunchKernelGGL(comp_keep_kernel, grid, block, 0, st, n_faces, n_verts, faces, labels, comp_faces, min_faces, vert_keep, face_keep);
+    if ((e = f2n_launch_status()) != F2N_OK) return e;
+  }
+  if ((e = f2n_segment_scan(stream, n_verts, vert_keep, vert_start_end, totals)) != F2N_OK) return e;
+  return f2n_segment_scan(stream, n_faces, face_keep, face_start_end, totals + 1);
+}
+
+int f2n_mesh_filter_emit(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, const int32_t* vert_keep,
+                         const int32_t* vert_start_end, const int32_t* face_keep, const int32_t* face_start_end, float* out_verts,
+                         int32_t* vert_src, int32_t* out_faces) {
+  if (n_verts < 0 || n_faces < 0 ||
+      (n_verts > 0 && (verts == nullptr || vert_keep == nullptr || vert_start_end == nullptr || out_verts == nullptr || vert_src == nullptr)) ||
+      (n_faces > 0 && (n_verts == 0 || faces == nullptr || face_keep == nullptr || face_start_end == nullptr || out_faces == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t) stream;
+  if (n_verts > 0)
+    hipLaunchKernelGGL(filter_vert_emit_kernel, dim3(f2n_div_up(n_verts, 256)), dim3(256), 0, st, n_verts, verts, vert_keep, vert_start_end,
+                       out_verts, vert_src);
+  if (n_faces > 0)
+    hipLaunchKernelGGL(filter_face_emit_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, st, n_faces, faces, face_keep, face_start_end,
+                       vert_start_end, out_faces);
+  return f2n_launch_status();
+}

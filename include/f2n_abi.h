@@ -859,6 +859,47 @@ int f2n_mesh_count(void* stream, int nx, int ny, int nz, const float* grid, floa
                    int32_t* face_start_end /*[C,2]*/, int32_t* totals /*[2]*/);
 int f2n_mesh_emit(void* stream, int nx, int ny, int nz, const float* grid, float level, const float* lo /*host [3]*/, float step,
                   const uint8_t* edge_mask, const int32_t* vert_start_end, const int32_t* face_start_end, float* verts, int32_t* faces);
+/* f2n_density_scatter with a colour: density[i] = exp(f0[k] - 3) (the same expression, the same bits) and rgb[i] = rgb_rows[k],
+ * k = start_end[i,0], for the non-empty points; density 0 and rgb (0, 0, 0) exactly for the empty ones (anchors[i,0] < 0).
+ * f0 [m] / rgb_rows [m,3] = the field's density pre-activation and the shader's output (no appearance embedding: what the inference
+ * path computes per sample) for the m compacted points of f2n_located_compact; both may be NULL when every point is empty.
+ * No reference counterpart. */
+int f2n_radiance_scatter(void* stream, int n, const int32_t* anchors /*[n,3]*/, const int32_t* start_end /*[n,2]*/, const float* f0,
+                         const float* rgb_rows, float* density /*[n]*/, float* rgb /*[n,3]*/);
+/* Unit normals at n points from ANY float32 grid g [nz, ny, nx] (x fastest; nx, ny, nz >= 2), step > 0, lo HOST data.  No reference
+ * counterpart.
+ *   Corner gradient G[c], component k: (g[c + e_k] - g[c - e_k]) / (2 step) in the interior; on the two border planes of axis k the
+ *   one-sided difference over step ((g[1] - g[0]) / step at index 0, (g[n-1] - g[n-2]) / step at index n_k - 1).
+ *   Point p: u_k = (p_k - lo_k) / step clamped to [0, n_k - 1] (NaN -> 0), cell c_k = min(floor(u_k), n_k - 2), f_k = u_k - c_k;
+ *   g(p) = the trilinear blend of the eight G of that cell, a (1 - f) + b f along x, then y, then z (continuous across cells: a
+ *   vertex on a cell face has no ambiguous case).  G is never materialised: 24 corner reads of g per point and component.
+ *   out = -g(p) / |g(p)| (density grows inwards, f2n_mesh_emit winds outwards); (0, 0, 0) where |g(p)| is 0 or not finite. */
+int f2n_grid_normals(void* stream, int n, const float* pts /*[n,3]*/, const float* grid, int nx, int ny, int nz,
+                     const float* lo /*host [3]*/, float step, float* out /*[n,3]*/);
+/* Connected components of a triangle mesh: labels[v] = the SMALLEST vertex index of v's component, two vertices being connected when
+ * a face uses both; a vertex no face uses is its own component.  The labels are a unique fixpoint: nothing depends on scheduling.
+ * A parent array (labels itself) starts as the identity; a round lets every face hook the larger roots of its three vertices under
+ * the smallest (atomicMin) and then points every vertex at its root; rounds repeat until one hooks nothing.  `changed` is a DEVICE
+ * word of scratch that a round sets; this call READS IT BACK after every round, so it synchronises the stream and returns with the
+ * labels complete.  *rounds (HOST, or NULL) receives the number of rounds, the confirming one included (0 without faces).
+ * A face with an index outside [0, n_verts) connects nothing.  F2N_ERR_UNSUPPORTED after 4096 rounds (no mesh gets near).
+ * No reference counterpart. */
+int f2n_mesh_components(void* stream, int n_verts, int n_faces, const int32_t* faces /*[F,3]*/, int32_t* labels /*[V]*/,
+                        int32_t* changed /*[1]*/, int* rounds /*host [1] or NULL*/);
+/* Removal of the components with fewer than min_faces faces, count -> f2n_segment_scan -> emit as f2n_mesh_count / f2n_mesh_emit.
+ * f2n_mesh_filter_count: comp_faces[l] = number of faces whose vertices carry label l (integer atomics: order-free); face_keep[f] =
+ *   (comp_faces[label of f] >= min_faces); vert_keep[v] = (a kept face uses v) -- so a vertex no face uses is never kept, whatever
+ *   min_faces; the scans of both; totals[0] = kept vertices, totals[1] = kept faces: the only values a caller needs on the host.
+ *   A face with an index outside [0, n_verts) is never kept.
+ * f2n_mesh_filter_emit: kept vertices and faces IN THEIR ORIGINAL RELATIVE ORDER: out_verts [totals[0],3], vert_src [totals[0]] =
+ *   the original index of every kept vertex, out_faces [totals[1],3] re-indexed (vert_start_end[v,0] of each corner).
+ * No reference counterpart. */
+int f2n_mesh_filter_count(void* stream, int n_verts, int n_faces, const int32_t* faces /*[F,3]*/, const int32_t* labels /*[V]*/,
+                          int min_faces, int32_t* comp_faces /*[V]*/, int32_t* vert_keep /*[V]*/, int32_t* vert_start_end /*[V,2]*/,
+                          int32_t* face_keep /*[F]*/, int32_t* face_start_end /*[F,2]*/, int32_t* totals /*[2]*/);
+int f2n_mesh_filter_emit(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/,
+                         const int32_t* vert_keep, const int32_t* vert_start_end, const int32_t* face_keep, const int32_t* face_start_end,
+                         float* out_verts, int32_t* vert_src, int32_t* out_faces);
 
 #ifdef __cplusplus
 }
