@@ -759,6 +759,33 @@ def density_scatter(n, anchors, start_end, f0, density):
         "f2n_density_scatter")
 
 
+def field_density_grad(n, n_volumes, table_h, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped, volume_idx, vol_stride,
+                       mlp_params_h, x_h, out_dx, out_df0_dw):
+    """df0/dx [n,32] (out_dx, optional) and df0/dw [n,3] of the shipped field shape from the pre-pass's h16 features x_h
+    (f2n_field_density_grad: all fp32, the same bits on every call)."""
+    _ck(lib().f2n_field_density_grad(_stream(), _i(n), _i(n_volumes), _p(table_h, "h16"), _p(prim_pool, "i32"), _p(local_idx, "i32"),
+                                     _p(local_size, "i32"), _p(bias_pool, "f32"), _p(level_scale, "f32"), _p(pts_warped, "f32", n == 0),
+                                     _p(volume_idx, "i32", n == 0), _i(vol_stride), _p(mlp_params_h, "h16"), _p(x_h, "h16", n == 0),
+                                     _p(out_dx, "f32", True), _p(out_df0_dw, "f32", n == 0)), "f2n_field_density_grad")
+
+
+def hash_pos_grad(n, n_volumes, table_h, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped, volume_idx, vol_stride, dx,
+                  out_df0_dw):
+    """df0/dw [n,3] from any df0/dx [n,32] f32 (f2n_hash_pos_grad)."""
+    _ck(lib().f2n_hash_pos_grad(_stream(), _i(n), _i(n_volumes), _p(table_h, "h16"), _p(prim_pool, "i32"), _p(local_idx, "i32"),
+                                _p(local_size, "i32"), _p(bias_pool, "f32"), _p(level_scale, "f32"), _p(pts_warped, "f32", n == 0),
+                                _p(volume_idx, "i32", n == 0), _i(vol_stride), _p(dx, "f32", n == 0), _p(out_df0_dw, "f32", n == 0)),
+        "f2n_hash_pos_grad")
+
+
+def density_grad_scatter(n, pts_world, anchors, start_end, transes, f0, df0_dw, out_density, out_grad, out_normal=None):
+    """density_scatter with the gradient sigma J^T df0/dw (and optionally the unit normal -grad / |grad|); zeros for the empty points."""
+    _ck(lib().f2n_density_grad_scatter(_stream(), _i(n), _p(pts_world, "f32", n == 0), _p(anchors, "i32", n == 0),
+                                       _p(start_end, "i32", n == 0), _p(transes, "u8"), _p(f0, "f32", True), _p(df0_dw, "f32", True),
+                                       _p(out_density, "f32", n == 0), _p(out_grad, "f32", n == 0), _p(out_normal, "f32", True)),
+        "f2n_density_grad_scatter")
+
+
 def mesh_from_grid(grid, level, lo=(0.0, 0.0, 0.0), step=1.0):
     """Marching-tetrahedra iso-surface of a float32 grid [nz, ny, nx] (f2n_mesh_count -> f2n_mesh_emit): (verts [V,3], faces [F,3]).
     Reads back the two totals only (they size the outputs)."""

@@ -117,7 +117,9 @@ int f2n_defer_reduction(int n, int n_blocks, const float* partials, float* out);
 #define F2N_WS_MLPG_DW 10   // ... per-block partial weight gradients
 #define F2N_WS_GATHER_BINS 11  // field.hip: request / result queues and slot lists of the slice-binned gather (big tables)
 #define F2N_WS_BIN_OVF 12      // field.hip: the scatter's overflow lists (records that found their queue segment full)
-#define F2N_WS_SLOTS 13
+#define F2N_WS_DGRAD_DX 13     // field.hip: df0/dx of f2n_field_density_grad as planes [8][n][4] f32
+#define F2N_WS_DGRAD_PART 14   // field.hip: the level pairs' partial df0/dw [8][3][n] f32
+#define F2N_WS_SLOTS 15
 // mlp_generic.hip: the tcnn FullyFusedMLP shapes the two specialised kernels do not cover
 bool f2n_mlpg_shape_ok(int d_in, int d_hidden, int n_hidden);
 int f2n_mlpg_fwd(void* stream, int n, int d_in, int d_hidden, int n_hidden, const void* params_h, const float* x, void* out_h);

@@ -1393,6 +1393,160 @@ __global__ void to_h16_kernel(int n, const float* __restrict__ in, half_t* __res
   if (i < n) out[i] = (half_t) in[i];
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Density gradient with respect to position (world-space queries: f2n_field_density_grad / f2n_hash_pos_grad).
+//   df0/dx = W1^T (m . W2[0,:]), m_j = ((W1 x)_j > 0)                          mlp_input_grad_kernel
+//   df0/dw = sum_l (scale_l / 2) sum_c df0/dx_{l,c} dblend_{l,c}/d(a, b, c)     hash_pos_grad_kernel + pos_grad_sum_kernel
+// Every input is an exact h16 value (weights, table entries, the pre-pass's features x); all arithmetic is fp32 in a fixed order,
+// no h16 rounding and no loss scale.  No atomics: the level pairs write their own partial sums, added in pair order afterwards.
+// ---------------------------------------------------------------------------------------------------
+// One thread per point.  The 64 x 32 weights sit in LDS as fp32 and are read as wave-wide broadcasts; a product of two h16
+// values is exact in fp32, so dx[k] is the plain fp32 sum over the hidden units j, in order, of W1[j][k] * W2[0][j] where the
+// unit is active.  dx leaves row-major [n][32] (dx_rows, optional) and as planes [8][n][4] (dx_planes, optional): plane p holds
+// the four values of level pair p, the 16 bytes hash_pos_grad_kernel's lane reads.
+__global__ __launch_bounds__(256) void mlp_input_grad_kernel(int n, const half_t* __restrict__ params, const half_t* __restrict__ x_h,
+                                                             float* __restrict__ dx_rows, float* __restrict__ dx_planes) {
+  __shared__ float s_w1[F2N_D_HID * F2N_D_IN];
+  __shared__ float s_g[F2N_D_HID];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < F2N_D_HID * F2N_D_IN; i += 256) s_w1[i] = (float) params[i];
+  if (tid < F2N_D_HID) s_g[tid] = (float) params[F2N_D_HID * F2N_D_IN + tid];  // row 0 of the output layer
+  __syncthreads();
+  for (int64_t s = (int64_t) blockIdx.x * 256 + tid; s < n; s += (int64_t) gridDim.x * 256) {
+    float x[F2N_D_IN], dx[F2N_D_IN];
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+      const half8_t xv = *(const half8_t*) (x_h + s * F2N_D_IN + 8 * v);
+#pragma unroll
+      for (int i = 0; i < 8; i++) x[8 * v + i] = (float) xv[i];
+    }
+#pragma unroll
+    for (int k = 0; k < F2N_D_IN; k++) dx[k] = 0.f;
+#pragma unroll 2
+    for (int j = 0; j < F2N_D_HID; j++) {
+      const float* w = s_w1 + F2N_D_IN * j;
+      float pre = w[0] * x[0];
+#pragma unroll
+      for (int k = 1; k < F2N_D_IN; k++) pre = pre + w[k] * x[k];
+      const float gj = pre > 0.f ? s_g[j] : 0.f;  // the ReLU mask from the fp32 pre-activation
+#pragma unroll
+      for (int k = 0; k < F2N_D_IN; k++) dx[k] = dx[k] + w[k] * gj;
+    }
+    if (dx_rows != nullptr) {
+#pragma unroll
+      for (int p = 0; p < 8; p++)
+        *(float4_t*) (dx_rows + s * F2N_D_IN + 4 * p) = float4_t{dx[4 * p], dx[4 * p + 1], dx[4 * p + 2], dx[4 * p + 3]};
+    }
+    if (dx_planes != nullptr) {
+#pragma unroll
+      for (int p = 0; p < 8; p++)
+        *(float4_t*) (dx_planes + ((size_t) p * n + s) * 4) = float4_t{dx[4 * p], dx[4 * p + 1], dx[4 * p + 2], dx[4 * p + 3]};
+    }
+  }
+}
+
+// The fractions (a, b, c) of f2n_hash_cell: the same expressions, the same bits.
+__device__ __forceinline__ void f2n_hash_frac(const float* p01, float mul, const float* bias3, float* f) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float q = p01[k] * mul + bias3[k];
+    f[k] = q - floorf(q);
+  }
+}
+
+// d(blend)/d(a, b, c) of one channel: the derivative of the eight weights of f2n_hash_cell (corner bit 2 = x, 1 = y, 0 = z) in
+// the cell floorf chose, as differences of the corner pairs along the axis weighted by the other two axes' weights.
+__device__ __forceinline__ void f2n_blend_grad(const float* v, float a, float b, float c, float* d) {
+  const float a0 = 1.f - a, b0 = 1.f - b, c0 = 1.f - c;
+  d[0] = (((b0 * c0) * (v[4] - v[0]) + (b0 * c) * (v[5] - v[1])) + (b * c0) * (v[6] - v[2])) + (b * c) * (v[7] - v[3]);
+  d[1] = (((a0 * c0) * (v[2] - v[0]) + (a0 * c) * (v[3] - v[1])) + (a * c0) * (v[6] - v[4])) + (a * c) * (v[7] - v[5]);
+  d[2] = (((a0 * b0) * (v[1] - v[0]) + (a0 * b) * (v[3] - v[2])) + (a * b0) * (v[5] - v[4])) + (a * b) * (v[7] - v[6]);
+}
+
+// The second gather, partitioned as hash_gather_planes_kernel: the blocks of XCD x (blockIdx % 8) serve level pair x, so an L2 sees
+// one 3 MiB slice of the table; STAGED keeps the pair's hash constants in LDS.  Thread = point of a 256-point tile.  The pair's
+// contribution to df0/dw goes to partials [8][3][n] (coalesced 4-byte stores); pos_grad_sum_kernel adds the eight in pair order.
+// dx value i = 0..3 of point s and pair p is dx[s * dx_ss + p * dx_ps + i] (rows: 32, 4; planes: 4, 4 n).
+template <bool STAGED>
+__global__ __launch_bounds__(256) void hash_pos_grad_kernel(int n, F2nHashArgs h, const int32_t* __restrict__ local_idx,
+                                                            const int32_t* __restrict__ local_size, const float* __restrict__ level_scale,
+                                                            const float* __restrict__ pts_warped, const int32_t* __restrict__ volume_idx,
+                                                            int vol_stride, const float* __restrict__ dx, size_t dx_ss, size_t dx_ps,
+                                                            float* __restrict__ partials) {
+  __shared__ F2nLevelTab lt;
+  extern __shared__ uint32_t pb_lds[];  // STAGED: [2 levels][V][prim xyz, bias xyz]
+  const int tid = threadIdx.x;
+  const int part = blockIdx.x % F2N_N_PARTS, q = blockIdx.x / F2N_N_PARTS, nq = gridDim.x / F2N_N_PARTS;
+  const int lv[2] = {2 * part, 2 * part + 1};
+  f2n_level_tab_fill(lt, level_scale, local_idx, local_size, tid);
+  if (STAGED) {
+    for (int i = tid; i < 2 * 3 * h.n_volumes; i += 256) {
+      const int j = i >= 3 * h.n_volumes, i1 = i - j * 3 * h.n_volumes;
+      const int r = i1 / 3, k = i1 - 3 * r;
+      const size_t src = 3 * (size_t) (2 * part + j) * h.n_volumes + i1;
+      pb_lds[6 * (j * h.n_volumes + r) + k] = (uint32_t) h.prim_pool[src];
+      pb_lds[6 * (j * h.n_volumes + r) + 3 + k] = __float_as_uint(h.bias_pool[src]);
+    }
+  }
+  __syncthreads();
+  const int n_tiles = (n + 255) / 256;
+  for (int tile = q; tile < n_tiles; tile += nq) {
+    const int s = tile * 256 + tid;
+    if (s >= n) continue;
+    float p01[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) p01[k] = (pts_warped[3 * (size_t) s + k] + 1.f) * .5f;
+    const int vol = volume_idx[(size_t) s * vol_stride];
+    const float4_t d = *(const float4_t*) (dx + (size_t) s * dx_ss + (size_t) part * dx_ps);
+    float t[2][3];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      const int l = lv[j];
+      F2nCell cell;
+      float fr[3];
+      if (STAGED) {
+        const uint32_t* row = pb_lds + 6 * (j * h.n_volumes + vol);
+        const int32_t prim3[3] = {(int32_t) row[0], (int32_t) row[1], (int32_t) row[2]};
+        const float bias3[3] = {__uint_as_float(row[3]), __uint_as_float(row[4]), __uint_as_float(row[5])};
+        f2n_hash_cell(p01, lt.scale[l], prim3, bias3, lt.size[l], cell);
+        f2n_hash_frac(p01, lt.scale[l], bias3, fr);
+      } else {
+        const int tf = l * h.n_volumes + vol;
+        f2n_hash_cell(p01, lt.scale[l], h.prim_pool + 3 * tf, h.bias_pool + 3 * tf, lt.size[l], cell);
+        f2n_hash_frac(p01, lt.scale[l], h.bias_pool + 3 * tf, fr);
+      }
+      const half2_t* base = (const half2_t*) (h.table + lt.base[l]);
+      float v0[8], v1[8];
+#pragma unroll
+      for (int c = 0; c < 8; c++) {
+        const half2_t e = base[cell.pos[c]];
+        v0[c] = (float) e[0];
+        v1[c] = (float) e[1];
+      }
+      float d0[3], d1[3];
+      f2n_blend_grad(v0, fr[0], fr[1], fr[2], d0);
+      f2n_blend_grad(v1, fr[0], fr[1], fr[2], d1);
+      const float half_scale = lt.scale[l] * .5f;  // dq/dw: q = ((w + 1) / 2) scale + bias
+#pragma unroll
+      for (int k = 0; k < 3; k++) t[j][k] = half_scale * (d[2 * j] * d0[k] + d[2 * j + 1] * d1[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) partials[(size_t) (part * 3 + k) * n + s] = t[0][k] + t[1][k];
+  }
+}
+
+__global__ __launch_bounds__(256) void pos_grad_sum_kernel(int n, const float* __restrict__ partials, float* __restrict__ out) {
+  const int64_t s = (int64_t) blockIdx.x * 256 + threadIdx.x;
+  if (s >= n) return;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    float t = partials[(size_t) k * n + s];
+#pragma unroll
+    for (int p = 1; p < F2N_N_PARTS; p++) t = t + partials[(size_t) (p * 3 + k) * n + s];
+    out[s * 3 + k] = t;
+  }
+}
+
 static inline unsigned f2n_wave_grid(int n_units, int waves_per_block) {
   // enough blocks to fill 256 CUs several times over, capped so that each wave still amortises its setup
   long blocks = ((long) n_units + waves_per_block - 1) / waves_per_block;
@@ -1524,6 +1678,27 @@ static inline bool f2n_use_bins(int n, int level_entries) {
   if (F2N_REFERENCE_NUMERICS) return false;  // per-addend f16 atomics in arrival order, as the reference (f2n_scatter_frag)
   return n >= F2N_BIN_MIN_N && n <= F2N_BIN_NB * (F2N_BIN_MAX_CHUNK - 256) && level_entries >= 2 * F2N_BIN_ENTRIES && (level_entries & (level_entries - 1)) == 0 &&
          (level_entries >> F2N_BIN_SHIFT) <= F2N_BIN_MAX_BINS;
+}
+
+static int f2n_pos_grad_launch(hipStream_t st, int n, const F2nHashArgs& h, const int32_t* local_idx, const int32_t* local_size,
+                               const float* level_scale, const float* pts_warped, const int32_t* volume_idx, int vol_stride,
+                               const float* dx, size_t dx_ss, size_t dx_ps, float* out_df0_dw) {
+  float* partials = (float*) f2n_ws_get(F2N_WS_DGRAD_PART, sizeof(float) * 3 * F2N_N_PARTS * (size_t) n);
+  if (partials == nullptr) return F2N_ERR_INVALID_ARG;
+  long per_part = ((long) n + 255) / 256;
+  if (per_part > 256) per_part = 256;  // 32 CUs per XCD x 8 resident 256-thread blocks, as the forward gather
+  const size_t stage_bytes = (size_t) 2 * h.n_volumes * 6 * sizeof(uint32_t);
+  const dim3 grid((unsigned) (F2N_N_PARTS * per_part)), block(256);
+  if (stage_bytes <= 20000 && n >= 64 * 256)  // (f2n_gather_variant's rule)
+    hipLaunchKernelGGL(hash_pos_grad_kernel<true>, grid, block, stage_bytes, st, n, h, local_idx, local_size, level_scale, pts_warped,
+                       volume_idx, vol_stride, dx, dx_ss, dx_ps, partials);
+  else
+    hipLaunchKernelGGL(hash_pos_grad_kernel<false>, grid, block, 0, st, n, h, local_idx, local_size, level_scale, pts_warped,
+                       volume_idx, vol_stride, dx, dx_ss, dx_ps, partials);
+  const int rc = f2n_launch_status();
+  if (rc != F2N_OK) return rc;
+  hipLaunchKernelGGL(pos_grad_sum_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, st, n, partials, out_df0_dw);
+  return f2n_launch_status();
 }
 
 extern "C" {
@@ -1824,6 +1999,38 @@ int f2n_field_mlp_planes(void* stream, int n, const void* planes_h, const void* 
                      (const half_t*) mlp_params_h, out_feat_f32, nullptr, out_f0, (half_t*) save_x_h, (const half_t*) planes_h,
                      nullptr, nullptr, nullptr);
   return f2n_launch_status();
+}
+
+int f2n_hash_pos_grad(void* stream, int n, int n_volumes, const void* table_h, const int32_t* prim_pool, const int32_t* local_idx,
+                      const int32_t* local_size, const float* bias_pool, const float* level_scale, const float* pts_warped,
+                      const int32_t* volume_idx, int vol_stride, const float* dx, float* out_df0_dw) {
+  if (n < 0 || n_volumes <= 0 || vol_stride < 1) return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  if (dx == nullptr || out_df0_dw == nullptr || ((uintptr_t) dx & 15)) return F2N_ERR_INVALID_ARG;  // 16-byte loads of dx
+  F2nHashArgs h = {(const half_t*) table_h, prim_pool, bias_pool, n_volumes};
+  return f2n_pos_grad_launch((hipStream_t) stream, n, h, local_idx, local_size, level_scale, pts_warped, volume_idx, vol_stride, dx,
+                             F2N_D_IN, 4, out_df0_dw);
+}
+
+int f2n_field_density_grad(void* stream, int n, int n_volumes, const void* table_h, const int32_t* prim_pool, const int32_t* local_idx,
+                           const int32_t* local_size, const float* bias_pool, const float* level_scale, const float* pts_warped,
+                           const int32_t* volume_idx, int vol_stride, const void* mlp_params_h, const void* x_h, float* out_dx,
+                           float* out_df0_dw) {
+  if (n < 0 || n_volumes <= 0 || vol_stride < 1) return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  if (mlp_params_h == nullptr || x_h == nullptr || out_df0_dw == nullptr || ((uintptr_t) x_h & 15) || ((uintptr_t) out_dx & 15))
+    return F2N_ERR_INVALID_ARG;  // 16-byte loads of x, 16-byte stores of dx
+  float* planes = (float*) f2n_ws_get(F2N_WS_DGRAD_DX, sizeof(float) * F2N_D_IN * (size_t) n);
+  if (planes == nullptr) return F2N_ERR_INVALID_ARG;
+  long blocks = ((long) n + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(mlp_input_grad_kernel, dim3((unsigned) blocks), dim3(256), 0, (hipStream_t) stream, n, (const half_t*) mlp_params_h,
+                     (const half_t*) x_h, out_dx, planes);
+  const int rc = f2n_launch_status();
+  if (rc != F2N_OK) return rc;
+  F2nHashArgs h = {(const half_t*) table_h, prim_pool, bias_pool, n_volumes};
+  return f2n_pos_grad_launch((hipStream_t) stream, n, h, local_idx, local_size, level_scale, pts_warped, volume_idx, vol_stride, planes,
+                             4, 4 * (size_t) n, out_df0_dw);
 }
 
 int f2n_field_fwd_cached(void* stream, int n, int n_cache, const int32_t* src_rows, const void* x_cache_h,

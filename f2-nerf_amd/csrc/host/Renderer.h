@@ -301,8 +301,20 @@ class Renderer : public Pipe {
   std::tuple<Tensor, Tensor> QueryRadiance(const Tensor& world, const Tensor& dirs);
   // ExtractMesh, then: the components of fewer than min_component_faces faces removed, normals of the surviving vertices from
   // the same density grid, colours = the radiance at each vertex seen along its inward normal ((0, 0, -1) where the normal is 0)
+  // normal_source "field": the normals are FieldNormals at the kept vertices (a vertex whose field normal is the zero vector takes
+  // its grid normal) and the colours follow them; "grid" (the default): the density grid's normals
   MeshAttrs ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
-                             bool normals, bool colors);
+                             bool normals, bool colors, const std::string& normal_source = "grid");
+  // (density [n], grad [n,3]) at world points: the density of QueryDensity, bit for bit, and its analytic gradient with respect to the
+  // world position, sigma J^T df0/dw (f2n_field_density_grad / f2n_density_grad_scatter: the hash table's trilinear blend, the
+  // density MLP and the leaf's warp differentiated exactly, fp32); zeros where no listed leaf holds the point.  Field shapes
+  // without the fused kernels take df0/dx from f2n_mlp_bwd (its h16 roundings) and f2n_hash_pos_grad.  The same side-effect contract
+  // as QueryDensity; reads back only the row count.
+  std::tuple<Tensor, Tensor> QueryDensityGrad(const Tensor& world);
+  // -grad / |grad| of QueryDensityGrad (the sign of GridNormals); 0 where |grad| is 0 or not finite, or the point is empty
+  Tensor FieldNormals(const Tensor& world);
+  // density, grad and (optionally) unit normals of at most density_slab_points_ points
+  void DensityGradChunk(const Tensor& world, Tensor& density, Tensor& grad, Tensor* normals);
   int64_t density_slab_points_ = int64_t(1) << 22;
 
   int LoadStates(const std::vector<Tensor>& states, int idx) override;

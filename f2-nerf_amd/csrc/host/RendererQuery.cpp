@@ -91,6 +91,79 @@ std::tuple<Tensor, Tensor> Renderer::QueryRadiance(const Tensor& world, const Te
   return {density, rgb};
 }
 
+void Renderer::DensityGradChunk(const Tensor& w, Tensor& density, Tensor& grad, Tensor* normals) {
+  auto* sampler = static_cast<PersSampler*>(pts_sampler_.get());
+  auto* field = static_cast<Hash3DAnchored*>(scene_field_.get());
+  auto located = sampler->LocatePoints(w);
+  const Tensor& warped = std::get<0>(located);
+  const Tensor& anchors = std::get<1>(located);
+  const int64_t n = anchors.size(0);
+  if (n == 0) return;
+  Tensor counts = torch::empty({n}, DevI32()), se = torch::empty({n, 2}, DevI32()), total = torch::empty({1}, DevI32());
+  Tensor cpts = torch::empty({n, 3}, DevF32()), cvol = torch::empty({n}, DevI32());
+  F2N_CALL(f2n_located_compact(CurStream(), (int) n, I32P(anchors), F32P(warped), I32P(counts), I32P(se), I32P(total), F32P(cpts),
+                               I32P(cvol), nullptr));
+  const int m = total.item<int>();  // (the field kernels take their row count from the host, as in DensityOfLocated)
+  Tensor f0 = torch::zeros({1}, DevF32()), g = torch::zeros({1, 3}, DevF32());
+  if (m > 0) {
+    Tensor keep = field->prepass_x_;  // a batch sampled ahead may still be served from this cache
+    Tensor p = cpts.narrow(0, 0, m), v = cvol.narrow(0, 0, m);
+    g = torch::empty({m, 3}, DevF32());
+    if (field->fused_ok_) {
+      f0 = field->QueryDensityPreAct(p, v, /*keep_features=*/true);
+      TORCH_CHECK(field->prepass_x_.defined(), "no pre-pass feature cache for this query");
+      F2N_CALL(f2n_field_density_grad(CurStream(), m, field->n_volumes_, VoidP(field->feat_pool_h_), I32P(field->prim_pool_),
+                                      I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
+                                      F32P(field->level_scale_), F32P(p), I32P(v), 1, VoidP(field->mlp_->params_h_),
+                                      VoidP(field->prepass_x_), nullptr, F32P(g)));
+    } else {  // network shapes without the fused kernels: df0/dx from the general MLP backward (its h16 roundings), dy = e_0, no loss scale
+      f0 = field->QueryDensityPreAct(p, v, /*keep_features=*/false);
+      auto& mlp = *field->mlp_;
+      Tensor x = field->HashEncode(p, v).to(torch::kFloat32).contiguous();
+      Tensor dy = torch::zeros({m, F2N_MLP_OUT_PAD}, DevF32());
+      dy.select(1, 0).fill_(1.f);
+      Tensor dparams = torch::zeros({mlp.n_params_}, DevF32()), dx = torch::empty({m, mlp.d_in_}, DevF32());
+      F2N_CALL(f2n_mlp_bwd(CurStream(), m, mlp.d_in_, mlp.d_hidden_, mlp.n_hidden_layers_, 1.f, VoidP(mlp.params_h_), F32P(x), F32P(dy),
+                           F32P(dparams), F32P(dx)));
+      F2N_CALL(f2n_hash_pos_grad(CurStream(), m, field->n_volumes_, VoidP(field->feat_pool_h_), I32P(field->prim_pool_),
+                                 I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
+                                 F32P(field->level_scale_), F32P(p), I32P(v), 1, F32P(dx), F32P(g)));
+    }
+    field->prepass_x_ = keep;
+  }
+  auto& o = *sampler->pers_octree_;
+  F2N_CALL(f2n_density_grad_scatter(CurStream(), (int) n, F32P(w), I32P(anchors), I32P(se), VoidP(o.pers_trans_gpu_), F32P(f0), F32P(g),
+                                    F32P(density), F32P(grad), normals != nullptr ? F32P(*normals) : nullptr));
+}
+
+std::tuple<Tensor, Tensor> Renderer::QueryDensityGrad(const Tensor& world) {
+  torch::NoGradGuard g;
+  Tensor w = world.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  const int64_t n = w.size(0);
+  TORCH_CHECK(n <= INT32_MAX, "too many points");
+  Tensor density = torch::empty({n}, DevF32()), grad = torch::empty({n, 3}, DevF32());
+  for (int64_t i0 = 0; i0 < n; i0 += density_slab_points_) {  // (bounded workspaces, as DensityGrid's slabs)
+    const int64_t c = std::min(density_slab_points_, n - i0);
+    Tensor d = density.narrow(0, i0, c), gr = grad.narrow(0, i0, c);
+    DensityGradChunk(w.narrow(0, i0, c), d, gr, nullptr);
+  }
+  return {density, grad};
+}
+
+Tensor Renderer::FieldNormals(const Tensor& world) {
+  torch::NoGradGuard g;
+  Tensor w = world.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  const int64_t n = w.size(0);
+  TORCH_CHECK(n <= INT32_MAX, "too many points");
+  Tensor normals = torch::empty({n, 3}, DevF32());
+  for (int64_t i0 = 0; i0 < n; i0 += density_slab_points_) {
+    const int64_t c = std::min(density_slab_points_, n - i0);
+    Tensor density = torch::empty({c}, DevF32()), grad = torch::empty({c, 3}, DevF32()), nr = normals.narrow(0, i0, c);
+    DensityGradChunk(w.narrow(0, i0, c), density, grad, &nr);
+  }
+  return normals;
+}
+
 GridSpec Renderer::MakeGridSpec(const std::vector<float>& lo, const std::vector<float>& hi, int res) {
   TORCH_CHECK(lo.size() == 3 && hi.size() == 3, "lo / hi must have three coordinates");
   TORCH_CHECK(res >= 1 && res <= 1024, "resolution must be in [1, 1024]");
@@ -202,8 +275,10 @@ std::tuple<Tensor, Tensor, Tensor> MeshFilterComponents(const Tensor& verts, con
 }
 
 MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level,
-                                     int min_component_faces, bool normals, bool colors) {
+                                     int min_component_faces, bool normals, bool colors, const std::string& normal_source) {
   torch::NoGradGuard g;
+  const bool from_field = normal_source == "field";
+  TORCH_CHECK(from_field || normal_source == "grid", "normal_source must be \"grid\" or \"field\", got \"", normal_source, "\"");
   const GridSpec s = MakeGridSpec(lo, hi, res);
   Tensor grid = DensityGrid(lo, hi, res);
   MeshAttrs out;
@@ -215,6 +290,10 @@ MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::ve
   }
   if (!normals && !colors) return out;
   Tensor nrm = GridNormals(grid, out.verts, s.lo, s.step);
+  if (from_field) {  // the field's own gradient at the vertex; the grid's where that vanishes
+    Tensor fn = FieldNormals(out.verts);
+    nrm = torch::where((fn == 0).all(1, /*keepdim=*/true), nrm, fn).contiguous();
+  }
   if (normals) out.normals = nrm;
   if (colors) {
     // a vertex colour is the radiance AT the vertex seen along the inward normal (by a viewer in front of the surface)

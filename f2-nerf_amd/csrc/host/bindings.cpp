@@ -326,12 +326,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("world"), py::arg("dirs"))
       .def("extract_mesh_attrs",  // extract_mesh + floater removal, normals from the density grid, colours along the inward normal
            [](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
-              bool normals, bool colors) {
+              bool normals, bool colors, const std::string& normal_source) {
              MeshAttrs a;
              {
                py::gil_scoped_release no_gil;
                r.FinishPending();
-               a = r.renderer_->ExtractMeshAttrs(lo, hi, res, level, min_component_faces, normals, colors);
+               a = r.renderer_->ExtractMeshAttrs(lo, hi, res, level, min_component_faces, normals, colors, normal_source);
              }
              py::dict d;
              d["verts"] = a.verts;
@@ -341,7 +341,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return d;
            },
            py::arg("lo"), py::arg("hi"), py::arg("res"), py::arg("level"), py::arg("min_component_faces") = 0, py::arg("normals") = true,
-           py::arg("colors") = true)
+           py::arg("colors") = true, py::arg("normal_source") = "grid")  // "field": normals (and colours) from the field's own gradient
+      .def("query_density_grad",  // world [n,3] -> [density [n] (= query_density), grad [n,3] = its analytic world-space gradient]
+           [](ExpRunner& r, const Tensor& world) {
+             py::gil_scoped_release no_gil;
+             r.FinishPending();
+             auto t = r.renderer_->QueryDensityGrad(world);
+             return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
+           },
+           py::arg("world"))
+      .def("field_normals",  // world [n,3] -> unit normals [n,3] = -grad / |grad| of query_density_grad, 0 where that is 0 or not finite
+           [](ExpRunner& r, const Tensor& world) {
+             py::gil_scoped_release no_gil;
+             r.FinishPending();
+             return r.renderer_->FieldNormals(world);
+           },
+           py::arg("world"))
       .def_property("density_slab_points",  // points per z-slab of density_grid (bounds its workspaces)
                     [](ExpRunner& r) { return r.renderer_->density_slab_points_; },
                     [](ExpRunner& r, int64_t n) { r.renderer_->density_slab_points_ = std::max<int64_t>(1, n); })

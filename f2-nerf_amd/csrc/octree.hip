@@ -655,6 +655,38 @@ __global__ void __launch_bounds__(256) radiance_scatter_kernel(int n, const int3
   for (int c = 0; c < 3; c++) rgb[i * 3 + c] = hit ? rgb_rows[k * 3 + c] : 0.f;
 }
 
+// density_scatter_kernel with the analytic gradient: sigma (the same expression, the same bits) and sigma * J^T * df0/dw, J = the
+// leaf's warp Jacobian at the world point; optionally the unit normal -grad / |grad| by the rule of grid_normals_kernel.
+__global__ void __launch_bounds__(256) density_grad_scatter_kernel(int n, const float* __restrict__ pts_world, const int32_t* __restrict__ anchors,
+                                                                  const int32_t* __restrict__ start_end, const F2nTransInfo* __restrict__ transes,
+                                                                  const float* __restrict__ f0, const float* __restrict__ df0_dw,
+                                                                  float* __restrict__ density, float* __restrict__ grad,
+                                                                  float* __restrict__ normal) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int t = anchors[i * 3];
+  float sigma = 0.f, gr[3] = {0.f, 0.f, 0.f};
+  if (t >= 0) {
+    const int64_t k = start_end[i * 2];
+    sigma = expf(f0[k] - F2N_DENSITY_SHIFT);
+    const float p[3] = {pts_world[i * 3], pts_world[i * 3 + 1], pts_world[i * 3 + 2]};
+    const float g[3] = {df0_dw[k * 3], df0_dw[k * 3 + 1], df0_dw[k * 3 + 2]};
+    float jac[3][3];
+    f2n_warp_jac(transes + t, p, jac);
+#pragma unroll
+    for (int c = 0; c < 3; c++) gr[c] = sigma * f2n_sum3(jac[0][c] * g[0], jac[1][c] * g[1], jac[2][c] * g[2]);
+  }
+  density[i] = sigma;
+#pragma unroll
+  for (int c = 0; c < 3; c++) grad[i * 3 + c] = gr[c];
+  if (normal != nullptr) {
+    const float len = sqrtf(F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(gr[0], gr[0]), F2N_MUL_RN(gr[1], gr[1])), F2N_MUL_RN(gr[2], gr[2])));
+    const bool ok = len > 0.f && len < __builtin_huge_valf();  // (false for NaN as well)
+#pragma unroll
+    for (int c = 0; c < 3; c++) normal[i * 3 + c] = ok ? -F2N_DIV_RN(gr[c], len) : 0.f;
+  }
+}
+
 // Component `axis` of the corner gradient G at corner (x, y, z): central difference over 2 step in the interior, the one-sided
 // difference over step on the two border planes of that axis.
 __device__ __forceinline__ float corner_gradient(const float* __restrict__ g, int x, int y, int z, int nx, int ny, int nz, int axis,
@@ -819,6 +851,18 @@ int f2n_radiance_scatter(void* stream, int n, const int32_t* anchors, const int3
   if (n == 0) return F2N_OK;
   hipLaunchKernelGGL(radiance_scatter_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, anchors, start_end, f0,
                      rgb_rows, density, rgb);
+  return f2n_launch_status();
+}
+
+int f2n_density_grad_scatter(void* stream, int n, const float* pts_world, const int32_t* anchors, const int32_t* start_end,
+                             const void* transes, const float* f0, const float* df0_dw, float* out_density, float* out_grad,
+                             float* out_normal) {
+  if (n < 0 || (n > 0 && (pts_world == nullptr || anchors == nullptr || start_end == nullptr || transes == nullptr || out_density == nullptr ||
+                          out_grad == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  hipLaunchKernelGGL(density_grad_scatter_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, pts_world, anchors,
+                     start_end, (const F2nTransInfo*) transes, f0, df0_dw, out_density, out_grad, out_normal);
   return f2n_launch_status();
 }
 

@@ -10,6 +10,9 @@ Options (hydra-style overrides, no `mesh` group in the configs):
   mesh.bbox_min / mesh.bbox_max  the box in the NORMALISED scene frame (default: pts_sampler.bbox_min / bbox_max, [-1, 1]^3,
                    which holds the normalised cameras; the octree's root cube is 512 wide and mostly empty)
   mesh.normals     true: per-vertex normals from the density grid's gradient (float nx, ny, nz; default false)
+  mesh.normal_source  grid | field (default grid): where the normals of mesh.normals (and the view directions of mesh.colors) come
+                   from -- the density grid's central differences, or the field's own analytic gradient at every vertex
+                   (runner.query_density_grad; a vertex where that vanishes keeps its grid normal)
   mesh.colors      true: per-vertex colours (uchar red, green, blue; default false): the radiance AT the vertex seen along the
                    inward normal -- a single-point query, not a volume-rendered pixel
   mesh.min_component_faces  N > 1: connected components of fewer than N faces ("floaters") are dropped (default 0: none)
@@ -31,7 +34,17 @@ def options(cfg):
     hi = [float(v) for v in m.get("bbox_max", ps.get("bbox_max", [1.0, 1.0, 1.0]))]
     return {"resolution": int(m.get("resolution", 256)), "level": float(m.get("level", DEFAULT_LEVEL)), "bbox_min": lo,
             "bbox_max": hi, "normals": _flag(m.get("normals", False)), "colors": _flag(m.get("colors", False)),
-            "min_component_faces": int(m.get("min_component_faces", 0))}
+            "min_component_faces": int(m.get("min_component_faces", 0)), "normal_source": _normal_source(m.get("normal_source", "grid"))}
+
+
+NORMAL_SOURCES = ("grid", "field")
+
+
+def _normal_source(v):
+    s = str(v).strip().lower()
+    if s not in NORMAL_SOURCES:
+        raise ValueError("mesh.normal_source must be one of %s, got %r" % (" | ".join(NORMAL_SOURCES), v))
+    return s
 
 
 def _flag(v):
@@ -95,7 +108,7 @@ def extract(runner, cfg, scene, exp_dir):
         write_ply(path, v, faces.cpu().numpy())
     else:
         m = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"], o["normals"],
-                                      o["colors"])
+                                      o["colors"], o["normal_source"])
         verts, faces = m["verts"], m["faces"]
         v = to_world(verts.cpu().numpy(), scene["center"], scene["radius"])
         # (the world frame is a uniform scale and a shift of the normalised one: normals are the same in both)

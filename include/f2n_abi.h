@@ -900,6 +900,31 @@ int f2n_mesh_filter_count(void* stream, int n_verts, int n_faces, const int32_t*
 int f2n_mesh_filter_emit(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/,
                          const int32_t* vert_keep, const int32_t* vert_start_end, const int32_t* face_keep, const int32_t* face_start_end,
                          float* out_verts, int32_t* vert_src, int32_t* out_faces);
+/* The analytic gradient of the density pre-activation f0 = (W2 relu(W1 x))[0] with respect to the WARPED position w of n points, for the
+ * shipped field shape (32 -> 64 -> 16): x = the h16 hash features of the points ([n,32], what f2n_field_fwd saves in save_x_h).
+ *   df0/dx = W1^T (m . W2[0,:]), m_j = 1 where the fp32 pre-activation (W1 x)_j of the h16 x is > 0, else 0;
+ *   df0/dw = sum_l (scale_l / 2) sum_c df0/dx_{l,c} d(blend_{l,c})/d(a, b, c): the derivative of the eight weights of the level's cell
+ *   (the one floorf chose: on a cell face the one-sided derivative of that cell; q < 0 saturates as in the forward) with respect to
+ *   the fractions, corner bit 2 = x, 1 = y, 0 = z.
+ * Every input is an exact h16 value; all arithmetic is fp32 in a fixed order (levels in pairs, pairs in order): no h16 rounding, no
+ * loss scale, no atomics, the same bits on every call.  out_dx [n,32] f32 (or NULL) receives df0/dx, out_df0_dw [n,3] f32 df0/dw.
+ * The world-space gradient of sigma = exp(f0 - 3) is sigma J^T df0/dw (f2n_density_grad_scatter).  No reference counterpart. */
+int f2n_field_density_grad(void* stream, int n, int n_volumes, const void* table_h, const int32_t* prim_pool, const int32_t* local_idx,
+                           const int32_t* local_size, const float* bias_pool, const float* level_scale, const float* pts_warped,
+                           const int32_t* volume_idx, int vol_stride, const void* mlp_params_h, const void* x_h /*[n,32] h16*/,
+                           float* out_dx /*[n,32] f32 or NULL*/, float* out_df0_dw /*[n,3] f32*/);
+/* The second half of the above on its own: df0/dw from ANY df0/dx [n,32] f32 (16-byte aligned), for field shapes the fused entry does
+ * not cover -- there dx comes from f2n_mlp_bwd(dy = e_0, loss_scale = 1) and carries that kernel's h16 roundings. */
+int f2n_hash_pos_grad(void* stream, int n, int n_volumes, const void* table_h, const int32_t* prim_pool, const int32_t* local_idx,
+                      const int32_t* local_size, const float* bias_pool, const float* level_scale, const float* pts_warped,
+                      const int32_t* volume_idx, int vol_stride, const float* dx /*[n,32] f32*/, float* out_df0_dw /*[n,3] f32*/);
+/* f2n_density_scatter with the gradient: per point i with k = start_end[i,0], out_density[i] = exp(f0[k] - 3) (the same expression, the
+ * same bits) and out_grad[i] = out_density[i] * J^T df0_dw[k], J = f2n_warp_jac of transes[anchors[i,0]] at pts_world[i]; exact zeros
+ * for the empty points (anchors[i,0] < 0).  out_normal [n,3] (or NULL) = -out_grad / |out_grad| by the rule of f2n_grid_normals:
+ * (0, 0, 0) where |out_grad| is 0 or not finite.  f0 / df0_dw may be NULL when every point is empty.  No reference counterpart. */
+int f2n_density_grad_scatter(void* stream, int n, const float* pts_world /*[n,3]*/, const int32_t* anchors /*[n,3]*/,
+                             const int32_t* start_end /*[n,2]*/, const void* transes, const float* f0, const float* df0_dw /*[m,3]*/,
+                             float* out_density /*[n]*/, float* out_grad /*[n,3]*/, float* out_normal /*[n,3] or NULL*/);
 
 #ifdef __cplusplus
 }
