@@ -786,6 +786,19 @@ def density_grad_scatter(n, pts_world, anchors, start_end, transes, f0, df0_dw, 
         "f2n_density_grad_scatter")
 
 
+def composite_geometry(n_rays, pts_start_end, weights, t, rays_o, rays_d, anchors, transes, df0_dw, tau, out_opacity, out_normal, out_surf_idx,
+                       out_surf_t, out_surf_point, out_surf_normal, out_sample_grad=None, out_sample_normal=None):
+    """Geometry buffers of rendered rays from f2n_composite_fwd's weights (f2n_composite_geometry): opacity, composited unit normal and
+    the first sample whose accumulated weight reaches tau; rays_d are the unit directions the samples' t count along."""
+    _ck(lib().f2n_composite_geometry(_stream(), _i(n_rays), _p(pts_start_end, "i32", n_rays == 0), _p(weights, "f32", n_rays == 0),
+                                     _p(t, "f32", n_rays == 0), _p(rays_o, "f32", n_rays == 0), _p(rays_d, "f32", n_rays == 0),
+                                     _p(anchors, "i32", n_rays == 0), _p(transes, "u8", n_rays == 0), _p(df0_dw, "f32", n_rays == 0), _f(tau),
+                                     _p(out_opacity, "f32", n_rays == 0), _p(out_normal, "f32", n_rays == 0), _p(out_surf_idx, "i32", n_rays == 0),
+                                     _p(out_surf_t, "f32", n_rays == 0), _p(out_surf_point, "f32", n_rays == 0),
+                                     _p(out_surf_normal, "f32", n_rays == 0), _p(out_sample_grad, "f32", True), _p(out_sample_normal, "f32", True)),
+        "f2n_composite_geometry")
+
+
 def mesh_from_grid(grid, level, lo=(0.0, 0.0, 0.0), step=1.0):
     """Marching-tetrahedra iso-surface of a float32 grid [nz, ny, nx] (f2n_mesh_count -> f2n_mesh_emit): (verts [V,3], faces [F,3]).
     Reads back the two totals only (they size the outputs)."""

@@ -187,3 +187,35 @@ __device__ __forceinline__ void f2n_warp_jac(const F2nTransInfo* __restrict__ tr
       jac[r][c] = f2n_sum12(e);
     }
 }
+
+// Single roundings that the compiler may not contract into an FMA.  (The CPU emulation of tests/wave_emul/ has no __f*_rn
+// intrinsics; it compiles with -ffp-contract=off like the product, so the plain operators are the same operations there.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define F2N_ADD_RN(a, b) __fadd_rn(a, b)
+#define F2N_SUB_RN(a, b) __fsub_rn(a, b)
+#define F2N_MUL_RN(a, b) __fmul_rn(a, b)
+#define F2N_DIV_RN(a, b) __fdiv_rn(a, b)
+#else
+#define F2N_ADD_RN(a, b) ((a) + (b))
+#define F2N_SUB_RN(a, b) ((a) - (b))
+#define F2N_MUL_RN(a, b) ((a) * (b))
+#define F2N_DIV_RN(a, b) ((a) / (b))
+#endif
+
+// J^T g: the gradient with respect to the world position p of a function whose gradient with respect to the warped position is g,
+// J = f2n_warp_jac of the leaf's transform at p.  Shared by density_grad_scatter_kernel (octree.hip) and composite_geometry_kernel
+// (render.hip), which must agree bit for bit.
+__device__ __forceinline__ void f2n_warp_jac_t_mul(const F2nTransInfo* __restrict__ tr, const float* p, const float* g, float* out) {
+  float jac[3][3];
+  f2n_warp_jac(tr, p, jac);
+#pragma unroll
+  for (int c = 0; c < 3; c++) out[c] = f2n_sum3(jac[0][c] * g[0], jac[1][c] * g[1], jac[2][c] * g[2]);
+}
+// sign * v / |v| by the rule of f2n_grid_normals: (0, 0, 0) where |v| is 0 or not finite (NaN included)
+template <bool NEGATE>
+__device__ __forceinline__ void f2n_unit3(const float* v, float* out) {
+  const float len = sqrtf(F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(v[0], v[0]), F2N_MUL_RN(v[1], v[1])), F2N_MUL_RN(v[2], v[2])));
+  const bool ok = len > 0.f && len < __builtin_huge_valf();  // (false for NaN as well)
+#pragma unroll
+  for (int c = 0; c < 3; c++) out[c] = ok ? (NEGATE ? -F2N_DIV_RN(v[c], len) : F2N_DIV_RN(v[c], len)) : 0.f;
+}

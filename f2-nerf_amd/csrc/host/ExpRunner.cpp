@@ -3,6 +3,8 @@
 // (image loading, ray generation) is outside the hot path: rays and ground-truth colours are inputs here.
 // The optimiser is the fused Adam of csrc/optim.hip driven over the modules' parameter groups; multi-GPU data
 // parallelism hooks in through `sync_` (GradSyncPipeline.h: in front of the optimiser, or pipelined under the next step's sampling).
+#include <functional>
+
 #include "ExpRunner.h"
 
 #include <deque>
@@ -647,6 +649,46 @@ std::vector<Tensor> ExpRunner::RenderWholeImage(const Tensor& rays_o, const Tens
   pred_disp = pred_disp / pred_disp.max();
   first_oct_disp = first_oct_disp.min() / first_oct_disp;
   return {pred_colors, first_oct_disp, pred_disp};
+}
+
+GeometryResult ExpRunner::RenderGeometry(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds, float tau, bool keep_samples) {
+  FinishPending();
+  torch::NoGradGuard no_grad;
+  const int n_rays = rays_d.size(0);
+  const int chunk = std::max(render_chunk_rays_, 1);
+  TORCH_CHECK(n_rays >= 1, "no rays");
+  TORCH_CHECK(!keep_samples || n_rays <= chunk, "return_samples needs the rays in one chunk: ", n_rays, " rays, render_chunk_rays = ", chunk);
+  auto prev = global_data_pool_->mode_;
+  global_data_pool_->mode_ = RunningMode::VALIDATE;
+  std::vector<GeometryResult> parts;
+  try {
+    for (int i = 0; i < n_rays; i += chunk) {
+      const int hi = std::min(i + chunk, n_rays);
+      parts.push_back(renderer_->RenderGeometry(rays_o.index({Slc(i, hi)}).contiguous(), rays_d.index({Slc(i, hi)}).contiguous(),
+                                                bounds.index({Slc(i, hi)}).contiguous(), tau, keep_samples));
+    }
+  } catch (...) {
+    global_data_pool_->mode_ = prev;
+    throw;
+  }
+  global_data_pool_->mode_ = prev;
+  if (parts.size() == 1) return parts[0];
+  GeometryResult out;
+  auto cat = [&](const std::function<Tensor(const GeometryResult&)>& f) {
+    std::vector<Tensor> v;
+    for (const auto& p : parts) v.push_back(f(p));
+    return torch::cat(v, 0);
+  };
+  out.render.colors = cat([](const GeometryResult& p) { return p.render.colors; });
+  out.render.disparity = cat([](const GeometryResult& p) { return p.render.disparity; });
+  out.render.depth = cat([](const GeometryResult& p) { return p.render.depth; });
+  out.opacity = cat([](const GeometryResult& p) { return p.opacity; });
+  out.normals = cat([](const GeometryResult& p) { return p.normals; });
+  out.surf_idx = cat([](const GeometryResult& p) { return p.surf_idx; });
+  out.surf_t = cat([](const GeometryResult& p) { return p.surf_t; });
+  out.surf_points = cat([](const GeometryResult& p) { return p.surf_points; });
+  out.surf_normals = cat([](const GeometryResult& p) { return p.surf_normals; });
+  return out;
 }
 
 // The per-image body of ExpRunner::TestImages (ExpRunner.cpp:353-369): render camera idx of the data set, quantise the

@@ -66,6 +66,9 @@ class ExpRunner {
   int render_chunk_rays_ = 65536;   // rays per chunk of RenderWholeImage on that path
   std::vector<Tensor> RenderRays(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds);
   std::vector<Tensor> RenderWholeImage(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds);
+  // Renderer::RenderGeometry over any number of rays in chunks of render_chunk_rays_ (VALIDATE mode, a streaming step flushed first).
+  // keep_samples needs all rays in one chunk; over several chunks surf_idx counts within the ray's own chunk.
+  GeometryResult RenderGeometry(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds, float tau, bool keep_samples);
   float TestImagePSNR(Dataset& dataset, int idx);       // 8-bit quantised prediction, as ExpRunner.cpp:360-369
   std::vector<float> TestImages(Dataset& dataset);      // per-view PSNR of the test set, then the mean
   Tensor RenderPathFrame(Dataset& dataset, const Tensor& pose, int res_level = 1);

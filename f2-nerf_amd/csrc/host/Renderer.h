@@ -85,6 +85,15 @@ struct MeshAttrs {  // Renderer::ExtractMeshAttrs; normals / colors are undefine
   Tensor verts, faces, normals, colors;
 };
 
+// Renderer::RenderGeometry: RenderForward's result and the geometry buffers of f2n_composite_geometry
+struct GeometryResult {
+  RenderResult render;  // colors, disparity, depth, weights, idx_start_end: RenderForward's, bit for bit
+  Tensor opacity, normals;                              // [R], [R,3]
+  Tensor surf_idx, surf_t, surf_points, surf_normals;   // [R] int32 (-1: none), [R], [R,3], [R,3]
+  // keep_samples only: the surviving samples ([M,3] warped, [M,3] int32, [M], [M]) and their J^T df0/dw / unit normals [M,3]
+  Tensor pts, anchors, t, dt, sample_grad, sample_normals;
+};
+
 struct TrainOutputs {
   Tensor losses;  // device [8]: loss, color, var, disp, tv, mse, 0, 0 (f2n_train_loss)
   Tensor colors;
@@ -315,6 +324,13 @@ class Renderer : public Pipe {
   Tensor FieldNormals(const Tensor& world);
   // density, grad and (optionally) unit normals of at most density_slab_points_ points
   void DensityGradChunk(const Tensor& world, Tensor& density, Tensor& grad, Tensor* normals);
+  // RenderForward plus geometry buffers (f2n_composite_geometry): per ray the opacity (sum of the weights), the weight-composited
+  // unit normal, and the surface = the first sample at which the accumulated weight reaches tau (index, t, world point, normal; -1 and
+  // zeros where none does).  The samples' normals are -J^T df0/dw / |.| at o + t d: f2n_field_density_grad on the survivors' rows of
+  // the pre-pass cache (f2n_mlp_bwd + f2n_hash_pos_grad for field shapes without the fused kernels).  Colours, disparity, depth and
+  // weights are RenderForward's bit for bit.  Inference mode only; the side-effect contract of RenderForward.  Unlike RenderForward
+  // this path reads the survivor count back, once per call (the gradient kernels take their row count from the host).
+  GeometryResult RenderGeometry(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds, float tau, bool keep_samples);
   int64_t density_slab_points_ = int64_t(1) << 22;
 
   int LoadStates(const std::vector<Tensor>& states, int idx) override;

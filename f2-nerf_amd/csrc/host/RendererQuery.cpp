@@ -164,6 +164,135 @@ Tensor Renderer::FieldNormals(const Tensor& world) {
   return normals;
 }
 
+// RenderForward step by step (SampleAndFilter -> f2n_field_shade_fwd_dyn -> f2n_composite_fwd: the same launches on the same inputs,
+// so colours, disparity, depth and weights are its bits), then the survivors' df0/dw and f2n_composite_geometry.  The gradient
+// kernels take their row count from the host and want the survivors' h16 features as rows of their own, so this path -- unlike
+// RenderForward, which leaves the count on the device -- reads the survivor count back, once per call (= per chunk of
+// ExpRunner::RenderGeometry), and takes the rows out of the pre-pass cache through src_rows before the cache is dropped.
+GeometryResult Renderer::RenderGeometry(const Tensor& rays_o_in, const Tensor& rays_d_in, const Tensor& bounds, float tau, bool keep_samples) {
+  auto* gdp = global_data_pool_;
+  auto* sampler = static_cast<PersSampler*>(pts_sampler_.get());
+  auto* field = static_cast<Hash3DAnchored*>(scene_field_.get());
+  auto* shader = static_cast<SHShader*>(shader_.get());
+  TORCH_CHECK(gdp->mode_ != RunningMode::TRAIN, "RenderGeometry is an inference path");
+  TORCH_CHECK(tau > 0.f && tau <= 1.f, "tau must lie in (0, 1], got ", tau);
+  torch::NoGradGuard no_grad;
+  Tensor rays_o = rays_o_in.contiguous(), rays_d = rays_d_in.contiguous();
+  CheckDev(rays_o, torch::kFloat32, "rays_o");
+  CheckDev(rays_d, torch::kFloat32, "rays_d");
+  const int n_rays = rays_o.size(0);
+  const bool fused = FusedPathOk();
+  void* st = CurStream();
+  GeometryResult out;
+  out.opacity = torch::zeros({n_rays}, DevF32());
+  out.normals = torch::zeros({n_rays, 3}, DevF32());
+  out.surf_idx = torch::full({n_rays}, -1, DevI32());
+  out.surf_t = torch::zeros({n_rays}, DevF32());
+  out.surf_points = torch::zeros({n_rays, 3}, DevF32());
+  out.surf_normals = torch::zeros({n_rays, 3}, DevF32());
+  auto no_samples = [&]() {
+    if (!keep_samples) return;
+    out.pts = torch::empty({0, 3}, DevF32());
+    out.anchors = torch::empty({0, 3}, DevI32());
+    out.t = torch::empty({0}, DevF32());
+    out.dt = torch::empty({0}, DevF32());
+    out.sample_grad = torch::empty({0, 3}, DevF32());
+    out.sample_normals = torch::empty({0, 3}, DevF32());
+  };
+  // (field shapes without the fused kernels render op by op, as RenderForward does through Render(): the synchronous count)
+  RenderFront fr = SampleAndFilter(rays_o, rays_d, bounds, Tensor(), /*async_count=*/fused);
+  if (fr.empty) {  // RenderForward's empty result
+    out.render = {fr.bg_color, torch::zeros({n_rays, 1}, DevF32()), torch::zeros({n_rays}, DevF32()), Tensor(),
+                  torch::full({n_rays}, 512.f, DevF32()), Tensor(), Tensor()};
+    no_samples();
+    return out;
+  }
+  SampleResultFlex& es = fr.es;
+  const int n_cap = std::max(fr.n_kept, 1);
+  Tensor colors, disparity, depth, weights;
+  int m = fr.n_kept;
+  Tensor g;  // df0/dw of the survivors [m,3]
+  auto hash_args_grad = [&](const Tensor& p, const Tensor& v, const Tensor& dx) {
+    F2N_CALL(f2n_hash_pos_grad(st, m, field->n_volumes_, VoidP(field->feat_pool_h_), I32P(field->prim_pool_), I32P(field->feat_local_idx_),
+                               I32P(field->feat_local_size_), F32P(field->bias_pool_), F32P(field->level_scale_), F32P(p), I32P(v), 1,
+                               F32P(dx), F32P(g)));
+  };
+  if (fused) {
+    TORCH_CHECK(field->prepass_x_.defined(), "no pre-pass feature cache for this query");
+    Tensor f0c = torch::empty({n_cap}, DevF32()), rgb = torch::empty({n_cap, 3}, DevF32());
+    const at::Half* cache = field->prepass_x_.data_ptr<at::Half>() + (int64_t) N_LEVELS * N_CHANNELS * fr.sample_cache_row;
+    F2N_TIMED_CALL("field_shade_fwd", f2n_field_shade_fwd_dyn(st, fr.n_kept, I32P(fr.n_kept_dev), I32P(fr.src_rows),
+                           static_cast<const void*>(cache), VoidP(field->mlp_->params_h_), F32P(es.dirs), nullptr, nullptr,
+                           VoidP(shader->mlp_->params_h_), F32P(f0c), nullptr, nullptr, F32P(rgb)));
+    colors = torch::empty({n_rays, 3}, DevF32());
+    disparity = torch::empty({n_rays}, DevF32());
+    depth = torch::empty({n_rays}, DevF32());
+    weights = torch::empty({n_cap}, DevF32());
+    Tensor bg = fr.bg_color.contiguous();
+    F2N_TIMED_CALL("composite_fwd", f2n_composite_fwd(st, n_rays, I32P(es.pts_idx_bounds), F32P(f0c), 1, F32P(es.dt), F32P(es.t), F32P(rgb),
+                               F32P(bg), F32P(colors), F32P(disparity), F32P(depth), F32P(weights), nullptr));
+    m = fr.n_kept_dev.item<int>();  // the read-back RenderForward avoids: everything above has been queued by now
+    TORCH_CHECK(m >= 0 && m <= fr.n_kept, "survivor count out of range");
+    g = torch::zeros({std::max(m, 1), 3}, DevF32());
+    if (m > 0) {
+      const int64_t row = (int64_t) N_LEVELS * N_CHANNELS;
+      Tensor cache_rows = field->prepass_x_.view({-1, row}).narrow(0, fr.sample_cache_row, field->prepass_x_.numel() / row - fr.sample_cache_row);
+      Tensor x = cache_rows.index_select(0, fr.src_rows.narrow(0, 0, m).to(torch::kInt64)).contiguous();
+      Tensor p = es.pts.narrow(0, 0, m).contiguous(), v = es.anchors.narrow(0, 0, m).select(1, 0).contiguous();
+      F2N_TIMED_CALL("field_density_grad", f2n_field_density_grad(st, m, field->n_volumes_, VoidP(field->feat_pool_h_), I32P(field->prim_pool_),
+                                      I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
+                                      F32P(field->level_scale_), F32P(p), I32P(v), 1, VoidP(field->mlp_->params_h_), VoidP(x), nullptr,
+                                      F32P(g)));
+    }
+    field->prepass_x_ = Tensor();  // (as RenderForward: the cache served its render)
+  } else {  // op by op, the launches of Render() in VALIDATE mode
+    Tensor feat = field->AnchoredQueryReuse(fr.pts_all, fr.vol_all, fr.src_rows, m).slice(0, 0, m);
+    Tensor rgb = shader->QueryFromField(feat, es.dirs, torch::empty({0}, DevF32()), fr.sample_emb_idx, nullptr).contiguous();
+    feat = feat.contiguous();
+    colors = torch::empty({n_rays, 3}, DevF32());
+    disparity = torch::empty({n_rays}, DevF32());
+    depth = torch::empty({n_rays}, DevF32());
+    weights = torch::empty({n_cap}, DevF32());
+    Tensor bg = fr.bg_color.contiguous();
+    F2N_TIMED_CALL("composite_fwd", f2n_composite_fwd(st, n_rays, I32P(es.pts_idx_bounds), F32P(feat), F2N_MLP_OUT_PAD, F32P(es.dt), F32P(es.t),
+                               F32P(rgb), F32P(bg), F32P(colors), F32P(disparity), F32P(depth), F32P(weights), nullptr));
+    g = torch::zeros({std::max(m, 1), 3}, DevF32());
+    if (m > 0) {  // df0/dx from the general MLP backward (its h16 roundings), dy = e_0, no loss scale: as DensityGradChunk
+      auto& mlp = *field->mlp_;
+      Tensor p = es.pts.narrow(0, 0, m).contiguous(), v = es.anchors.narrow(0, 0, m).select(1, 0).contiguous();
+      Tensor x = field->HashEncode(p, v).to(torch::kFloat32).contiguous();
+      Tensor dy = torch::zeros({m, F2N_MLP_OUT_PAD}, DevF32());
+      dy.select(1, 0).fill_(1.f);
+      Tensor dparams = torch::zeros({mlp.n_params_}, DevF32()), dx = torch::empty({m, mlp.d_in_}, DevF32());
+      F2N_CALL(f2n_mlp_bwd(st, m, mlp.d_in_, mlp.d_hidden_, mlp.n_hidden_layers_, 1.f, VoidP(mlp.params_h_), F32P(x), F32P(dy),
+                           F32P(dparams), F32P(dx)));
+      hash_args_grad(p, v, dx);
+    }
+  }
+  out.render = {colors, es.first_oct_dis, disparity, Tensor(), depth, weights, es.pts_idx_bounds};
+  Tensor dirs = torch::empty_like(rays_d);  // the unit directions the march walked along (the sampler's own normalisation)
+  F2N_CALL(f2n_normalize_dirs(st, n_rays, F32P(rays_d), F32P(dirs)));
+  if (keep_samples) {
+    out.sample_grad = torch::empty({std::max(m, 1), 3}, DevF32());
+    out.sample_normals = torch::empty({std::max(m, 1), 3}, DevF32());
+  }
+  Tensor anchors = es.anchors.contiguous(), tt = es.t.contiguous();
+  F2N_TIMED_CALL("composite_geometry", f2n_composite_geometry(st, n_rays, I32P(es.pts_idx_bounds), F32P(weights), F32P(tt), F32P(rays_o), F32P(dirs),
+                                  I32P(anchors), VoidP(sampler->pers_octree_->pers_trans_gpu_), F32P(g), tau, F32P(out.opacity),
+                                  F32P(out.normals), I32P(out.surf_idx), F32P(out.surf_t), F32P(out.surf_points), F32P(out.surf_normals),
+                                  keep_samples ? F32P(out.sample_grad) : nullptr, keep_samples ? F32P(out.sample_normals) : nullptr));
+  if (keep_samples) {
+    out.render.weights = weights.narrow(0, 0, m);
+    out.pts = es.pts.narrow(0, 0, m);
+    out.anchors = es.anchors.narrow(0, 0, m);
+    out.t = es.t.narrow(0, 0, m);
+    out.dt = es.dt.narrow(0, 0, m);
+    out.sample_grad = out.sample_grad.narrow(0, 0, m);
+    out.sample_normals = out.sample_normals.narrow(0, 0, m);
+  }
+  return out;
+}
+
 GridSpec Renderer::MakeGridSpec(const std::vector<float>& lo, const std::vector<float>& hi, int res) {
   TORCH_CHECK(lo.size() == 3 && hi.size() == 3, "lo / hi must have three coordinates");
   TORCH_CHECK(res >= 1 && res <= 1024, "resolution must be in [1, 1024]");

@@ -357,6 +357,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return r.renderer_->FieldNormals(world);
            },
            py::arg("world"))
+      .def("render_geometry",  // render_rays plus geometry buffers (f2n_composite_geometry): a dict, see README "world-space queries"
+           [](ExpRunner& r, const Tensor& ro, const Tensor& rd, const Tensor& b, float tau, bool return_samples) {
+             GeometryResult g;
+             {
+               py::gil_scoped_release no_gil;
+               g = r.RenderGeometry(ro, rd, b, tau, return_samples);
+             }
+             py::dict d;
+             d["colors"] = g.render.colors; d["disparity"] = g.render.disparity; d["depth"] = g.render.depth;
+             d["opacity"] = g.opacity; d["normals"] = g.normals;
+             d["surf_idx"] = g.surf_idx; d["surf_t"] = g.surf_t; d["surf_points"] = g.surf_points; d["surf_normals"] = g.surf_normals;
+             if (return_samples) {
+               const bool none = !g.render.weights.defined();  // (no ray met the scene)
+               d["pts"] = g.pts; d["anchors"] = g.anchors; d["t"] = g.t; d["dt"] = g.dt;
+               d["weights"] = none ? torch::empty({0}, DevF32()) : g.render.weights;
+               d["idx_start_end"] = none ? torch::zeros({g.opacity.size(0), 2}, DevI32()) : g.render.idx_start_end;
+               d["sample_grad"] = g.sample_grad; d["sample_normals"] = g.sample_normals;
+             }
+             return d;
+           },
+           py::arg("rays_o"), py::arg("rays_d"), py::arg("bounds"), py::arg("tau") = 0.5f, py::arg("return_samples") = false)
       .def_property("density_slab_points",  // points per z-slab of density_grid (bounds its workspaces)
                     [](ExpRunner& r) { return r.renderer_->density_slab_points_; },
                     [](ExpRunner& r, int64_t n) { r.renderer_->density_slab_points_ = std::max<int64_t>(1, n); })

@@ -277,19 +277,7 @@ int f2n_oct_subdivide(void* stream, int n_nodes, const void* nodes, const int32_
 
 namespace {
 
-// Single roundings that the compiler may not contract into an FMA.  (The CPU emulation of tests/wave_emul/ has no __f*_rn
-// intrinsics; it compiles with -ffp-contract=off like the product, so the plain operators are the same operations there.)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define F2N_ADD_RN(a, b) __fadd_rn(a, b)
-#define F2N_SUB_RN(a, b) __fsub_rn(a, b)
-#define F2N_MUL_RN(a, b) __fmul_rn(a, b)
-#define F2N_DIV_RN(a, b) __fdiv_rn(a, b)
-#else
-#define F2N_ADD_RN(a, b) ((a) + (b))
-#define F2N_SUB_RN(a, b) ((a) - (b))
-#define F2N_MUL_RN(a, b) ((a) * (b))
-#define F2N_DIV_RN(a, b) ((a) / (b))
-#endif
+// (F2N_ADD_RN / _SUB_RN / _MUL_RN / _DIV_RN: single roundings that the compiler may not contract into an FMA, f2n_dev.h)
 
 // The grid point of index (ix, iy, iz): lo + step * i with two roundings, never contracted into an FMA, so that float32 numpy
 // (lo + np.float32(step) * np.float32(i)) restates it bit for bit.
@@ -671,19 +659,19 @@ __global__ void __launch_bounds__(256) density_grad_scatter_kernel(int n, const 
     sigma = expf(f0[k] - F2N_DENSITY_SHIFT);
     const float p[3] = {pts_world[i * 3], pts_world[i * 3 + 1], pts_world[i * 3 + 2]};
     const float g[3] = {df0_dw[k * 3], df0_dw[k * 3 + 1], df0_dw[k * 3 + 2]};
-    float jac[3][3];
-    f2n_warp_jac(transes + t, p, jac);
+    float jg[3];
+    f2n_warp_jac_t_mul(transes + t, p, g, jg);  // (shared with composite_geometry_kernel, render.hip)
 #pragma unroll
-    for (int c = 0; c < 3; c++) gr[c] = sigma * f2n_sum3(jac[0][c] * g[0], jac[1][c] * g[1], jac[2][c] * g[2]);
+    for (int c = 0; c < 3; c++) gr[c] = sigma * jg[c];
   }
   density[i] = sigma;
 #pragma unroll
   for (int c = 0; c < 3; c++) grad[i * 3 + c] = gr[c];
   if (normal != nullptr) {
-    const float len = sqrtf(F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(gr[0], gr[0]), F2N_MUL_RN(gr[1], gr[1])), F2N_MUL_RN(gr[2], gr[2])));
-    const bool ok = len > 0.f && len < __builtin_huge_valf();  // (false for NaN as well)
+    float nr[3];
+    f2n_unit3<true>(gr, nr);
 #pragma unroll
-    for (int c = 0; c < 3; c++) normal[i * 3 + c] = ok ? -F2N_DIV_RN(gr[c], len) : 0.f;
+    for (int c = 0; c < 3; c++) normal[i * 3 + c] = nr[c];
   }
 }
 

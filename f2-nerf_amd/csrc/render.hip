@@ -649,6 +649,117 @@ __global__ __launch_bounds__(256) void weight_var_bwd_kernel(int n_rays, const f
   }
 }
 
+// Geometry buffers of rendered rays (no reference counterpart): per sample the world-space direction of the density gradient,
+// g = J^T df0/dw with J = f2n_warp_jac of the sample's leaf at x = o + t d (the point the march warped), and n = -g / |g| -- the
+// expressions of density_grad_scatter_kernel (f2n_warp_jac_t_mul / f2n_unit3, f2n_dev.h), so the two agree bit for bit; per ray
+// opacity = sum w, N = sum w n (normalised behind the walk) and the first sample whose inclusive running sum of w reaches tau.
+// The walk of composite_fwd_kernel: 16 lanes take 16 consecutive samples, the four sums are row chains that add left to right, one
+// term after the other, and the next chunk's loads are in flight while this chunk's Jacobians run.  A lane reads its leaf's
+// transform (132 floats) through its own pointer: the lanes of a chunk mostly sit in one leaf, so the reads are same-address
+// broadcasts out of L1 / L2.  Every lane remembers the first sample at which ITS inclusive sum reached tau; one row minimum
+// behind the walk picks the ray's.  No atomics, no LDS: the outputs are a function of the inputs alone.
+__global__ __launch_bounds__(256) void composite_geometry_kernel(
+    int n_rays, const int32_t* __restrict__ se, const float* __restrict__ weights, const float* __restrict__ t,
+    const float* __restrict__ rays_o, const float* __restrict__ rays_d, const int32_t* __restrict__ anchors,
+    const F2nTransInfo* __restrict__ transes, const float* __restrict__ df0_dw, float tau, float* __restrict__ opacity,
+    float* __restrict__ normal, int32_t* __restrict__ surf_idx, float* __restrict__ surf_t, float* __restrict__ surf_point,
+    float* __restrict__ surf_normal, float* __restrict__ sample_grad, float* __restrict__ sample_normal) {
+  const int c = threadIdx.x & 15;
+  const int ray = blockIdx.x * F2N_ROW_RAYS_PER_BLOCK + (threadIdx.x >> 4);
+  if (ray >= n_rays) return;
+  const int s = se[2 * ray], e = se[2 * ray + 1];
+  const float o[3] = {rays_o[3 * ray], rays_o[3 * ray + 1], rays_o[3 * ray + 2]};
+  const float d[3] = {rays_d[3 * ray], rays_d[3 * ray + 1], rays_d[3 * ray + 2]};
+  const int kNone = 0x7fffffff;
+  float op = 0.f, N[3] = {0.f, 0.f, 0.f};
+  int first = kNone;  // the first sample of this lane's whose inclusive sum reached tau, and what is written for it
+  float f_t = 0.f, f_x[3] = {0.f, 0.f, 0.f}, f_n[3] = {0.f, 0.f, 0.f};
+  struct In {
+    float w, t, g0, g1, g2;
+    int a;
+  };
+  auto fetch = [&](int i) {
+    In r;
+    r.w = weights[i];
+    r.t = t[i];
+    r.a = anchors[3 * (size_t) i];
+    r.g0 = df0_dw[3 * (size_t) i];
+    r.g1 = df0_dw[3 * (size_t) i + 1];
+    r.g2 = df0_dw[3 * (size_t) i + 2];
+    return r;
+  };
+  In nxt = {0.f, 0.f, 0.f, 0.f, 0.f, 0};
+  if (s < e) nxt = fetch(min(s + c, e - 1));
+  for (int base = s; base < e; base += 16) {
+    const int i = base + c;
+    const bool in = i < e;
+    const In cur = nxt;
+    if (base + 16 < e) nxt = fetch(min(i + 16, e - 1));
+    float w = 0.f, x[3] = {0.f, 0.f, 0.f}, nr[3] = {0.f, 0.f, 0.f};
+    if (in) {
+      w = cur.w;
+#pragma unroll
+      for (int k = 0; k < 3; k++) x[k] = o[k] + d[k] * cur.t;  // (sampler.hip: xyz = o + d * cur_t)
+      float g[3] = {0.f, 0.f, 0.f};
+      if (cur.a >= 0) {  // (a survivor always has a leaf; a negative index reads no transform and gives the zero normal)
+        const float gw[3] = {cur.g0, cur.g1, cur.g2};
+        f2n_warp_jac_t_mul(transes + cur.a, x, gw, g);
+      }
+      f2n_unit3<true>(g, nr);
+      if (sample_grad != nullptr) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) sample_grad[3 * (size_t) i + k] = g[k];
+      }
+      if (sample_normal != nullptr) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) sample_normal[3 * (size_t) i + k] = nr[k];
+      }
+    }
+    // lanes past the end add exact zeros to the running sums
+    f2n_row_chain4(w, w * nr[0], w * nr[1], w * nr[2], op, N[0], N[1], N[2]);
+    if (in && first == kNone && op >= tau) {
+      first = i;
+      f_t = cur.t;
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        f_x[k] = x[k];
+        f_n[k] = nr[k];
+      }
+    }
+  }
+  int hit = first;
+#pragma unroll
+  for (int off = 8; off >= 1; off >>= 1) hit = min(hit, __shfl_xor(hit, off, 16));
+  op = f2n_row_last(op);
+#pragma unroll
+  for (int k = 0; k < 3; k++) N[k] = f2n_row_last(N[k]);
+  if (c == 0) {
+    float un[3];
+    f2n_unit3<false>(N, un);
+    opacity[ray] = op;
+#pragma unroll
+    for (int k = 0; k < 3; k++) normal[3 * ray + k] = un[k];
+    if (hit == kNone) {
+      surf_idx[ray] = -1;
+      surf_t[ray] = 0.f;
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        surf_point[3 * ray + k] = 0.f;
+        surf_normal[3 * ray + k] = 0.f;
+      }
+    }
+  }
+  if (hit != kNone && first == hit) {  // (sample indices are distinct across the lanes: exactly one lane)
+    surf_idx[ray] = hit;
+    surf_t[ray] = f_t;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      surf_point[3 * ray + k] = f_x[k];
+      surf_normal[3 * ray + k] = f_n[k];
+    }
+  }
+}
+
 // FlexOps.cu:5-93
 __global__ void flex_sum_fwd_kernel(int n, int vec, const float* __restrict__ val, const int32_t* __restrict__ se,
                                     float* __restrict__ sum) {
@@ -811,6 +922,19 @@ int f2n_weight_var_fwd(void* stream, int n_rays, const float* weights, const int
 int f2n_weight_var_bwd(void* stream, int n_rays, const float* weights, const int32_t* pts_start_end, const float* dvars,
                        float* dweights) {
   F2N_ROW_LAUNCH(weight_var_bwd_kernel, n_rays, weights, pts_start_end, dvars, dweights);
+}
+
+int f2n_composite_geometry(void* stream, int n_rays, const int32_t* pts_start_end, const float* weights, const float* t, const float* rays_o,
+                           const float* rays_d, const int32_t* anchors, const void* transes, const float* df0_dw, float tau,
+                           float* out_opacity, float* out_normal, int32_t* out_surf_idx, float* out_surf_t, float* out_surf_point,
+                           float* out_surf_normal, float* out_sample_grad, float* out_sample_normal) {
+  if (!(tau > 0.f && tau <= 1.f)) return F2N_ERR_INVALID_ARG;  // (false for NaN as well)
+  if (n_rays > 0 && (pts_start_end == nullptr || weights == nullptr || t == nullptr || rays_o == nullptr || rays_d == nullptr ||
+                     anchors == nullptr || transes == nullptr || df0_dw == nullptr || out_opacity == nullptr || out_normal == nullptr ||
+                     out_surf_idx == nullptr || out_surf_t == nullptr || out_surf_point == nullptr || out_surf_normal == nullptr))
+    return F2N_ERR_INVALID_ARG;
+  F2N_ROW_LAUNCH(composite_geometry_kernel, n_rays, pts_start_end, weights, t, rays_o, rays_d, anchors, (const F2nTransInfo*) transes, df0_dw,
+                 tau, out_opacity, out_normal, out_surf_idx, out_surf_t, out_surf_point, out_surf_normal, out_sample_grad, out_sample_normal);
 }
 
 int f2n_flex_sum_fwd(void* stream, int n_rays, int vec, const float* val, const int32_t* start_end, float* sum) {

@@ -16,6 +16,15 @@ Options (hydra-style overrides, no `mesh` group in the configs):
   mesh.colors      true: per-vertex colours (uchar red, green, blue; default false): the radiance AT the vertex seen along the
                    inward normal -- a single-point query, not a volume-rendered pixel
   mesh.min_component_faces  N > 1: connected components of fewer than N faces ("floaters") are dropped (default 0: none)
+
+Point-cloud export: `mode=extract_points is_continue=true` renders every training camera with runner.render_geometry and writes the
+rays' surface points, oriented and coloured, to <exp>/points/<iter>.ply in the data set's world frame (the usual input of a Poisson
+reconstruction, and the cheapest check on a mesh export).  Options:
+  points.res_level   the cameras are rendered at 1/res_level of their resolution (default 4)
+  points.tau         the surface of a ray is its first sample at which the accumulated weight reaches tau (default 0.5)
+  points.min_opacity rays whose opacity (the sum of their weights) is below this are dropped (default 0.5)
+  points.normals     surface | composited (default surface): the field's normal at the surface sample, or the weight-composited one
+  points.max_points  at most this many points are kept (default 2 000 000), by a fixed stride over the kept rays: no random draw
 """
 import os
 
@@ -45,6 +54,27 @@ def _normal_source(v):
     if s not in NORMAL_SOURCES:
         raise ValueError("mesh.normal_source must be one of %s, got %r" % (" | ".join(NORMAL_SOURCES), v))
     return s
+
+
+POINT_NORMALS = ("surface", "composited")
+
+
+def points_options(cfg):
+    p = cfg.get("points") or {}
+    nrm = str(p.get("normals", "surface")).strip().lower()
+    if nrm not in POINT_NORMALS:
+        raise ValueError("points.normals must be one of %s, got %r" % (" | ".join(POINT_NORMALS), p.get("normals")))
+    o = {"res_level": int(p.get("res_level", 4)), "min_opacity": float(p.get("min_opacity", 0.5)), "tau": float(p.get("tau", 0.5)),
+         "normals": nrm, "max_points": int(p.get("max_points", 2000000))}
+    if o["res_level"] < 1 or o["max_points"] < 1 or not 0.0 < o["tau"] <= 1.0:
+        raise ValueError("points.res_level and points.max_points must be >= 1 and points.tau in (0, 1], got %r" % (o,))
+    return o
+
+
+def stride_subset(n, cap):
+    """Indices of at most `cap` of n items: every k-th with the smallest k that fits (all of them when n <= cap)."""
+    k = max(1, -(-int(n) // int(cap)))
+    return np.arange(0, int(n), k)
 
 
 def _flag(v):
@@ -95,6 +125,71 @@ def write_ply(path, verts, faces, normals=None, colors=None):
         fh.write(header.encode("ascii"))
         fh.write(v.tobytes())
         fh.write(rec.tobytes())
+    return path
+
+
+def write_points_ply(path, points, normals=None, colors=None):
+    """Binary little-endian PLY of a point cloud: the vertex element of write_ply (float x, y, z, then float nx, ny, nz and / or uchar
+    red, green, blue when given) and no face element."""
+    v = np.ascontiguousarray(points, dtype="<f4").reshape(-1, 3)
+    props = "property float x\nproperty float y\nproperty float z\n"
+    fields = [("xyz", "<f4", (3,))]
+    for name, arr in (("normals", normals), ("colors", colors)):
+        if arr is not None and np.asarray(arr).reshape(-1, 3).shape[0] != len(v):
+            raise ValueError("%s: %d rows for %d points" % (name, np.asarray(arr).reshape(-1, 3).shape[0], len(v)))
+    if normals is not None:
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+        fields.append(("n", "<f4", (3,)))
+    if colors is not None:
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        fields.append(("rgb", "u1", (3,)))
+    rec = np.empty(len(v), dtype=fields)
+    rec["xyz"] = v
+    if normals is not None:
+        rec["n"] = np.asarray(normals, "<f4").reshape(len(v), 3)
+    if colors is not None:
+        rec["rgb"] = quantize_colors(colors).reshape(len(v), 3)
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(v) + props + "end_header\n").encode("ascii"))
+        fh.write(rec.tobytes())
+    return path
+
+
+def camera_rays(dataset, bounds, idx, res_level):
+    """Rays of camera idx at 1 / res_level of its resolution (the pixel grid of Dataset::RaysFromPose), with that camera's bounds."""
+    import torch
+    H, W = max(1, int(dataset.height) // res_level), max(1, int(dataset.width) // res_level)
+    ii = torch.linspace(0.0, dataset.height - 1.0, H, device="cuda").to(torch.int32)
+    jj = torch.linspace(0.0, dataset.width - 1.0, W, device="cuda").to(torch.int32)
+    gi, gj = torch.meshgrid(ii, jj, indexing="ij")
+    ij = torch.stack([gi.reshape(-1), gj.reshape(-1)], -1).contiguous()
+    ro, rd = dataset.img2world_ray_flex(torch.full((H * W,), int(idx), dtype=torch.int32, device="cuda"), ij)
+    b = torch.as_tensor(np.asarray(bounds, np.float32)[idx], device="cuda").reshape(1, 2).repeat(H * W, 1).contiguous()
+    return ro, rd, b
+
+
+def extract_points(runner, cfg, scene, dataset, exp_dir):
+    """Every training camera -> runner.render_geometry -> the rays that found a surface -> <exp_dir>/points/<iter>.ply."""
+    o = points_options(cfg)
+    pts, nrm, col = [], [], []
+    for idx in scene["train_set"]:
+        ro, rd, b = camera_rays(dataset, scene["bounds"], int(idx), o["res_level"])
+        g = runner.render_geometry(ro, rd, b, tau=o["tau"])
+        keep = (g["surf_idx"] >= 0) & (g["opacity"] >= o["min_opacity"])
+        pts.append(g["surf_points"][keep].cpu().numpy())
+        nrm.append(g["surf_normals" if o["normals"] == "surface" else "normals"][keep].cpu().numpy())
+        col.append(g["colors"][keep].cpu().numpy())
+    pts, nrm, col = (np.concatenate(a).reshape(-1, 3) if a else np.zeros((0, 3), np.float32) for a in (pts, nrm, col))
+    n_kept = len(pts)
+    sel = stride_subset(n_kept, o["max_points"])
+    path = os.path.join(exp_dir, "points", "%d.ply" % runner.iter_step)
+    # (the world frame is a uniform scale and a shift of the normalised one: normals are the same in both)
+    write_points_ply(path, to_world(pts[sel], scene["center"], scene["radius"]), nrm[sel], col[sel])
+    print("Points: %d of %d rays with a surface from %d cameras (tau %g, opacity >= %g) -> %s" % (
+        len(sel), n_kept, len(scene["train_set"]), o["tau"], o["min_opacity"], path))
     return path
 
 

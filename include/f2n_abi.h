@@ -926,6 +926,23 @@ int f2n_density_grad_scatter(void* stream, int n, const float* pts_world /*[n,3]
                              const int32_t* start_end /*[n,2]*/, const void* transes, const float* f0, const float* df0_dw /*[m,3]*/,
                              float* out_density /*[n]*/, float* out_grad /*[n,3]*/, float* out_normal /*[n,3] or NULL*/);
 
+/* Geometry buffers of rendered rays, from the weights f2n_composite_fwd wrote.  Per sample i of ray r (s = pts_start_end[r,0] <= i <
+ * e = pts_start_end[r,1]): x_i = rays_o[r] + t[i] * rays_d[r] (the point the march warped, the same two roundings),
+ * g_i = J^T df0_dw[i] with J = f2n_warp_jac of transes[anchors[i,0]] at x_i, n_i = -g_i / |g_i| -- the expressions of
+ * f2n_density_grad_scatter, bit for bit; (0, 0, 0) where |g_i| is 0 or not finite (or anchors[i,0] < 0).  Per ray, every sum fp32, left
+ * to right, one term after the other:
+ *   out_opacity[r] = sum w_i;  out_normal[r] = N / |N| with N = sum w_i n_i componentwise, (0, 0, 0) where |N| is 0 or not finite;
+ *   out_surf_idx[r] = the first (global) sample index i whose inclusive running sum of w reaches tau (>= tau), with
+ *   out_surf_t = t[i], out_surf_point = x_i, out_surf_normal = n_i; if there is none (or the ray has no sample): -1 and zeros.
+ * out_sample_grad / out_sample_normal [M,3] (each may be NULL) receive g_i / n_i.  tau must lie in (0, 1].  No atomics: the outputs
+ * are a function of the inputs alone.  No reference counterpart. */
+int f2n_composite_geometry(void* stream, int n_rays, const int32_t* pts_start_end /*[R,2]*/, const float* weights /*[M], f2n_composite_fwd's*/,
+                           const float* t /*[M]*/, const float* rays_o /*[R,3]*/, const float* rays_d /*[R,3]*/,
+                           const int32_t* anchors /*[M,3]*/, const void* transes, const float* df0_dw /*[M,3]*/, float tau,
+                           float* out_opacity /*[R]*/, float* out_normal /*[R,3]*/, int32_t* out_surf_idx /*[R]*/, float* out_surf_t /*[R]*/,
+                           float* out_surf_point /*[R,3]*/, float* out_surf_normal /*[R,3]*/, float* out_sample_grad /*[M,3] or NULL*/,
+                           float* out_sample_normal /*[M,3] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
