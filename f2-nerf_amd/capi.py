@@ -868,3 +868,54 @@ def mesh_filter_components(verts, faces, min_faces):
                                        _p(vse, "i32"), _p(fkeep, "i32", nf == 0), _p(fse, "i32", nf == 0), _p(ov, "f32", kv == 0),
                                        _p(src, "i32", kv == 0), _p(of, "i32", kf == 0)), "f2n_mesh_filter_emit")
     return ov, of, src
+
+
+# ---------------------------------------------------------------- TSDF fusion of depth maps
+def tsdf_integrate(S, W, lo, step, poses, intri, dist_params, depth, conf, trunc):
+    """Adds the depth maps depth [V,h,w] (conf [V,h,w] or None: weight 1) seen from poses [V,3,4] / intri [V,3,3] / dist_params [V,4] into
+    the running sums S, W [nz, ny, nx] of the grid lo + step * (ix, iy, iz), in place (f2n_tsdf_integrate)."""
+    nz, ny, nx = (int(v) for v in S.shape)
+    if tuple(W.shape) != tuple(S.shape):
+        raise F2nError("S and W must have the same shape")
+    V, h, w = (int(v) for v in depth.shape)
+    if poses.numel() != 12 * V or intri.numel() != 9 * V or dist_params.numel() != 4 * V or (conf is not None and conf.shape != depth.shape):
+        raise F2nError("poses [V,3,4], intri [V,3,3], dist_params [V,4] and conf must match depth [V,h,w]")
+    none = V == 0 or nx * ny * nz == 0
+    _ck(lib().f2n_tsdf_integrate(_stream(), _lo3(lo), _f(step), _i(nx), _i(ny), _i(nz), _i(V), _p(poses, "f32", none), _p(intri, "f32", none),
+                                 _p(dist_params, "f32", none), _p(depth, "f32", none), _p(conf, "f32", True), _i(h), _i(w), _f(trunc),
+                                 _p(S, "f32", none), _p(W, "f32", none)), "f2n_tsdf_integrate")
+
+
+def tsdf_finalize(S, W, min_weight):
+    """(g, valid uint8) of the running sums: valid = (W >= min_weight and W > 0), g = -S / W (positive inside), 0 where not valid."""
+    if tuple(W.shape) != tuple(S.shape):
+        raise F2nError("S and W must have the same shape")
+    n = S.numel()
+    g = torch.empty_like(S)
+    valid = torch.empty(S.shape, dtype=torch.uint8, device=S.device)
+    _ck(lib().f2n_tsdf_finalize(_stream(), ctypes.c_int64(n), _p(S, "f32", n == 0), _p(W, "f32", n == 0), _f(min_weight), _p(g, "f32", n == 0),
+                                _p(valid, "u8", n == 0)), "f2n_tsdf_finalize")
+    return g, valid
+
+
+def mesh_from_grid_masked(grid, valid, lo=(0.0, 0.0, 0.0), step=1.0, level=0.0):
+    """mesh_from_grid over the grid points that carry a value (valid [nz, ny, nx] uint8; f2n_mesh_count_masked -> f2n_mesh_emit): faces
+    only from cells whose eight corners are valid, vertices only where a face uses them."""
+    nz, ny, nx = (int(v) for v in grid.shape)
+    if tuple(valid.shape) != tuple(grid.shape):
+        raise F2nError("valid must have the shape of the grid")
+    dev = grid.device
+    n, c = nx * ny * nz, (nx - 1) * (ny - 1) * (nz - 1)
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    vc, vse = torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 2), dtype=torch.int32, device=dev)
+    fc, fse = torch.empty(c, dtype=torch.int32, device=dev), torch.empty((c, 2), dtype=torch.int32, device=dev)
+    totals = torch.empty(2, dtype=torch.int32, device=dev)
+    _ck(lib().f2n_mesh_count_masked(_stream(), _i(nx), _i(ny), _i(nz), _p(grid, "f32"), _f(level), _p(valid, "u8"), _p(mask, "u8"),
+                                    _p(vc, "i32"), _p(vse, "i32"), _p(fc, "i32"), _p(fse, "i32"), _p(totals, "i32")), "f2n_mesh_count_masked")
+    nv, nf = (int(v) for v in totals.cpu())
+    verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    if nv or nf:
+        _ck(lib().f2n_mesh_emit(_stream(), _i(nx), _i(ny), _i(nz), _p(grid, "f32"), _f(level), _lo3(lo), _f(step), _p(mask, "u8"),
+                                _p(vse, "i32"), _p(fse, "i32"), _p(verts, "f32"), _p(faces, "i32")), "f2n_mesh_emit")
+    return verts, faces

@@ -136,7 +136,74 @@ __global__ void draw_ray_batch_kernel(int n_rays, const float* __restrict__ u01,
   bounds[2 * (size_t) r + 1] = cam_bounds[2 * (size_t) c + 1];
 }
 
+// TSDF fusion of depth maps (include/f2n_abi.h, f2n_tsdf_integrate): the inverse of img2world_kernel's camera model -- a grid point is
+// taken into every view's camera frame, distorted (f2n_distort, no Newton: the forward direction of the model) and looked up in that
+// view's depth map at the nearest pixel.  One thread owns one voxel and walks the views in index order with its two running sums in
+// registers: no atomics, the state is read once and written once, and the sums of a launch over [0, V) are those of launches over
+// [0, k) and [k, V).  A view's 20 constants (pose, fx, fy, cx, cy, distortion) are addressed by the loop variable alone: wave-uniform,
+// fetched by scalar loads into SGPRs, so that the vector registers hold the voxel's own state only.
+__global__ void __launch_bounds__(256) tsdf_integrate_kernel(int64_t n, int nx, int ny, float lo0, float lo1, float lo2, float step, int n_views,
+                                                            const float* __restrict__ poses, const float* __restrict__ intri,
+                                                            const float* __restrict__ dist, const float* __restrict__ depth,
+                                                            const float* __restrict__ conf, int h, int w, float trunc,
+                                                            float* __restrict__ S, float* __restrict__ W) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t plane = (int64_t) nx * ny;
+  const int64_t r = i % plane;
+  const float p[3] = {f2n_grid_coord(lo0, step, (int) (r % nx)), f2n_grid_coord(lo1, step, (int) (r / nx)),
+                      f2n_grid_coord(lo2, step, (int) (i / plane))};
+  float s_sum = S[i], w_sum = W[i];
+  const float fh = (float) h, fw = (float) w;
+  for (int v = 0; v < n_views; v++) {
+    const float* P = poses + 12 * (size_t) v;
+    const float* K = intri + 9 * (size_t) v;
+    const float q[3] = {F2N_SUB_RN(p[0], P[3]), F2N_SUB_RN(p[1], P[7]), F2N_SUB_RN(p[2], P[11])};
+    float c[3];  // R^T q: the point in the camera frame (x right, y up, z backwards: OpenGL style)
+#pragma unroll
+    for (int a = 0; a < 3; a++) c[a] = f2n_sum3(F2N_MUL_RN(P[a], q[0]), F2N_MUL_RN(P[4 + a], q[1]), F2N_MUL_RN(P[8 + a], q[2]));
+    const float s = -c[2];
+    if (!(s > 0.f)) continue;  // behind the camera (NaN as well)
+    const float un = F2N_DIV_RN(c[0], s), vn = F2N_DIV_RN(-c[1], s);
+    float du, dv;
+    f2n_distort(dist + 4 * (size_t) v, un, vn, du, dv);
+    const float x = F2N_ADD_RN(F2N_MUL_RN(K[0], F2N_ADD_RN(un, du)), K[2]);
+    const float y = F2N_ADD_RN(F2N_MUL_RN(K[4], F2N_ADD_RN(vn, dv)), K[5]);
+    const float fb = floorf(x), fa = floorf(y);
+    if (!(fa >= 0.f && fa < fh && fb >= 0.f && fb < fw)) continue;  // outside the image (NaN as well)
+    const size_t px = ((size_t) v * h + (int) fa) * w + (int) fb;
+    const float D = depth[px];
+    if (!(D > 0.f)) continue;  // no surface along this pixel's ray
+    const float wgt = conf != nullptr ? conf[px] : 1.f;
+    if (!(wgt > 0.f)) continue;
+    const float sdf = F2N_SUB_RN(D, f2n_norm3(q[0], q[1], q[2]));
+    if (sdf < -trunc) continue;  // further than trunc behind the surface: not observed
+    const float ratio = F2N_DIV_RN(sdf, trunc);
+    const float d = ratio < 1.f ? ratio : 1.f;
+    s_sum = F2N_ADD_RN(s_sum, F2N_MUL_RN(wgt, d));
+    w_sum = F2N_ADD_RN(w_sum, wgt);
+  }
+  S[i] = s_sum;
+  W[i] = w_sum;
+}
+
 extern "C" {
+
+int f2n_tsdf_integrate(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int n_views, const float* poses,
+                       const float* intri, const float* dist_params, const float* depth, const float* conf, int h, int w, float trunc,
+                       float* S, float* W) {
+  if (lo == nullptr || nx < 0 || ny < 0 || nz < 0 || n_views < 0 || h < 0 || w < 0 || !(trunc > 0.f) || !(trunc < __builtin_huge_valf()))
+    return F2N_ERR_INVALID_ARG;
+  const int64_t n = (int64_t) nx * ny * nz;
+  if (n_views == 0 || n == 0) return F2N_OK;
+  // (pixel coordinates are compared as floats: exact up to 2^24; a depth map's index is computed in 64 bits)
+  if (h < 1 || w < 1 || h > (1 << 24) || w > (1 << 24) || n > (int64_t) 0x7fffffff * 256) return F2N_ERR_INVALID_ARG;
+  if (poses == nullptr || intri == nullptr || dist_params == nullptr || depth == nullptr || S == nullptr || W == nullptr)
+    return F2N_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, nx, ny, lo[0], lo[1], lo[2],
+                     step, n_views, poses, intri, dist_params, depth, conf, h, w, trunc, S, W);
+  return f2n_launch_status();
+}
 
 int f2n_draw_ray_batch(void* stream, int n_rays, const float* u01, const int32_t* image_set, int n_set, int height, int width,
                        const float* poses, const float* intri, const float* dist_params, const float* images, const float* cam_bounds,

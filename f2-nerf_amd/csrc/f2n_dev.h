@@ -202,6 +202,11 @@ __device__ __forceinline__ void f2n_warp_jac(const F2nTransInfo* __restrict__ tr
 #define F2N_DIV_RN(a, b) ((a) / (b))
 #endif
 
+// The point of index i along one axis of an implicit grid: lo + step * i with two roundings, never contracted into an FMA, so that
+// float32 numpy (lo + np.float32(step) * np.float32(i)) restates it bit for bit.  Shared by the grid kernels of octree.hip and the
+// TSDF integration of dataset.hip, which must name the same points.
+__device__ __forceinline__ float f2n_grid_coord(float lo, float step, int i) { return F2N_ADD_RN(lo, F2N_MUL_RN(step, (float) i)); }
+
 // J^T g: the gradient with respect to the world position p of a function whose gradient with respect to the warped position is g,
 // J = f2n_warp_jac of the leaf's transform at p.  Shared by density_grad_scatter_kernel (octree.hip) and composite_geometry_kernel
 // (render.hip), which must agree bit for bit.

@@ -73,6 +73,14 @@ struct GridSpec {
 };
 // Iso-surface of any float32 grid [nz, ny, nx] (f2n_mesh_count / f2n_mesh_emit): (verts [V,3] f32, faces [F,3] int32)
 std::tuple<Tensor, Tensor> MeshFromGrid(const Tensor& grid, float level, const float lo[3], float step);
+// The same with a uint8 mask [nz, ny, nx] of the grid points that carry a value (f2n_mesh_count_masked): faces only from cells whose
+// eight corners are valid, vertices only where a face uses them
+std::tuple<Tensor, Tensor> MeshFromGridMasked(const Tensor& grid, const Tensor& valid, float level, const float lo[3], float step);
+// TSDF fusion on any grid (f2n_tsdf_integrate / f2n_tsdf_finalize).  TsdfIntegrate adds depth [V,h,w] (conf [V,h,w] or undefined) seen
+// from poses [V,3,4] / intri [V,3,3] / dist [V,4] into the device tensors S, W [nz, ny, nx] IN PLACE; TsdfFinalize: (g, valid uint8).
+void TsdfIntegrate(const Tensor& S, const Tensor& W, const float lo[3], float step, const Tensor& poses, const Tensor& intri,
+                   const Tensor& dist, const Tensor& depth, const Tensor& conf, float trunc);
+std::tuple<Tensor, Tensor> TsdfFinalize(const Tensor& S, const Tensor& W, float min_weight);
 // Unit normals [n,3] at pts [n,3] from the gradient of any float32 grid [nz, ny, nx] (f2n_grid_normals): -grad / |grad|, 0 where flat
 Tensor GridNormals(const Tensor& grid, const Tensor& pts, const float lo[3], float step);
 // labels [V] int32: the smallest vertex index of every vertex's connected component (f2n_mesh_components); *rounds: labelling rounds

@@ -332,18 +332,29 @@ Tensor Renderer::DensityGrid(const std::vector<float>& lo, const std::vector<flo
   return out;
 }
 
-std::tuple<Tensor, Tensor> MeshFromGrid(const Tensor& grid, float level, const float lo[3], float step) {
+namespace {
+// valid: undefined = every corner carries a value (f2n_mesh_count), else the uint8 mask of f2n_mesh_count_masked
+std::tuple<Tensor, Tensor> MeshFromGridImpl(const Tensor& grid, const Tensor& valid, float level, const float lo[3], float step) {
   torch::NoGradGuard g;
   Tensor gr = grid.to(torch::kCUDA, torch::kFloat32).contiguous();
   TORCH_CHECK(gr.dim() == 3, "grid must be [nz, ny, nx]");
   const int nz = (int) gr.size(0), ny = (int) gr.size(1), nx = (int) gr.size(2);
+  Tensor va;
+  if (valid.defined()) {
+    va = valid.to(torch::kCUDA, torch::kUInt8).contiguous();
+    TORCH_CHECK(va.numel() == gr.numel(), "valid must have one entry per grid point");
+  }
   if (nx < 2 || ny < 2 || nz < 2) return {torch::empty({0, 3}, DevF32()), torch::empty({0, 3}, DevI32())};
   const int64_t n_corners = (int64_t) nx * ny * nz, n_cells = (int64_t) (nx - 1) * (ny - 1) * (nz - 1);
   Tensor mask = torch::empty({n_corners}, torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA));
   Tensor vc = torch::empty({n_corners}, DevI32()), vse = torch::empty({n_corners, 2}, DevI32());
   Tensor fc = torch::empty({n_cells}, DevI32()), fse = torch::empty({n_cells, 2}, DevI32()), totals = torch::empty({2}, DevI32());
-  F2N_CALL(f2n_mesh_count(CurStream(), nx, ny, nz, F32P(gr), level, mask.data_ptr<uint8_t>(), I32P(vc), I32P(vse), I32P(fc), I32P(fse),
-                          I32P(totals)));
+  if (va.defined())
+    F2N_CALL(f2n_mesh_count_masked(CurStream(), nx, ny, nz, F32P(gr), level, va.data_ptr<uint8_t>(), mask.data_ptr<uint8_t>(), I32P(vc),
+                                   I32P(vse), I32P(fc), I32P(fse), I32P(totals)));
+  else
+    F2N_CALL(f2n_mesh_count(CurStream(), nx, ny, nz, F32P(gr), level, mask.data_ptr<uint8_t>(), I32P(vc), I32P(vse), I32P(fc), I32P(fse),
+                            I32P(totals)));
   Tensor t = totals.cpu();  // the two totals: the only read-back (they size the outputs)
   const int64_t nv = t.data_ptr<int32_t>()[0], nf = t.data_ptr<int32_t>()[1];
   Tensor verts = torch::empty({nv, 3}, DevF32()), faces = torch::empty({nf, 3}, DevI32());
@@ -351,6 +362,55 @@ std::tuple<Tensor, Tensor> MeshFromGrid(const Tensor& grid, float level, const f
     F2N_CALL(f2n_mesh_emit(CurStream(), nx, ny, nz, F32P(gr), level, lo, step, mask.data_ptr<uint8_t>(), I32P(vse), I32P(fse),
                            F32P(verts), I32P(faces)));
   return {verts, faces};
+}
+}  // namespace
+
+std::tuple<Tensor, Tensor> MeshFromGrid(const Tensor& grid, float level, const float lo[3], float step) {
+  return MeshFromGridImpl(grid, Tensor(), level, lo, step);
+}
+
+std::tuple<Tensor, Tensor> MeshFromGridMasked(const Tensor& grid, const Tensor& valid, float level, const float lo[3], float step) {
+  TORCH_CHECK(valid.defined(), "valid is required");
+  return MeshFromGridImpl(grid, valid, level, lo, step);
+}
+
+namespace {
+const Tensor& DevArg(const Tensor& t, torch::ScalarType dt, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt && t.is_contiguous(), name, " must be a contiguous device tensor of its type");
+  return t;
+}
+}  // namespace
+
+void TsdfIntegrate(const Tensor& S, const Tensor& W, const float lo[3], float step, const Tensor& poses, const Tensor& intri,
+                   const Tensor& dist, const Tensor& depth, const Tensor& conf, float trunc) {
+  torch::NoGradGuard g;
+  // (S and W are updated in place: no copy may stand in for them)
+  DevArg(S, torch::kFloat32, "S");
+  DevArg(W, torch::kFloat32, "W");
+  TORCH_CHECK(S.dim() == 3 && W.sizes() == S.sizes(), "S and W must be [nz, ny, nx]");
+  Tensor po = poses.to(torch::kCUDA, torch::kFloat32).contiguous(), in = intri.to(torch::kCUDA, torch::kFloat32).contiguous();
+  Tensor di = dist.to(torch::kCUDA, torch::kFloat32).contiguous(), de = depth.to(torch::kCUDA, torch::kFloat32).contiguous();
+  TORCH_CHECK(de.dim() == 3, "depth must be [V, h, w]");
+  const int64_t V = de.size(0);
+  TORCH_CHECK(V <= INT32_MAX && po.numel() == V * 12 && in.numel() == V * 9 && di.numel() == V * 4,
+              "poses [V,3,4], intri [V,3,3] and dist_params [V,4] must match depth [V,h,w]");
+  Tensor co;
+  if (conf.defined()) {
+    co = conf.to(torch::kCUDA, torch::kFloat32).contiguous();
+    TORCH_CHECK(co.sizes() == de.sizes(), "conf must have the shape of depth");
+  }
+  F2N_CALL(f2n_tsdf_integrate(CurStream(), lo, step, (int) S.size(2), (int) S.size(1), (int) S.size(0), (int) V, F32P(po), F32P(in), F32P(di),
+                              F32P(de), co.defined() ? F32P(co) : nullptr, (int) de.size(1), (int) de.size(2), trunc, F32P(S), F32P(W)));
+}
+
+std::tuple<Tensor, Tensor> TsdfFinalize(const Tensor& S, const Tensor& W, float min_weight) {
+  torch::NoGradGuard g;
+  DevArg(S, torch::kFloat32, "S");
+  DevArg(W, torch::kFloat32, "W");
+  TORCH_CHECK(W.sizes() == S.sizes(), "S and W must have the same shape");
+  Tensor out = torch::empty_like(S), valid = torch::empty(S.sizes(), torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA));
+  F2N_CALL(f2n_tsdf_finalize(CurStream(), S.numel(), F32P(S), F32P(W), min_weight, F32P(out), valid.data_ptr<uint8_t>()));
+  return {out, valid};
 }
 
 std::tuple<Tensor, Tensor> Renderer::ExtractMesh(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level) {

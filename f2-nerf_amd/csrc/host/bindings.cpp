@@ -112,6 +112,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
         },
         py::arg("grid"), py::arg("level"), py::arg("lo") = std::vector<float>{0.f, 0.f, 0.f}, py::arg("step") = 1.f);
+  // the same with a uint8 mask [nz, ny, nx] of the grid points that carry a value (f2n_mesh_count_masked / f2n_mesh_emit)
+  m.def("mesh_from_grid_masked",
+        [](const Tensor& grid, const Tensor& valid, const std::vector<float>& lo, float step, float level) {
+          TORCH_CHECK(lo.size() == 3, "lo must have three coordinates");
+          auto t = MeshFromGridMasked(grid, valid, level, lo.data(), step);
+          return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
+        },
+        py::arg("grid"), py::arg("valid"), py::arg("lo") = std::vector<float>{0.f, 0.f, 0.f}, py::arg("step") = 1.f, py::arg("level") = 0.f);
+  // TSDF fusion on any grid: depth maps [V,h,w] (conf [V,h,w] or None) into the running sums S, W [nz, ny, nx], in place
+  // (f2n_tsdf_integrate); then (g, valid) of the sums (f2n_tsdf_finalize)
+  m.def("tsdf_integrate",
+        [](const Tensor& S, const Tensor& W, const std::vector<float>& lo, float step, const Tensor& poses, const Tensor& intri,
+           const Tensor& dist, const Tensor& depth, const c10::optional<Tensor>& conf, float trunc) {
+          TORCH_CHECK(lo.size() == 3, "lo must have three coordinates");
+          TsdfIntegrate(S, W, lo.data(), step, poses, intri, dist, depth, conf.has_value() ? *conf : Tensor(), trunc);
+        },
+        py::arg("S"), py::arg("W"), py::arg("lo"), py::arg("step"), py::arg("poses"), py::arg("intri"), py::arg("dist"), py::arg("depth"),
+        py::arg("conf"), py::arg("trunc"));
+  m.def("tsdf_finalize",
+        [](const Tensor& S, const Tensor& W, float min_weight) {
+          auto t = TsdfFinalize(S, W, min_weight);
+          return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
+        },
+        py::arg("S"), py::arg("W"), py::arg("min_weight"));
   // unit normals [n,3] at pts [n,3] from the gradient of any float32 grid [nz, ny, nx] (f2n_grid_normals)
   m.def("grid_normals",
         [](const Tensor& grid, const Tensor& pts, const std::vector<float>& lo, float step) {

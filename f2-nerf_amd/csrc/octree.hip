@@ -279,9 +279,8 @@ namespace {
 
 // (F2N_ADD_RN / _SUB_RN / _MUL_RN / _DIV_RN: single roundings that the compiler may not contract into an FMA, f2n_dev.h)
 
-// The grid point of index (ix, iy, iz): lo + step * i with two roundings, never contracted into an FMA, so that float32 numpy
-// (lo + np.float32(step) * np.float32(i)) restates it bit for bit.
-__device__ __forceinline__ float grid_coord(float lo, float step, int i) { return F2N_ADD_RN(lo, F2N_MUL_RN(step, (float) i)); }
+// The grid point of index (ix, iy, iz): lo + step * i with two roundings (f2n_grid_coord, f2n_dev.h)
+__device__ __forceinline__ float grid_coord(float lo, float step, int i) { return f2n_grid_coord(lo, step, i); }
 
 // Leaf of the point p, or -1 when p lies outside the root cube, in a missing child slot, or in a leaf with trans_idx < 0
 // (exactly the nodes the ray walk never lists).  *trans receives the leaf's trans_idx.
@@ -405,9 +404,22 @@ __constant__ int8_t c_tri_count[4] = {0, 1, 1, 2};
 
 __device__ __forceinline__ int64_t corner_index(int x, int y, int z, int nx, int ny) { return ((int64_t) z * ny + y) * nx + x; }
 
+// (masked meshing, f2n_mesh_count_masked) the cell whose lowest corner is (x, y, z) lies in the grid and all eight of its corners are valid
+__device__ __forceinline__ bool cell_observed(int x, int y, int z, int nx, int ny, int nz, const uint8_t* __restrict__ valid) {
+  if (x < 0 || y < 0 || z < 0 || x + 1 >= nx || y + 1 >= ny || z + 1 >= nz) return false;
+  bool all = true;
+#pragma unroll
+  for (int o = 0; o < 8; o++) all = all && valid[corner_index(x + (o & 1), y + ((o >> 1) & 1), z + ((o >> 2) & 1), nx, ny)] != 0;
+  return all;
+}
+
 // Vertex count pass: bit t of edge_mask[c] = edge of type t from corner c to a corner inside the grid crosses the level.
+// MASKED: ... and one of the cells whose Kuhn tetrahedra use that edge is observed: the cells c - d, d over the subsets of the axes
+// the edge's offset does not have.
+template <bool MASKED>
 __global__ void __launch_bounds__(256) mesh_vert_count_kernel(int nx, int ny, int nz, const float* __restrict__ g, float level,
-                                                             uint8_t* __restrict__ edge_mask, int32_t* __restrict__ counts) {
+                                                             const uint8_t* __restrict__ valid, uint8_t* __restrict__ edge_mask,
+                                                             int32_t* __restrict__ counts) {
   const int64_t c = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= (int64_t) nx * ny * nz) return;
   const int x = (int) (c % nx), y = (int) ((c / nx) % ny), z = (int) (c / ((int64_t) nx * ny));
@@ -418,7 +430,17 @@ __global__ void __launch_bounds__(256) mesh_vert_count_kernel(int nx, int ny, in
     const int dx = o & 1, dy = (o >> 1) & 1, dz = (o >> 2) & 1;
     if (x + dx >= nx || y + dy >= ny || z + dz >= nz) continue;
     const bool in1 = g[corner_index(x + dx, y + dy, z + dz, nx, ny)] > level;
-    if (in0 != in1) m |= 1u << c_edge_type[o];
+    if (in0 == in1) continue;
+    if (MASKED) {
+      bool used = false;
+#pragma unroll
+      for (int d = 0; d < 8; d++) {
+        if (d & o) continue;  // (only the axes the edge does not run along)
+        used = used || cell_observed(x - (d & 1), y - ((d >> 1) & 1), z - ((d >> 2) & 1), nx, ny, nz, valid);
+      }
+      if (!used) continue;
+    }
+    m |= 1u << c_edge_type[o];
   }
   edge_mask[c] = (uint8_t) m;
   counts[c] = __popc(m);
@@ -437,15 +459,16 @@ __device__ __forceinline__ int tet_inside(int cm, int t) {
   return ((cm >> 0) & 1) | (((cm >> a) & 1) << 1) | (((cm >> ab) & 1) << 2) | (((cm >> 7) & 1) << 3);
 }
 
+template <bool MASKED>
 __global__ void __launch_bounds__(256) mesh_face_count_kernel(int nx, int ny, int nz, const float* __restrict__ g, float level,
-                                                             int32_t* __restrict__ counts) {
+                                                             const uint8_t* __restrict__ valid, int32_t* __restrict__ counts) {
   const int cx = nx - 1, cy = ny - 1;
   const int64_t c = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= (int64_t) cx * cy * (nz - 1)) return;
   const int x = (int) (c % cx), y = (int) ((c / cx) % cy), z = (int) (c / ((int64_t) cx * cy));
   const int cm = cell_mask(x, y, z, nx, ny, g, level);
   int n = 0;
-  if (cm != 0 && cm != 255)
+  if (cm != 0 && cm != 255 && (!MASKED || cell_observed(x, y, z, nx, ny, nz, valid)))
     for (int t = 0; t < 6; t++) n += c_tri_count[c_tet_case[tet_inside(cm, t)][0]];
   counts[c] = n;
 }
@@ -531,6 +554,17 @@ __global__ void __launch_bounds__(256) mesh_face_emit_kernel(int nx, int ny, int
   }
 }
 
+// TSDF of the running sums of f2n_tsdf_integrate: positive inside (the mesher's convention), 0 and invalid where too little was seen
+__global__ void __launch_bounds__(256) tsdf_finalize_kernel(int64_t n, const float* __restrict__ S, const float* __restrict__ W,
+                                                           float min_weight, float* __restrict__ g, uint8_t* __restrict__ valid) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float w = W[i];
+  const bool ok = w >= min_weight && w > 0.f;
+  valid[i] = ok ? 1 : 0;
+  g[i] = ok ? F2N_DIV_RN(-S[i], w) : 0.f;
+}
+
 }  // namespace
 
 int f2n_oct_locate_warp(void* stream, int n, const float* pts_world, const void* tree_nodes, const void* transes, float* out_pts_warped,
@@ -586,21 +620,42 @@ static bool mesh_dims_ok(int nx, int ny, int nz) {
   return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t) nx * ny * nz <= 0x7fffffff;
 }
 
-int f2n_mesh_count(void* stream, int nx, int ny, int nz, const float* grid, float level, uint8_t* edge_mask, int32_t* vert_counts,
-                   int32_t* vert_start_end, int32_t* face_counts, int32_t* face_start_end, int32_t* totals) {
+template <bool MASKED>
+static int mesh_count(void* stream, int nx, int ny, int nz, const float* grid, float level, const uint8_t* valid, uint8_t* edge_mask,
+                      int32_t* vert_counts, int32_t* vert_start_end, int32_t* face_counts, int32_t* face_start_end, int32_t* totals) {
   if (!mesh_dims_ok(nx, ny, nz) || grid == nullptr || edge_mask == nullptr || vert_counts == nullptr || vert_start_end == nullptr ||
-      face_counts == nullptr || face_start_end == nullptr || totals == nullptr)
+      face_counts == nullptr || face_start_end == nullptr || totals == nullptr || (MASKED && valid == nullptr))
     return F2N_ERR_INVALID_ARG;
   const int64_t n_corners = (int64_t) nx * ny * nz, n_cells = (int64_t) (nx - 1) * (ny - 1) * (nz - 1);
-  hipLaunchKernelGGL(mesh_vert_count_kernel, dim3(f2n_div_up(n_corners, 256)), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, grid, level,
-                     edge_mask, vert_counts);
+  hipLaunchKernelGGL(mesh_vert_count_kernel<MASKED>, dim3(f2n_div_up(n_corners, 256)), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, grid,
+                     level, valid, edge_mask, vert_counts);
   int e = f2n_launch_status();
   if (e != F2N_OK) return e;
-  hipLaunchKernelGGL(mesh_face_count_kernel, dim3(f2n_div_up(n_cells, 256)), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, grid, level,
-                     face_counts);
+  hipLaunchKernelGGL(mesh_face_count_kernel<MASKED>, dim3(f2n_div_up(n_cells, 256)), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, grid,
+                     level, valid, face_counts);
   if ((e = f2n_launch_status()) != F2N_OK) return e;
   if ((e = f2n_segment_scan(stream, (int) n_corners, vert_counts, vert_start_end, totals)) != F2N_OK) return e;
   return f2n_segment_scan(stream, (int) n_cells, face_counts, face_start_end, totals + 1);
+}
+
+int f2n_mesh_count(void* stream, int nx, int ny, int nz, const float* grid, float level, uint8_t* edge_mask, int32_t* vert_counts,
+                   int32_t* vert_start_end, int32_t* face_counts, int32_t* face_start_end, int32_t* totals) {
+  return mesh_count<false>(stream, nx, ny, nz, grid, level, nullptr, edge_mask, vert_counts, vert_start_end, face_counts, face_start_end,
+                           totals);
+}
+
+int f2n_mesh_count_masked(void* stream, int nx, int ny, int nz, const float* grid, float level, const uint8_t* valid, uint8_t* edge_mask,
+                          int32_t* vert_counts, int32_t* vert_start_end, int32_t* face_counts, int32_t* face_start_end, int32_t* totals) {
+  return mesh_count<true>(stream, nx, ny, nz, grid, level, valid, edge_mask, vert_counts, vert_start_end, face_counts, face_start_end,
+                          totals);
+}
+
+int f2n_tsdf_finalize(void* stream, int64_t n, const float* S, const float* W, float min_weight, float* g, uint8_t* valid) {
+  if (n < 0 || n > (int64_t) 0x7fffffff * 256 || min_weight != min_weight) return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  if (S == nullptr || W == nullptr || g == nullptr || valid == nullptr) return F2N_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(tsdf_finalize_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, S, W, min_weight, g, valid);
+  return f2n_launch_status();
 }
 
 int f2n_mesh_emit(void* stream, int nx, int ny, int nz, const float* grid, float level, const float* lo /*host [3]*/, float step,

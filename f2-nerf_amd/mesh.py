@@ -16,6 +16,20 @@ Options (hydra-style overrides, no `mesh` group in the configs):
   mesh.colors      true: per-vertex colours (uchar red, green, blue; default false): the radiance AT the vertex seen along the
                    inward normal -- a single-point query, not a volume-rendered pixel
   mesh.min_component_faces  N > 1: connected components of fewer than N faces ("floaters") are dropped (default 0: none)
+  mesh.source      density | tsdf (default density): the iso-surface of the raw density at mesh.level, or the zero crossing of a
+                   truncated signed distance field fused from the training views' rendered depth (fuse_tsdf; mesh.level is not
+                   used, normals of source "grid" come from the TSDF) -> <exp>/meshes/<iter>_<res>_tsdf.ply
+
+TSDF fusion (mesh.source=tsdf): every training camera is rendered with runner.render_geometry at 1/res_level of its resolution, the rays'
+surface distances (surf_t, weighted by the rays' opacity) are fused into the grid of mesh.resolution / mesh.bbox_* (f2n_tsdf_integrate),
+and the masked mesher leaves the surface open where no camera looked (f2n_mesh_count_masked).  Options:
+  tsdf.res_level     the depth maps are rendered at 1/res_level of the cameras' resolution (default 4)
+  tsdf.trunc_voxels  truncation distance in grid steps (default 4)
+  tsdf.tau           the surface of a ray is its first sample at which the accumulated weight reaches tau (default 0.5)
+  tsdf.min_opacity   rays whose opacity is below this carry no surface (default 0.5)
+  tsdf.min_weight    a grid point is known where its summed weight reaches this (default 1.0)
+  tsdf.views_per_batch  cameras rendered per integration launch (default 8); the result does not depend on it
+  tsdf.max_views     only the first N training cameras are fused (default 0: all)
 
 Point-cloud export: `mode=extract_points is_continue=true` renders every training camera with runner.render_geometry and writes the
 rays' surface points, oriented and coloured, to <exp>/points/<iter>.ply in the data set's world frame (the usual input of a Poisson
@@ -43,7 +57,32 @@ def options(cfg):
     hi = [float(v) for v in m.get("bbox_max", ps.get("bbox_max", [1.0, 1.0, 1.0]))]
     return {"resolution": int(m.get("resolution", 256)), "level": float(m.get("level", DEFAULT_LEVEL)), "bbox_min": lo,
             "bbox_max": hi, "normals": _flag(m.get("normals", False)), "colors": _flag(m.get("colors", False)),
-            "min_component_faces": int(m.get("min_component_faces", 0)), "normal_source": _normal_source(m.get("normal_source", "grid"))}
+            "min_component_faces": int(m.get("min_component_faces", 0)), "normal_source": _normal_source(m.get("normal_source", "grid")),
+            "source": _source(m.get("source", "density"))}
+
+
+SOURCES = ("density", "tsdf")
+
+
+def _source(v):
+    s = str(v).strip().lower()
+    if s not in SOURCES:
+        raise ValueError("mesh.source must be one of %s, got %r" % (" | ".join(SOURCES), v))
+    return s
+
+
+def tsdf_options(cfg):
+    """The tsdf.* options.  The defaults follow common practice (a truncation of a few voxels, the point-cloud export's thresholds); none
+    of them is measured on a scene."""
+    t = cfg.get("tsdf") or {}
+    o = {"res_level": int(t.get("res_level", 4)), "trunc_voxels": float(t.get("trunc_voxels", 4.0)), "tau": float(t.get("tau", 0.5)),
+         "min_opacity": float(t.get("min_opacity", 0.5)), "min_weight": float(t.get("min_weight", 1.0)),
+         "views_per_batch": int(t.get("views_per_batch", 8)), "max_views": int(t.get("max_views", 0))}
+    if (o["res_level"] < 1 or o["views_per_batch"] < 1 or o["max_views"] < 0 or not 0.0 < o["tau"] <= 1.0 or
+            not 0.0 < o["trunc_voxels"] < float("inf") or not o["min_weight"] >= 0.0 or not o["min_opacity"] >= 0.0):
+        raise ValueError("tsdf.res_level and tsdf.views_per_batch must be >= 1, tsdf.max_views >= 0, tsdf.tau in (0, 1], tsdf.trunc_voxels "
+                         "> 0 and finite, tsdf.min_weight and tsdf.min_opacity >= 0, got %r" % (o,))
+    return o
 
 
 NORMAL_SOURCES = ("grid", "field")
@@ -193,9 +232,109 @@ def extract_points(runner, cfg, scene, dataset, exp_dir):
     return path
 
 
-def extract(runner, cfg, scene, exp_dir):
-    """Density grid -> iso-surface -> <exp_dir>/meshes/<iter>_<res>.ply, vertices in the data set's world frame."""
+def tsdf_camera_rays(dataset, bounds, idx, s):
+    """Rays of camera idx on the regular sub-grid of the TSDF depth maps: h = H // s, w = W // s, entry (a, b) looks through pixel
+    (a s + s // 2, b s + s // 2) -- inside pixel (a, b) of an image s times smaller, whose intrinsics are fx, fy, cx, cy divided by s.
+    Returns (rays_o, rays_d, bounds, h, w)."""
+    import torch
+    s = int(s)
+    h, w = int(dataset.height) // s, int(dataset.width) // s
+    if h < 1 or w < 1:
+        raise ValueError("tsdf.res_level %d leaves no pixel of a %d x %d image" % (s, int(dataset.height), int(dataset.width)))
+    ii = torch.arange(h, dtype=torch.int32, device="cuda") * s + s // 2
+    jj = torch.arange(w, dtype=torch.int32, device="cuda") * s + s // 2
+    gi, gj = torch.meshgrid(ii, jj, indexing="ij")
+    ij = torch.stack([gi.reshape(-1), gj.reshape(-1)], -1).contiguous()
+    ro, rd = dataset.img2world_ray_flex(torch.full((h * w,), int(idx), dtype=torch.int32, device="cuda"), ij)
+    b = torch.as_tensor(np.asarray(bounds, np.float32)[idx], device="cuda").reshape(1, 2).repeat(h * w, 1).contiguous()
+    return ro, rd, b, h, w
+
+
+def tsdf_intrinsics(intri, s):
+    """intri [V,3,3] in units of the depth maps' pixels: fx, fy, cx, cy divided by s (float32)."""
+    k = np.array(intri, np.float32, copy=True).reshape(-1, 3, 3)
+    for r, c in ((0, 0), (1, 1), (0, 2), (1, 2)):
+        k[:, r, c] = k[:, r, c] / np.float32(s)
+    return k
+
+
+def fuse_tsdf(runner, dataset, scene, o):
+    """The training views' rendered depth fused into a TSDF on the grid of o["bbox_min"] / o["bbox_max"] / o["resolution"] (the grid of
+    runner.density_grid).  o: options() and tsdf_options() in one dict.  Returns dict(g [nz, ny, nx] positive inside, valid uint8, S, W,
+    lo, step), tensors on the device.  No side effect on training: nothing is drawn, no vote is cast, a pending step is flushed first."""
+    import torch
+    from . import runtime
+    host = runtime.host()
+    runner.flush()
+    lo = [float(v) for v in o["bbox_min"]]
+    step, nx, ny, nz = host.grid_spec(lo, [float(v) for v in o["bbox_max"]], int(o["resolution"]))
+    S = torch.zeros((nz, ny, nx), dtype=torch.float32, device="cuda")
+    W = torch.zeros((nz, ny, nx), dtype=torch.float32, device="cuda")
+    views = [int(v) for v in scene["train_set"]]
+    if o["max_views"] > 0:
+        views = views[:o["max_views"]]
+    s = int(o["res_level"])
+    trunc = float(np.float32(o["trunc_voxels"]) * np.float32(step))
+    for k in range(0, len(views), o["views_per_batch"]):
+        batch = views[k:k + o["views_per_batch"]]
+        depth, conf = [], []
+        for idx in batch:
+            ro, rd, b, h, w = tsdf_camera_rays(dataset, scene["bounds"], idx, s)
+            g = runner.render_geometry(ro, rd, b, tau=o["tau"])
+            hit = (g["surf_idx"] >= 0) & (g["opacity"] >= o["min_opacity"])
+            depth.append(torch.where(hit, g["surf_t"], torch.zeros_like(g["surf_t"])).reshape(h, w))
+            conf.append(g["opacity"].reshape(h, w))
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()  # noqa: E731
+        host.tsdf_integrate(S, W, lo, step, dev(np.asarray(scene["poses"], np.float32)[batch]), dev(tsdf_intrinsics(np.asarray(scene["intri"])[batch], s)),
+                            dev(np.asarray(scene["dist_params"], np.float32)[batch]), torch.stack(depth).contiguous(),
+                            torch.stack(conf).contiguous(), trunc)
+    g, valid = host.tsdf_finalize(S, W, float(o["min_weight"]))
+    return {"g": g, "valid": valid, "S": S, "W": W, "lo": lo, "step": step, "n_views": len(views), "trunc": trunc}
+
+
+def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
+    """fuse_tsdf -> the masked mesher at level 0 -> <exp_dir>/meshes/<iter>_<res>_tsdf.ply, with the floater removal, normals and colours
+    of the density export (mesh.min_component_faces, mesh.normals, mesh.normal_source, mesh.colors)."""
+    if dataset is None:
+        raise ValueError("mesh.source=tsdf renders the training cameras: it needs the data set")
+    import torch
+    from . import runtime
+    host = runtime.host()
     o = options(cfg)
+    o.update(tsdf_options(cfg))
+    t = fuse_tsdf(runner, dataset, scene, o)
+    verts, faces = host.mesh_from_grid_masked(t["g"], t["valid"], t["lo"], t["step"], 0.0)
+    if o["min_component_faces"] > 1:
+        verts, faces, _ = host.mesh_filter_components(verts, faces, o["min_component_faces"])
+    normals = colors = None
+    if (o["normals"] or o["colors"]) and len(verts) > 0:
+        nrm = host.grid_normals(t["g"], verts, t["lo"], t["step"])  # (g is positive inside, as a density is: the same sign)
+        if o["normal_source"] == "field":  # the field's own gradient at the vertex; the grid's where that vanishes
+            fn = runner.field_normals(verts)
+            nrm = torch.where((fn == 0).all(1, keepdim=True), nrm, fn).contiguous()
+        if o["normals"]:
+            normals = nrm.cpu().numpy()
+        if o["colors"]:  # the radiance AT the vertex seen along the inward normal, as in the density export
+            flat = (nrm == 0).all(1, keepdim=True)
+            dirs = torch.where(flat, torch.tensor([[0.0, 0.0, -1.0]], device=nrm.device), -nrm).contiguous()
+            colors = runner.query_radiance(verts, dirs)[1].cpu().numpy()
+    elif o["normals"] or o["colors"]:
+        normals = np.zeros((0, 3), np.float32) if o["normals"] else None
+        colors = np.zeros((0, 3), np.float32) if o["colors"] else None
+    path = os.path.join(exp_dir, "meshes", "%d_%d_tsdf.ply" % (runner.iter_step, o["resolution"]))
+    v = to_world(verts.cpu().numpy(), scene["center"], scene["radius"])
+    write_ply(path, v, faces.cpu().numpy(), normals, colors)
+    print("Mesh: %d vertices, %d faces from the TSDF of %d views (%d of %d grid points known, truncation %g) -> %s" % (
+        len(v), len(faces), t["n_views"], int(t["valid"].sum()), t["valid"].numel(), t["trunc"], path))
+    return path
+
+
+def extract(runner, cfg, scene, exp_dir, dataset=None):
+    """Density grid -> iso-surface -> <exp_dir>/meshes/<iter>_<res>.ply, vertices in the data set's world frame (mesh.source=tsdf:
+    extract_tsdf, which needs the data set)."""
+    o = options(cfg)
+    if o["source"] == "tsdf":
+        return extract_tsdf(runner, cfg, scene, dataset, exp_dir)
     path = os.path.join(exp_dir, "meshes", "%d_%d.ply" % (runner.iter_step, o["resolution"]))
     if not (o["normals"] or o["colors"] or o["min_component_faces"] > 1):
         verts, faces = runner.extract_mesh(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"])

@@ -13,7 +13,8 @@
     are applied as there; images are decoded with PIL and kept resident in HBM.
   * modes (ExpRunner::Execute): train (ExpRunner::Train with checkpoints every save_freq and the final TestImages),
     test (TestImages of the latest checkpoint), render_path (RenderPath over poses_render.npy), extract_mesh (with is_continue:
-    <exp>/meshes/<iter>_<res>.ply, the density iso-surface in the data set's world frame; mesh.py), extract_points (with
+    <exp>/meshes/<iter>_<res>.ply, the density iso-surface in the data set's world frame, or with mesh.source=tsdf the surface fused from
+    the training views' rendered depth; mesh.py), extract_points (with
     is_continue: <exp>/points/<iter>.ply, the training views' surface points with normals and colours; mesh.py).  Image files are written with
     PIL; everything per-ray runs in the C++/HIP host (there is no Python in the training loop: ExpRunner::Train).
   * data-parallel training (the reference is single-GPU): launched as N ranks -- `python -m torch.distributed.run --nnodes=1
@@ -201,7 +202,10 @@ def main(argv=None):
                 save_png(os.path.join(exp_dir, "images", "%d_%d.png" % (runner.iter_step, idx)), runner.visualize_image(ds, idx))
         elif mode == "extract_mesh":  # no reference counterpart: <exp>/meshes/<iter>_<res>.ply (mesh.py; options mesh.*)
             from . import mesh
-            mesh.extract(runner, cfg, sc, exp_dir)
+            if mesh.options(cfg)["source"] == "tsdf":  # (fused from renders of the training cameras: the one source that needs them)
+                mesh.extract(runner, cfg, sc, exp_dir, dataset=ds)
+            else:
+                mesh.extract(runner, cfg, sc, exp_dir)
         elif mode == "extract_points":  # no reference counterpart: <exp>/points/<iter>.ply (mesh.py; options points.*)
             from . import mesh
             mesh.extract_points(runner, cfg, sc, ds, exp_dir)

@@ -943,6 +943,51 @@ int f2n_composite_geometry(void* stream, int n_rays, const int32_t* pts_start_en
                            float* out_surf_point /*[R,3]*/, float* out_surf_normal /*[R,3]*/, float* out_sample_grad /*[M,3] or NULL*/,
                            float* out_sample_normal /*[M,3] or NULL*/);
 
+/* ---------------------------------------------------------------------------------------------------
+ * TSDF fusion of depth maps (additive; the ABI version is unchanged).  No reference counterpart.
+ * ------------------------------------------------------------------------------------------------- */
+/* Adds n_views depth maps into the running sums S [N] (sum of w d) and W [N] (sum of w) of the implicit grid of
+ * f2n_oct_locate_warp_grid: N = nx ny nz points (64 bits), x fastest, p_k = lo[k] + step * (float) i_k (rounded twice, never an FMA);
+ * lo is HOST data.  csrc/dataset.hip.
+ *   poses [V,3,4] camera-to-world (R | o), intri [V,3,3] in units of depth-map pixels (fx = [0], cx = [2], fy = [4], cy = [5]),
+ *   dist_params [V,4], depth [V,h,w] = the Euclidean distance from the camera centre to the surface along the pixel's ray (no surface
+ *   where the value is not > 0: zero, negative, NaN), conf [V,h,w] or NULL (weight 1), trunc > 0 and finite.
+ * One thread owns one voxel and walks the views in index order; every operation below is ONE fp32 rounding, in this order:
+ *    1. q = p - o_v                                            (componentwise)
+ *    2. c_j = R[0][j] q_0 + (R[1][j] q_1 + R[2][j] q_2)        (c = R^T q: three products, then f2n_sum3's order)
+ *    3. s = -c_2; skip the view unless s > 0
+ *    4. u = c_0 / s, v = (-c_1) / s                            (the inverse of the ray direction (u, -v, -1) of f2n_img2world_rays)
+ *    5. (du, dv) = the distortion of f2n_img2world_rays' camera model at (u, v):  r2 = u u + v v, radial = k1 r2 + (k2 r2) r2,
+ *       du = (u radial + (2 p1) (u v)) + p2 (r2 + 2 (u u)), dv = (v radial + (2 p2) (u v)) + p1 (r2 + 2 (v v))
+ *    6. x = fx (u + du) + cx, y = fy (v + dv) + cy
+ *    7. b = floor(x), a = floor(y); skip unless 0 <= a < h and 0 <= b < w (NaN skips)   -- the NEAREST pixel: no interpolation
+ *       across depth discontinuities
+ *    8. D = depth[v,a,b]; skip unless D > 0
+ *    9. wgt = conf ? conf[v,a,b] : 1; skip unless wgt > 0
+ *   10. sdf = D - sqrt(q_0 q_0 + (q_1 q_1 + q_2 q_2)); skip if sdf < -trunc
+ *   11. d = sdf / trunc; d = d < 1 ? d : 1
+ *   12. S += wgt d;  W += wgt
+ * S and W are read once and written once per launch; there are no atomics, so the outputs are a function of the inputs alone, and
+ * integrating the views [0, k) and then [k, V) into the same state gives the bits of one call over [0, V).
+ * n_views == 0 or N == 0: F2N_OK, nothing is touched.  F2N_ERR_INVALID_ARG: a negative size, h or w outside [1, 2^24], trunc not
+ * positive and finite, a NULL pointer other than conf. */
+int f2n_tsdf_integrate(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int n_views,
+                       const float* poses /*[V,3,4]*/, const float* intri /*[V,3,3]*/, const float* dist_params /*[V,4]*/,
+                       const float* depth /*[V,h,w]*/, const float* conf /*[V,h,w] or NULL*/, int h, int w, float trunc,
+                       float* S /*[N]*/, float* W /*[N]*/);
+/* The signed distance of the sums, POSITIVE INSIDE (the mesher's convention "inside iff g > level"), and where it is known:
+ *   valid[i] = (W[i] >= min_weight && W[i] > 0);  g[i] = valid[i] ? (-S[i]) / W[i] : 0.   min_weight must not be NaN.  csrc/octree.hip. */
+int f2n_tsdf_finalize(void* stream, int64_t n, const float* S, const float* W, float min_weight, float* g /*[n]*/, uint8_t* valid /*[n]*/);
+/* f2n_mesh_count with a mask of the corners that carry a value (valid [N], non-zero = valid): the same outputs, for the UNCHANGED
+ * f2n_mesh_emit.  A cell has faces only if all eight of its corners are valid.  The edge of offset o owned by corner c keeps its bit
+ * only if it crosses the level AND at least one cell c - d inside the grid has eight valid corners, d running over the subsets of the
+ * axes that o does not have -- exactly the cells whose Kuhn tetrahedra use that edge.  So every emitted vertex is used by a face, every
+ * face comes from a fully observed cell, and the surface is open where observation ends.  With valid all non-zero every output equals
+ * f2n_mesh_count's bit for bit.  csrc/octree.hip. */
+int f2n_mesh_count_masked(void* stream, int nx, int ny, int nz, const float* grid, float level, const uint8_t* valid /*[N]*/,
+                          uint8_t* edge_mask /*[N]*/, int32_t* vert_counts /*[N]*/, int32_t* vert_start_end /*[N,2]*/,
+                          int32_t* face_counts /*[C]*/, int32_t* face_start_end /*[C,2]*/, int32_t* totals /*[2]*/);
+
 #ifdef __cplusplus
 }
 #endif
