@@ -240,6 +240,17 @@ Tensor Hash3DAnchored::HashEncode(const Tensor& points, const Tensor& anchors) {
   return HashEncodeFunction::apply(feat_pool_, pts, anchors, reinterpret_cast<int64_t>(this))[0];
 }
 
+void Hash3DAnchored::DensityGrad(const Tensor& points, const Tensor& vol, const Tensor& x_h, Tensor& g) {
+  F2N_TIMED_CALL("field_density_grad", f2n_field_density_grad(CurStream(), (int) points.size(0), n_volumes_, VoidP(feat_pool_h_), I32P(prim_pool_),
+                         I32P(feat_local_idx_), I32P(feat_local_size_), F32P(bias_pool_), F32P(level_scale_), F32P(points), I32P(vol), 1,
+                         VoidP(mlp_->params_h_), VoidP(x_h), nullptr, F32P(g)));
+}
+
+void Hash3DAnchored::PosGrad(const Tensor& points, const Tensor& vol, const Tensor& dx, Tensor& g) {
+  F2N_CALL(f2n_hash_pos_grad(CurStream(), (int) points.size(0), n_volumes_, VoidP(feat_pool_h_), I32P(prim_pool_), I32P(feat_local_idx_),
+                             I32P(feat_local_size_), F32P(bias_pool_), F32P(level_scale_), F32P(points), I32P(vol), 1, F32P(dx), F32P(g)));
+}
+
 void Hash3DAnchored::ForwardRaw(const Tensor& points, const Tensor& anchors, int stride, const Tensor& src_rows, int n_reuse,
                                 Tensor& feat, Tensor& saved_x, Tensor* f0_cached) {
   const int n = points.size(0);

@@ -38,6 +38,10 @@ class Hash3DAnchored : public Field {
   // (csrc/mlp_generic.hip through FusedMLP::Query) -> f2n_hash_bwd, on the autograd tape (no feature cache, no streaming step).
   bool fused_ok_ = true;
   Tensor HashEncode(const Tensor& points, const Tensor& anchors);  // [n,32] fp32 features, differentiable w.r.t. the table
+  // df0/dw [n,3] into g for the rows (points [n,3] warped, vol [n]): from their h16 hash features x_h [n,32] through the field network
+  // (f2n_field_density_grad, the fused shape only), or from any df0/dx [n,32] fp32 (f2n_hash_pos_grad)
+  void DensityGrad(const Tensor& points, const Tensor& vol, const Tensor& x_h, Tensor& g);
+  void PosGrad(const Tensor& points, const Tensor& vol, const Tensor& dx, Tensor& g);
   Tensor TableGradUnscaled();  // fp32 [pool,2] = grad_h / 128 (Hash3DAnchored.cu:232)
 
   int pool_size_;

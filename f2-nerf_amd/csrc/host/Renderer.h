@@ -307,6 +307,9 @@ class Renderer : public Pipe {
   // on the grid of MakeGridSpec as [nz, ny, nx] (x fastest), in z-slabs of at most density_slab_points_ points; and the
   // iso-surface of that grid at `level`.  Free of side effects on training (no keyed draws, no occupancy votes, the pre-pass
   // feature cache kept); the caller flushes a streaming step first (ExpRunner::FinishPending).
+  // Every point query below is the same four steps (helpers at the top of RendererQuery.cpp): locate; LocatedRows = the non-empty
+  // points compacted into rows, whose count is the query's one read-back; the query's own field calls on the rows, under a
+  // PrepassCacheGuard that puts Hash3DAnchored::prepass_x_ back on every exit path, an exception included; its own scatter kernel.
   Tensor QueryDensity(const Tensor& world);
   Tensor DensityGrid(const std::vector<float>& lo, const std::vector<float>& hi, int res);
   std::tuple<Tensor, Tensor> ExtractMesh(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level);
@@ -325,13 +328,16 @@ class Renderer : public Pipe {
   // (density [n], grad [n,3]) at world points: the density of QueryDensity, bit for bit, and its analytic gradient with respect to the
   // world position, sigma J^T df0/dw (f2n_field_density_grad / f2n_density_grad_scatter: the hash table's trilinear blend, the
   // density MLP and the leaf's warp differentiated exactly, fp32); zeros where no listed leaf holds the point.  Field shapes
-  // without the fused kernels take df0/dx from f2n_mlp_bwd (its h16 roundings) and f2n_hash_pos_grad.  The same side-effect contract
-  // as QueryDensity; reads back only the row count.
+  // without the fused kernels take df0/dx from f2n_mlp_bwd (its h16 roundings) and f2n_hash_pos_grad: both routes are Df0Dw of
+  // RendererQuery.cpp, which RenderGeometry shares.  The same side-effect contract as QueryDensity; reads back only the row count.
   std::tuple<Tensor, Tensor> QueryDensityGrad(const Tensor& world);
   // -grad / |grad| of QueryDensityGrad (the sign of GridNormals); 0 where |grad| is 0 or not finite, or the point is empty
   Tensor FieldNormals(const Tensor& world);
-  // density, grad and (optionally) unit normals of at most density_slab_points_ points
-  void DensityGradChunk(const Tensor& world, Tensor& density, Tensor& grad, Tensor* normals);
+  // The slab loop both share: world [n,3] in chunks of at most density_slab_points_ points, each through DensityGradChunk; whichever
+  // of density [n], grad [n,3], normals [n,3] is defined is filled (an undefined density / grad gets a scratch buffer per chunk).
+  void DensityGradSlabs(const Tensor& world, const Tensor& density, const Tensor& grad, const Tensor& normals);
+  // density, grad and (where defined) unit normals of one chunk, written in place
+  void DensityGradChunk(const Tensor& world, const Tensor& density, const Tensor& grad, const Tensor& normals);
   // RenderForward plus geometry buffers (f2n_composite_geometry): per ray the opacity (sum of the weights), the weight-composited
   // unit normal, and the surface = the first sample at which the accumulated weight reaches tau (index, t, world point, normal; -1 and
   // zeros where none does).  The samples' normals are -J^T df0/dw / |.| at o + t d: f2n_field_density_grad on the survivors' rows of

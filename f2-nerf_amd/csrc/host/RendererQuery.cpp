@@ -2,17 +2,83 @@
 // None of this is on the training path: the queries draw nothing from the keyed streams, touch no occupancy statistics and leave
 // the pre-pass feature cache of Hash3DAnchored (prepass_x_) as they found it.  Callers flush a streaming step first
 // (ExpRunner::FinishPending, as SaveCheckpoint does).
+// Shared by the drivers, defined first: Points3, LocatedRows (locate -> compact: the non-empty points as rows, the one read-back),
+// PrepassCacheGuard (the cache contract on every exit path), Df0Dw (df0/dw of rows, fused or op by op), TwoTotals.  A point query
+// is: locate, rows, its own field calls under the guard, its own scatter kernel.
 #include <cmath>
 
 #include "Renderer.h"
 
 namespace f2n {
 
+namespace {
+
+// [n,3] float32 on the device, of at most INT32_MAX rows (the kernels count in int)
+Tensor Points3(const Tensor& t) {
+  Tensor p = t.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  TORCH_CHECK(p.size(0) <= INT32_MAX, "too many points");
+  return p;
+}
+
+// The non-empty points of a located set as rows of their own (f2n_located_compact): se [n,2] = every point's row range (what the
+// scatter kernels read), total = the row count on the device, pts / vol (/ src: the point each row came from, on request) = the m rows.
+// The field kernels take their row count from the host: m is the one read-back of a query.
+struct LocatedRows {
+  Tensor se, total, pts, vol, src;
+  int m = 0;
+  LocatedRows(const Tensor& warped, const Tensor& anchors, bool want_src) {
+    const int64_t n = anchors.size(0);
+    Tensor counts = torch::empty({n}, DevI32());
+    se = torch::empty({n, 2}, DevI32());
+    total = torch::empty({1}, DevI32());
+    Tensor cpts = torch::empty({n, 3}, DevF32()), cvol = torch::empty({n}, DevI32()), csrc;
+    if (want_src) csrc = torch::empty({n}, DevI32());
+    F2N_CALL(f2n_located_compact(CurStream(), (int) n, I32P(anchors), F32P(warped), I32P(counts), I32P(se), I32P(total), F32P(cpts),
+                                 I32P(cvol), want_src ? I32P(csrc) : nullptr));
+    m = total.item<int>();
+    pts = cpts.narrow(0, 0, m);
+    vol = cvol.narrow(0, 0, m);
+    if (want_src) src = csrc.narrow(0, 0, m);
+  }
+};
+
+// The side-effect contract of every query: a batch sampled ahead may still be served from the pre-pass feature cache, so whatever a
+// query's field calls make of Hash3DAnchored::prepass_x_ is undone when the guard goes out of scope -- by return or by exception.
+struct PrepassCacheGuard {
+  Hash3DAnchored* field;
+  Tensor kept;
+  explicit PrepassCacheGuard(Hash3DAnchored* f) : field(f), kept(f->prepass_x_) {}
+  ~PrepassCacheGuard() { field->prepass_x_ = kept; }
+};
+
+// df0/dw [m,3] of the rows (p [m,3] warped, v [m]) into g.  x_h defined: their h16 hash features, the fused route
+// (f2n_field_density_grad).  Undefined -- field shapes without the fused kernels --: df0/dx from the general MLP backward (its h16
+// roundings) with dy = e_0 and no loss scale, then f2n_hash_pos_grad.
+void Df0Dw(Hash3DAnchored* field, const Tensor& p, const Tensor& v, const Tensor& x_h, Tensor& g) {
+  if (x_h.defined()) return field->DensityGrad(p, v, x_h, g);
+  auto& mlp = *field->mlp_;
+  const int m = (int) p.size(0);
+  Tensor x = field->HashEncode(p, v).to(torch::kFloat32).contiguous();
+  Tensor dy = torch::zeros({m, F2N_MLP_OUT_PAD}, DevF32());
+  dy.select(1, 0).fill_(1.f);
+  Tensor dparams = torch::zeros({mlp.n_params_}, DevF32()), dx = torch::empty({m, mlp.d_in_}, DevF32());
+  F2N_CALL(f2n_mlp_bwd(CurStream(), m, mlp.d_in_, mlp.d_hidden_, mlp.n_hidden_layers_, 1.f, VoidP(mlp.params_h_), F32P(x), F32P(dy),
+                       F32P(dparams), F32P(dx)));
+  field->PosGrad(p, v, dx, g);
+}
+
+// the two totals a count kernel left on the device: the one read-back of a mesher (they size its outputs)
+std::pair<int64_t, int64_t> TwoTotals(const Tensor& totals) {
+  Tensor t = totals.cpu();
+  return {t.data_ptr<int32_t>()[0], t.data_ptr<int32_t>()[1]};
+}
+
+}  // namespace
+
 std::tuple<Tensor, Tensor> PersSampler::LocatePoints(const Tensor& world) {
   torch::NoGradGuard g;
-  Tensor w = world.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  Tensor w = Points3(world);
   const int64_t n = w.size(0);
-  TORCH_CHECK(n <= INT32_MAX, "too many points");
   Tensor warped = torch::empty({n, 3}, DevF32()), anchors = torch::empty({n, 3}, DevI32());
   auto& o = *pers_octree_;
   F2N_CALL(f2n_oct_locate_warp(CurStream(), (int) n, F32P(w), VoidP(o.tree_nodes_gpu_), VoidP(o.pers_trans_gpu_), F32P(warped),
@@ -26,19 +92,13 @@ Tensor Renderer::DensityOfLocated(const Tensor& warped, const Tensor& anchors) {
   const int64_t n = anchors.size(0);
   Tensor density = torch::empty({n}, DevF32());
   if (n == 0) return density;
-  Tensor counts = torch::empty({n}, DevI32()), se = torch::empty({n, 2}, DevI32()), total = torch::empty({1}, DevI32());
-  Tensor cpts = torch::empty({n, 3}, DevF32()), cvol = torch::empty({n}, DevI32());
-  F2N_CALL(f2n_located_compact(CurStream(), (int) n, I32P(anchors), F32P(warped), I32P(counts), I32P(se), I32P(total), F32P(cpts),
-                               I32P(cvol), nullptr));
-  // The field kernels take their row count from the host: the one read-back of a query (the densities stay on the device)
-  const int m = total.item<int>();
+  LocatedRows rows(warped, anchors, /*want_src=*/false);
   Tensor f0 = torch::zeros({1}, DevF32());
-  if (m > 0) {
-    Tensor keep = field->prepass_x_;  // a batch sampled ahead may still be served from this cache
-    f0 = field->QueryDensityPreAct(cpts.narrow(0, 0, m), cvol.narrow(0, 0, m), /*keep_features=*/false);
-    field->prepass_x_ = keep;
+  if (rows.m > 0) {
+    PrepassCacheGuard cache(field);
+    f0 = field->QueryDensityPreAct(rows.pts, rows.vol, /*keep_features=*/false);
   }
-  F2N_CALL(f2n_density_scatter(CurStream(), (int) n, I32P(anchors), I32P(se), F32P(f0), F32P(density)));
+  F2N_CALL(f2n_density_scatter(CurStream(), (int) n, I32P(anchors), I32P(rows.se), F32P(f0), F32P(density)));
   return density;
 }
 
@@ -57,41 +117,36 @@ std::tuple<Tensor, Tensor> Renderer::QueryRadiance(const Tensor& world, const Te
   const Tensor& warped = std::get<0>(located);
   const Tensor& anchors = std::get<1>(located);
   const int64_t n = anchors.size(0);
-  Tensor d = dirs.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  Tensor d = Points3(dirs);
   TORCH_CHECK(d.size(0) == n, "one view direction per point");
   Tensor density = torch::empty({n}, DevF32()), rgb = torch::empty({n, 3}, DevF32());
   if (n == 0) return {density, rgb};
-  Tensor counts = torch::empty({n}, DevI32()), se = torch::empty({n, 2}, DevI32()), total = torch::empty({1}, DevI32());
-  Tensor cpts = torch::empty({n, 3}, DevF32()), cvol = torch::empty({n}, DevI32()), csrc = torch::empty({n}, DevI32());
-  F2N_CALL(f2n_located_compact(CurStream(), (int) n, I32P(anchors), F32P(warped), I32P(counts), I32P(se), I32P(total), F32P(cpts),
-                               I32P(cvol), I32P(csrc)));
-  const int m = total.item<int>();  // (the pre-pass takes its row count from the host, as in DensityOfLocated)
+  LocatedRows rows(warped, anchors, /*want_src=*/true);
+  const int m = rows.m;
   Tensor f0 = torch::zeros({1}, DevF32()), crgb = torch::zeros({1, 3}, DevF32());
   if (m > 0) {
-    Tensor keep = field->prepass_x_;  // a batch sampled ahead may still be served from this cache
-    Tensor p = cpts.narrow(0, 0, m), v = cvol.narrow(0, 0, m);
-    Tensor cdirs = d.index_select(0, csrc.narrow(0, 0, m)).contiguous();  // the directions travel with their points
+    PrepassCacheGuard cache(field);
+    Tensor cdirs = d.index_select(0, rows.src).contiguous();  // the directions travel with their points
     if (FusedPathOk()) {
-      f0 = field->QueryDensityPreAct(p, v, /*keep_features=*/true);
+      f0 = field->QueryDensityPreAct(rows.pts, rows.vol, /*keep_features=*/true);
       TORCH_CHECK(field->prepass_x_.defined(), "no pre-pass feature cache for this query");
       crgb = torch::empty({m, 3}, DevF32());
       Tensor f0_again = torch::empty({m}, DevF32());  // (the fused launch writes its own copy; the density comes from the pre-pass)
-      F2N_CALL(f2n_field_shade_fwd_dyn(CurStream(), m, I32P(total), nullptr, VoidP(field->prepass_x_), VoidP(field->mlp_->params_h_),
+      F2N_CALL(f2n_field_shade_fwd_dyn(CurStream(), m, I32P(rows.total), nullptr, VoidP(field->prepass_x_), VoidP(field->mlp_->params_h_),
                                        F32P(cdirs), nullptr, nullptr, VoidP(shader->mlp_->params_h_), F32P(f0_again), nullptr, nullptr,
                                        F32P(crgb)));
     } else {  // network shapes without fused kernels: op by op, as Render()
-      f0 = field->QueryDensityPreAct(p, v, /*keep_features=*/false);
-      Tensor feat = field->AnchoredQuery(p, v);
+      f0 = field->QueryDensityPreAct(rows.pts, rows.vol, /*keep_features=*/false);
+      Tensor feat = field->AnchoredQuery(rows.pts, rows.vol);
       Tensor none = torch::empty({0}, DevF32());
       crgb = shader->QueryFromField(feat, cdirs, none, torch::empty({0}, DevI32()), nullptr).to(torch::kFloat32).contiguous();
     }
-    field->prepass_x_ = keep;
   }
-  F2N_CALL(f2n_radiance_scatter(CurStream(), (int) n, I32P(anchors), I32P(se), F32P(f0), F32P(crgb), F32P(density), F32P(rgb)));
+  F2N_CALL(f2n_radiance_scatter(CurStream(), (int) n, I32P(anchors), I32P(rows.se), F32P(f0), F32P(crgb), F32P(density), F32P(rgb)));
   return {density, rgb};
 }
 
-void Renderer::DensityGradChunk(const Tensor& w, Tensor& density, Tensor& grad, Tensor* normals) {
+void Renderer::DensityGradChunk(const Tensor& w, const Tensor& density, const Tensor& grad, const Tensor& normals) {
   auto* sampler = static_cast<PersSampler*>(pts_sampler_.get());
   auto* field = static_cast<Hash3DAnchored*>(scene_field_.get());
   auto located = sampler->LocatePoints(w);
@@ -99,73 +154,48 @@ void Renderer::DensityGradChunk(const Tensor& w, Tensor& density, Tensor& grad, 
   const Tensor& anchors = std::get<1>(located);
   const int64_t n = anchors.size(0);
   if (n == 0) return;
-  Tensor counts = torch::empty({n}, DevI32()), se = torch::empty({n, 2}, DevI32()), total = torch::empty({1}, DevI32());
-  Tensor cpts = torch::empty({n, 3}, DevF32()), cvol = torch::empty({n}, DevI32());
-  F2N_CALL(f2n_located_compact(CurStream(), (int) n, I32P(anchors), F32P(warped), I32P(counts), I32P(se), I32P(total), F32P(cpts),
-                               I32P(cvol), nullptr));
-  const int m = total.item<int>();  // (the field kernels take their row count from the host, as in DensityOfLocated)
+  LocatedRows rows(warped, anchors, /*want_src=*/false);
   Tensor f0 = torch::zeros({1}, DevF32()), g = torch::zeros({1, 3}, DevF32());
-  if (m > 0) {
-    Tensor keep = field->prepass_x_;  // a batch sampled ahead may still be served from this cache
-    Tensor p = cpts.narrow(0, 0, m), v = cvol.narrow(0, 0, m);
-    g = torch::empty({m, 3}, DevF32());
-    if (field->fused_ok_) {
-      f0 = field->QueryDensityPreAct(p, v, /*keep_features=*/true);
-      TORCH_CHECK(field->prepass_x_.defined(), "no pre-pass feature cache for this query");
-      F2N_CALL(f2n_field_density_grad(CurStream(), m, field->n_volumes_, VoidP(field->feat_pool_h_), I32P(field->prim_pool_),
-                                      I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
-                                      F32P(field->level_scale_), F32P(p), I32P(v), 1, VoidP(field->mlp_->params_h_),
-                                      VoidP(field->prepass_x_), nullptr, F32P(g)));
-    } else {  // network shapes without the fused kernels: df0/dx from the general MLP backward (its h16 roundings), dy = e_0, no loss scale
-      f0 = field->QueryDensityPreAct(p, v, /*keep_features=*/false);
-      auto& mlp = *field->mlp_;
-      Tensor x = field->HashEncode(p, v).to(torch::kFloat32).contiguous();
-      Tensor dy = torch::zeros({m, F2N_MLP_OUT_PAD}, DevF32());
-      dy.select(1, 0).fill_(1.f);
-      Tensor dparams = torch::zeros({mlp.n_params_}, DevF32()), dx = torch::empty({m, mlp.d_in_}, DevF32());
-      F2N_CALL(f2n_mlp_bwd(CurStream(), m, mlp.d_in_, mlp.d_hidden_, mlp.n_hidden_layers_, 1.f, VoidP(mlp.params_h_), F32P(x), F32P(dy),
-                           F32P(dparams), F32P(dx)));
-      F2N_CALL(f2n_hash_pos_grad(CurStream(), m, field->n_volumes_, VoidP(field->feat_pool_h_), I32P(field->prim_pool_),
-                                 I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
-                                 F32P(field->level_scale_), F32P(p), I32P(v), 1, F32P(dx), F32P(g)));
-    }
-    field->prepass_x_ = keep;
+  if (rows.m > 0) {
+    PrepassCacheGuard cache(field);
+    g = torch::empty({rows.m, 3}, DevF32());
+    f0 = field->QueryDensityPreAct(rows.pts, rows.vol, /*keep_features=*/field->fused_ok_);
+    TORCH_CHECK(!field->fused_ok_ || field->prepass_x_.defined(), "no pre-pass feature cache for this query");
+    Df0Dw(field, rows.pts, rows.vol, field->prepass_x_, g);  // (field shapes without the fused kernels keep no features)
   }
   auto& o = *sampler->pers_octree_;
-  F2N_CALL(f2n_density_grad_scatter(CurStream(), (int) n, F32P(w), I32P(anchors), I32P(se), VoidP(o.pers_trans_gpu_), F32P(f0), F32P(g),
-                                    F32P(density), F32P(grad), normals != nullptr ? F32P(*normals) : nullptr));
+  F2N_CALL(f2n_density_grad_scatter(CurStream(), (int) n, F32P(w), I32P(anchors), I32P(rows.se), VoidP(o.pers_trans_gpu_), F32P(f0), F32P(g),
+                                    F32P(density), F32P(grad), normals.defined() ? F32P(normals) : nullptr));
+}
+
+void Renderer::DensityGradSlabs(const Tensor& w, const Tensor& density, const Tensor& grad, const Tensor& normals) {
+  const int64_t n = w.size(0);
+  for (int64_t i0 = 0; i0 < n; i0 += density_slab_points_) {  // (bounded workspaces, as DensityGrid's slabs)
+    const int64_t c = std::min(density_slab_points_, n - i0);
+    DensityGradChunk(w.narrow(0, i0, c), density.defined() ? density.narrow(0, i0, c) : torch::empty({c}, DevF32()),
+                     grad.defined() ? grad.narrow(0, i0, c) : torch::empty({c, 3}, DevF32()),
+                     normals.defined() ? normals.narrow(0, i0, c) : Tensor());
+  }
 }
 
 std::tuple<Tensor, Tensor> Renderer::QueryDensityGrad(const Tensor& world) {
   torch::NoGradGuard g;
-  Tensor w = world.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
-  const int64_t n = w.size(0);
-  TORCH_CHECK(n <= INT32_MAX, "too many points");
-  Tensor density = torch::empty({n}, DevF32()), grad = torch::empty({n, 3}, DevF32());
-  for (int64_t i0 = 0; i0 < n; i0 += density_slab_points_) {  // (bounded workspaces, as DensityGrid's slabs)
-    const int64_t c = std::min(density_slab_points_, n - i0);
-    Tensor d = density.narrow(0, i0, c), gr = grad.narrow(0, i0, c);
-    DensityGradChunk(w.narrow(0, i0, c), d, gr, nullptr);
-  }
+  Tensor w = Points3(world);
+  Tensor density = torch::empty({w.size(0)}, DevF32()), grad = torch::empty({w.size(0), 3}, DevF32());
+  DensityGradSlabs(w, density, grad, Tensor());
   return {density, grad};
 }
 
 Tensor Renderer::FieldNormals(const Tensor& world) {
   torch::NoGradGuard g;
-  Tensor w = world.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
-  const int64_t n = w.size(0);
-  TORCH_CHECK(n <= INT32_MAX, "too many points");
-  Tensor normals = torch::empty({n, 3}, DevF32());
-  for (int64_t i0 = 0; i0 < n; i0 += density_slab_points_) {
-    const int64_t c = std::min(density_slab_points_, n - i0);
-    Tensor density = torch::empty({c}, DevF32()), grad = torch::empty({c, 3}, DevF32()), nr = normals.narrow(0, i0, c);
-    DensityGradChunk(w.narrow(0, i0, c), density, grad, &nr);
-  }
+  Tensor w = Points3(world);
+  Tensor normals = torch::empty({w.size(0), 3}, DevF32());
+  DensityGradSlabs(w, Tensor(), Tensor(), normals);
   return normals;
 }
 
 // RenderForward step by step (SampleAndFilter -> f2n_field_shade_fwd_dyn -> f2n_composite_fwd: the same launches on the same inputs,
-// so colours, disparity, depth and weights are its bits), then the survivors' df0/dw and f2n_composite_geometry.  The gradient
+// so colours, disparity, depth and weights are its bits), then the survivors' df0/dw (Df0Dw) and f2n_composite_geometry.  The gradient
 // kernels take their row count from the host and want the survivors' h16 features as rows of their own, so this path -- unlike
 // RenderForward, which leaves the count on the device -- reads the survivor count back, once per call (= per chunk of
 // ExpRunner::RenderGeometry), and takes the rows out of the pre-pass cache through src_rows before the cache is dropped.
@@ -190,85 +220,69 @@ GeometryResult Renderer::RenderGeometry(const Tensor& rays_o_in, const Tensor& r
   out.surf_t = torch::zeros({n_rays}, DevF32());
   out.surf_points = torch::zeros({n_rays, 3}, DevF32());
   out.surf_normals = torch::zeros({n_rays, 3}, DevF32());
-  auto no_samples = [&]() {
+  // keep_samples: the per-sample outputs are the first m rows of the samples' arrays and of the gradient / normal buffers
+  auto kept_samples = [&](const Tensor& pts, const Tensor& anchors, const Tensor& t, const Tensor& dt, int64_t m) {
     if (!keep_samples) return;
-    out.pts = torch::empty({0, 3}, DevF32());
-    out.anchors = torch::empty({0, 3}, DevI32());
-    out.t = torch::empty({0}, DevF32());
-    out.dt = torch::empty({0}, DevF32());
-    out.sample_grad = torch::empty({0, 3}, DevF32());
-    out.sample_normals = torch::empty({0, 3}, DevF32());
+    out.pts = pts.narrow(0, 0, m);
+    out.anchors = anchors.narrow(0, 0, m);
+    out.t = t.narrow(0, 0, m);
+    out.dt = dt.narrow(0, 0, m);
+    out.sample_grad = out.sample_grad.narrow(0, 0, m);
+    out.sample_normals = out.sample_normals.narrow(0, 0, m);
   };
   // (field shapes without the fused kernels render op by op, as RenderForward does through Render(): the synchronous count)
   RenderFront fr = SampleAndFilter(rays_o, rays_d, bounds, Tensor(), /*async_count=*/fused);
   if (fr.empty) {  // RenderForward's empty result
     out.render = {fr.bg_color, torch::zeros({n_rays, 1}, DevF32()), torch::zeros({n_rays}, DevF32()), Tensor(),
                   torch::full({n_rays}, 512.f, DevF32()), Tensor(), Tensor()};
-    no_samples();
+    if (keep_samples) {  // (no rows of anything)
+      out.sample_grad = torch::empty({0, 3}, DevF32());
+      out.sample_normals = torch::empty({0, 3}, DevF32());
+    }
+    kept_samples(torch::empty({0, 3}, DevF32()), torch::empty({0, 3}, DevI32()), torch::empty({0}, DevF32()), torch::empty({0}, DevF32()), 0);
     return out;
   }
   SampleResultFlex& es = fr.es;
   const int n_cap = std::max(fr.n_kept, 1);
-  Tensor colors, disparity, depth, weights;
   int m = fr.n_kept;
-  Tensor g;  // df0/dw of the survivors [m,3]
-  auto hash_args_grad = [&](const Tensor& p, const Tensor& v, const Tensor& dx) {
-    F2N_CALL(f2n_hash_pos_grad(st, m, field->n_volumes_, VoidP(field->feat_pool_h_), I32P(field->prim_pool_), I32P(field->feat_local_idx_),
-                               I32P(field->feat_local_size_), F32P(field->bias_pool_), F32P(field->level_scale_), F32P(p), I32P(v), 1,
-                               F32P(dx), F32P(g)));
-  };
+  // the two routes differ in where the density pre-activations lie (sigma, its row stride) and in how rgb was made
+  Tensor sigma, rgb;
+  int sigma_stride = 1;
   if (fused) {
     TORCH_CHECK(field->prepass_x_.defined(), "no pre-pass feature cache for this query");
-    Tensor f0c = torch::empty({n_cap}, DevF32()), rgb = torch::empty({n_cap, 3}, DevF32());
+    sigma = torch::empty({n_cap}, DevF32());
+    rgb = torch::empty({n_cap, 3}, DevF32());
     const at::Half* cache = field->prepass_x_.data_ptr<at::Half>() + (int64_t) N_LEVELS * N_CHANNELS * fr.sample_cache_row;
     F2N_TIMED_CALL("field_shade_fwd", f2n_field_shade_fwd_dyn(st, fr.n_kept, I32P(fr.n_kept_dev), I32P(fr.src_rows),
                            static_cast<const void*>(cache), VoidP(field->mlp_->params_h_), F32P(es.dirs), nullptr, nullptr,
-                           VoidP(shader->mlp_->params_h_), F32P(f0c), nullptr, nullptr, F32P(rgb)));
-    colors = torch::empty({n_rays, 3}, DevF32());
-    disparity = torch::empty({n_rays}, DevF32());
-    depth = torch::empty({n_rays}, DevF32());
-    weights = torch::empty({n_cap}, DevF32());
-    Tensor bg = fr.bg_color.contiguous();
-    F2N_TIMED_CALL("composite_fwd", f2n_composite_fwd(st, n_rays, I32P(es.pts_idx_bounds), F32P(f0c), 1, F32P(es.dt), F32P(es.t), F32P(rgb),
-                               F32P(bg), F32P(colors), F32P(disparity), F32P(depth), F32P(weights), nullptr));
-    m = fr.n_kept_dev.item<int>();  // the read-back RenderForward avoids: everything above has been queued by now
-    TORCH_CHECK(m >= 0 && m <= fr.n_kept, "survivor count out of range");
-    g = torch::zeros({std::max(m, 1), 3}, DevF32());
-    if (m > 0) {
-      const int64_t row = (int64_t) N_LEVELS * N_CHANNELS;
-      Tensor cache_rows = field->prepass_x_.view({-1, row}).narrow(0, fr.sample_cache_row, field->prepass_x_.numel() / row - fr.sample_cache_row);
-      Tensor x = cache_rows.index_select(0, fr.src_rows.narrow(0, 0, m).to(torch::kInt64)).contiguous();
-      Tensor p = es.pts.narrow(0, 0, m).contiguous(), v = es.anchors.narrow(0, 0, m).select(1, 0).contiguous();
-      F2N_TIMED_CALL("field_density_grad", f2n_field_density_grad(st, m, field->n_volumes_, VoidP(field->feat_pool_h_), I32P(field->prim_pool_),
-                                      I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
-                                      F32P(field->level_scale_), F32P(p), I32P(v), 1, VoidP(field->mlp_->params_h_), VoidP(x), nullptr,
-                                      F32P(g)));
-    }
-    field->prepass_x_ = Tensor();  // (as RenderForward: the cache served its render)
+                           VoidP(shader->mlp_->params_h_), F32P(sigma), nullptr, nullptr, F32P(rgb)));
   } else {  // op by op, the launches of Render() in VALIDATE mode
     Tensor feat = field->AnchoredQueryReuse(fr.pts_all, fr.vol_all, fr.src_rows, m).slice(0, 0, m);
-    Tensor rgb = shader->QueryFromField(feat, es.dirs, torch::empty({0}, DevF32()), fr.sample_emb_idx, nullptr).contiguous();
-    feat = feat.contiguous();
-    colors = torch::empty({n_rays, 3}, DevF32());
-    disparity = torch::empty({n_rays}, DevF32());
-    depth = torch::empty({n_rays}, DevF32());
-    weights = torch::empty({n_cap}, DevF32());
-    Tensor bg = fr.bg_color.contiguous();
-    F2N_TIMED_CALL("composite_fwd", f2n_composite_fwd(st, n_rays, I32P(es.pts_idx_bounds), F32P(feat), F2N_MLP_OUT_PAD, F32P(es.dt), F32P(es.t),
-                               F32P(rgb), F32P(bg), F32P(colors), F32P(disparity), F32P(depth), F32P(weights), nullptr));
-    g = torch::zeros({std::max(m, 1), 3}, DevF32());
-    if (m > 0) {  // df0/dx from the general MLP backward (its h16 roundings), dy = e_0, no loss scale: as DensityGradChunk
-      auto& mlp = *field->mlp_;
-      Tensor p = es.pts.narrow(0, 0, m).contiguous(), v = es.anchors.narrow(0, 0, m).select(1, 0).contiguous();
-      Tensor x = field->HashEncode(p, v).to(torch::kFloat32).contiguous();
-      Tensor dy = torch::zeros({m, F2N_MLP_OUT_PAD}, DevF32());
-      dy.select(1, 0).fill_(1.f);
-      Tensor dparams = torch::zeros({mlp.n_params_}, DevF32()), dx = torch::empty({m, mlp.d_in_}, DevF32());
-      F2N_CALL(f2n_mlp_bwd(st, m, mlp.d_in_, mlp.d_hidden_, mlp.n_hidden_layers_, 1.f, VoidP(mlp.params_h_), F32P(x), F32P(dy),
-                           F32P(dparams), F32P(dx)));
-      hash_args_grad(p, v, dx);
-    }
+    rgb = shader->QueryFromField(feat, es.dirs, torch::empty({0}, DevF32()), fr.sample_emb_idx, nullptr).contiguous();
+    sigma = feat.contiguous();
+    sigma_stride = F2N_MLP_OUT_PAD;
   }
+  Tensor colors = torch::empty({n_rays, 3}, DevF32()), disparity = torch::empty({n_rays}, DevF32()), depth = torch::empty({n_rays}, DevF32());
+  Tensor weights = torch::empty({n_cap}, DevF32());
+  Tensor bg = fr.bg_color.contiguous();
+  F2N_TIMED_CALL("composite_fwd", f2n_composite_fwd(st, n_rays, I32P(es.pts_idx_bounds), F32P(sigma), sigma_stride, F32P(es.dt), F32P(es.t),
+                             F32P(rgb), F32P(bg), F32P(colors), F32P(disparity), F32P(depth), F32P(weights), nullptr));
+  if (fused) {
+    m = fr.n_kept_dev.item<int>();  // the read-back RenderForward avoids: everything above has been queued by now
+    TORCH_CHECK(m >= 0 && m <= fr.n_kept, "survivor count out of range");
+  }
+  Tensor g = torch::zeros({std::max(m, 1), 3}, DevF32());  // df0/dw of the survivors [m,3]
+  if (m > 0) {
+    Tensor x_h;  // fused: the survivors' rows of the pre-pass cache
+    if (fused) {
+      const int64_t row = (int64_t) N_LEVELS * N_CHANNELS;
+      Tensor cache_rows = field->prepass_x_.view({-1, row}).narrow(0, fr.sample_cache_row, field->prepass_x_.numel() / row - fr.sample_cache_row);
+      x_h = cache_rows.index_select(0, fr.src_rows.narrow(0, 0, m).to(torch::kInt64)).contiguous();
+    }
+    Tensor p = es.pts.narrow(0, 0, m).contiguous(), v = es.anchors.narrow(0, 0, m).select(1, 0).contiguous();
+    Df0Dw(field, p, v, x_h, g);
+  }
+  if (fused) field->prepass_x_ = Tensor();  // (as RenderForward: the cache served its render)
   out.render = {colors, es.first_oct_dis, disparity, Tensor(), depth, weights, es.pts_idx_bounds};
   Tensor dirs = torch::empty_like(rays_d);  // the unit directions the march walked along (the sampler's own normalisation)
   F2N_CALL(f2n_normalize_dirs(st, n_rays, F32P(rays_d), F32P(dirs)));
@@ -281,15 +295,8 @@ GeometryResult Renderer::RenderGeometry(const Tensor& rays_o_in, const Tensor& r
                                   I32P(anchors), VoidP(sampler->pers_octree_->pers_trans_gpu_), F32P(g), tau, F32P(out.opacity),
                                   F32P(out.normals), I32P(out.surf_idx), F32P(out.surf_t), F32P(out.surf_points), F32P(out.surf_normals),
                                   keep_samples ? F32P(out.sample_grad) : nullptr, keep_samples ? F32P(out.sample_normals) : nullptr));
-  if (keep_samples) {
-    out.render.weights = weights.narrow(0, 0, m);
-    out.pts = es.pts.narrow(0, 0, m);
-    out.anchors = es.anchors.narrow(0, 0, m);
-    out.t = es.t.narrow(0, 0, m);
-    out.dt = es.dt.narrow(0, 0, m);
-    out.sample_grad = out.sample_grad.narrow(0, 0, m);
-    out.sample_normals = out.sample_normals.narrow(0, 0, m);
-  }
+  if (keep_samples) out.render.weights = weights.narrow(0, 0, m);
+  kept_samples(es.pts, es.anchors, es.t, es.dt, m);
   return out;
 }
 
@@ -355,8 +362,7 @@ std::tuple<Tensor, Tensor> MeshFromGridImpl(const Tensor& grid, const Tensor& va
   else
     F2N_CALL(f2n_mesh_count(CurStream(), nx, ny, nz, F32P(gr), level, mask.data_ptr<uint8_t>(), I32P(vc), I32P(vse), I32P(fc), I32P(fse),
                             I32P(totals)));
-  Tensor t = totals.cpu();  // the two totals: the only read-back (they size the outputs)
-  const int64_t nv = t.data_ptr<int32_t>()[0], nf = t.data_ptr<int32_t>()[1];
+  const auto [nv, nf] = TwoTotals(totals);
   Tensor verts = torch::empty({nv, 3}, DevF32()), faces = torch::empty({nf, 3}, DevI32());
   if (nv > 0 || nf > 0)
     F2N_CALL(f2n_mesh_emit(CurStream(), nx, ny, nz, F32P(gr), level, lo, step, mask.data_ptr<uint8_t>(), I32P(vse), I32P(fse),
@@ -424,9 +430,8 @@ Tensor GridNormals(const Tensor& grid, const Tensor& pts, const float lo[3], flo
   Tensor gr = grid.to(torch::kCUDA, torch::kFloat32).contiguous();
   TORCH_CHECK(gr.dim() == 3 && gr.size(0) >= 2 && gr.size(1) >= 2 && gr.size(2) >= 2, "grid must be [nz, ny, nx] with at least 2 points per axis");
   TORCH_CHECK(gr.numel() <= INT32_MAX && step > 0.f, "grid too large or step not positive");
-  Tensor p = pts.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  Tensor p = Points3(pts);
   const int64_t n = p.size(0);
-  TORCH_CHECK(n <= INT32_MAX, "too many points");
   Tensor out = torch::empty({n, 3}, DevF32());
   F2N_CALL(f2n_grid_normals(CurStream(), (int) n, F32P(p), F32P(gr), (int) gr.size(2), (int) gr.size(1), (int) gr.size(0), lo, step,
                             F32P(out)));
@@ -444,18 +449,17 @@ Tensor MeshComponents(const Tensor& faces, int64_t n_verts, int* rounds) {
 
 std::tuple<Tensor, Tensor, Tensor> MeshFilterComponents(const Tensor& verts, const Tensor& faces, int min_faces) {
   torch::NoGradGuard g;
-  Tensor v = verts.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 3});
+  Tensor v = Points3(verts);
   Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
   const int64_t nv = v.size(0), nf = f.size(0);
-  TORCH_CHECK(nv <= INT32_MAX && nf <= INT32_MAX, "mesh too large");
+  TORCH_CHECK(nf <= INT32_MAX, "mesh too large");
   if (min_faces <= 1) return {v, f, torch::arange(nv, DevI32())};
   Tensor labels = MeshComponents(f, nv);
   Tensor comp = torch::empty({nv}, DevI32()), vkeep = torch::empty({nv}, DevI32()), vse = torch::empty({nv, 2}, DevI32());
   Tensor fkeep = torch::empty({nf}, DevI32()), fse = torch::empty({nf, 2}, DevI32()), totals = torch::empty({2}, DevI32());
   F2N_CALL(f2n_mesh_filter_count(CurStream(), (int) nv, (int) nf, I32P(f), I32P(labels), min_faces, I32P(comp), I32P(vkeep), I32P(vse),
                                  I32P(fkeep), I32P(fse), I32P(totals)));
-  Tensor t = totals.cpu();  // the two totals: they size the outputs
-  const int64_t kv = t.data_ptr<int32_t>()[0], kf = t.data_ptr<int32_t>()[1];
+  const auto [kv, kf] = TwoTotals(totals);
   Tensor ov = torch::empty({kv, 3}, DevF32()), src = torch::empty({kv}, DevI32()), of = torch::empty({kf, 3}, DevI32());
   if (kv > 0 || kf > 0)
     F2N_CALL(f2n_mesh_filter_emit(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), I32P(vkeep), I32P(vse), I32P(fkeep), I32P(fse),

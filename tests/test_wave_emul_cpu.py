@@ -881,6 +881,252 @@ def test_plain_bench_run_and_its_outputs_on_the_emulator(rt, monkeypatch, capsys
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# the world-space query drivers (csrc/host/RendererQuery.cpp) on the emulated host: the contracts Renderer.h documents and the GPU
+# modules check at scale (test_gpu_mesh / _mesh_attrs / _density_grad / _geometry), at the smallest sizes at which a driver can still go
+# wrong -- a few hundred points with empty ones among them, chunks with a ragged last one, an 11-point grid in four z-slabs, 24 camera
+# rays -- for the shipped field shape (the fused route) and for field.mlp_hidden_dim=32 (op by op).  Bit for bit unless stated.
+# ---------------------------------------------------------------------------------------------------------------------------------
+import test_gpu_geometry as ggeo  # noqa: E402
+import test_gpu_mesh as gmesh  # noqa: E402
+
+_QUERY_SHAPES = {"fused": [], "op_by_op": ["field.mlp_hidden_dim=32"]}
+_QUERY_BOX = ([-1.0, -0.8, -0.9], [1.0, 0.7, 1.05])
+_QUERY_RES = 10
+_query_runners = {}
+
+
+def _query_runner(rt, st, shape):
+    """(runner, arrays) on the fox state as the GPU modules' fox_runner builds it; built once per field shape (the queries leave it as
+    they found it: that is one of the contracts below)."""
+    if shape not in _query_runners:
+        runner, cfg, arrays = rt.make_runner(st, "wanjinyou", ["field.log2_table_size=14"] + _QUERY_SHAPES[shape], seed=1, table_init=0.3)
+        assert len(arrays[8]) == (32 * 64 + 16 * 64 if shape == "fused" else 32 * 32 + 16 * 32)
+        _query_runners[shape] = (runner, arrays)
+    return _query_runners[shape]
+
+
+def _qnp(t):
+    return t.detach().numpy().copy()
+
+
+def _bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and (np.ascontiguousarray(a).view(np.uint8) == np.ascontiguousarray(b).view(np.uint8)).all()
+
+
+def _query_points(n=300, seed=3):
+    rng = np.random.default_rng(seed)
+    pts = rng.uniform(-1.1, 1.1, (n, 3)).astype(np.float32)
+    d = rng.standard_normal((n, 3))
+    return pts, (d / np.sqrt((d ** 2).sum(1))[:, None]).astype(np.float32)
+
+
+def _view_dirs(normals):
+    flat = (normals == 0).all(1)
+    return np.where(flat[:, None], np.array([0.0, 0.0, -1.0], np.float32), -normals).astype(np.float32)
+
+
+@pytest.mark.parametrize("shape", list(_QUERY_SHAPES))
+def test_point_query_drivers_on_the_emulator(rt, fox_state, shape):
+    runner, _ = _query_runner(rt, fox_state, shape)
+    pts, dirs = _query_points()
+    n = len(pts)
+    pd, dd = torch.from_numpy(pts), torch.from_numpy(dirs)
+    dens = _qnp(runner.query_density(pd))
+    gd, grad = (_qnp(x) for x in runner.query_density_grad(pd))
+    rd, rgb = (_qnp(x) for x in runner.query_radiance(pd, dd))
+    nrm = _qnp(runner.field_normals(pd))
+    assert dens.shape == (n,) and grad.shape == (n, 3) and rgb.shape == (n, 3) and nrm.shape == (n, 3)
+    assert all(a.dtype == np.float32 for a in (dens, gd, grad, rd, rgb, nrm))
+    assert _bits(gd, dens) and _bits(rd, dens)  # one density, whichever driver computed it
+    empty = _qnp(runner.locate_points(pd)[1])[:, 0] < 0
+    assert 0 < empty.sum() < n  # both kinds of points
+    assert (dens[empty] == 0).all() and (grad[empty] == 0).all() and (rgb[empty] == 0).all() and (nrm[empty] == 0).all()
+    assert (dens[~empty] > 0).all() and (np.ptp(grad, axis=0) > 0).all() and np.ptp(rgb[~empty]) > 0
+    # a second call: the same bits
+    assert _bits(_qnp(runner.query_density(pd)), dens) and _bits(_qnp(runner.field_normals(pd)), nrm)
+    assert all(_bits(_qnp(a), b) for a, b in zip(runner.query_density_grad(pd), (dens, grad)))
+    assert all(_bits(_qnp(a), b) for a, b in zip(runner.query_radiance(pd, dd), (dens, rgb)))
+    # several chunks with a ragged last one: the single chunk's results
+    assert runner.density_slab_points > n
+    runner.density_slab_points = 128
+    try:
+        assert all(_bits(_qnp(a), b) for a, b in zip(runner.query_density_grad(pd), (dens, grad)))
+        assert _bits(_qnp(runner.field_normals(pd)), nrm)
+    finally:
+        runner.density_slab_points = 1 << 22
+    # field_normals: -grad / |grad| (the bar of test_gpu_density_grad.py::test_query_density_grad_on_the_fox), zero where the gradient is
+    ln = np.sqrt((grad.astype(np.float64) ** 2).sum(1))
+    assert (nrm[ln == 0] == 0).all()
+    mid = (ln > 1e-18) & (ln < 1e18)  # (outside, the float32 length under- or overflows: the kernel's to judge)
+    assert mid.sum() > 100 and np.abs(nrm[mid] + grad[mid] / ln[mid, None]).max() < 1e-5
+    # all points empty, and no points
+    far, none = torch.full((7, 3), 1000.0), torch.zeros((0, 3))
+    for out, shapes in ((runner.query_density(far), [(7,)]), (runner.query_density_grad(far), [(7,), (7, 3)]),
+                        (runner.query_radiance(far, dd[:7].contiguous()), [(7,), (7, 3)]), (runner.field_normals(far), [(7, 3)]),
+                        (runner.query_density(none), [(0,)]), (runner.query_density_grad(none), [(0,), (0, 3)]),
+                        (runner.query_radiance(none, none), [(0,), (0, 3)]), (runner.field_normals(none), [(0, 3)])):
+        out = out if isinstance(out, (list, tuple)) else [out]
+        assert [tuple(o.shape) for o in out] == shapes and all(o.dtype == torch.float32 and (o == 0).all() for o in out)
+    w0, a0 = runner.locate_points(none)
+    assert tuple(w0.shape) == (0, 3) and tuple(a0.shape) == (0, 3)
+
+
+@pytest.mark.parametrize("shape", list(_QUERY_SHAPES))
+def test_density_grid_and_mesh_attribute_drivers_on_the_emulator(rt, fox_state, shape):
+    runner, _ = _query_runner(rt, fox_state, shape)
+    h = rt.host()
+    lo, hi = _QUERY_BOX
+    res = _QUERY_RES
+    world, (nz, ny, nx) = gmesh._grid_world(rt, lo, hi, res)
+    step = h.grid_spec(lo, hi, res)[0]
+    point_dens = _qnp(runner.query_density(torch.from_numpy(world))).reshape(nz, ny, nx)
+    assert (point_dens == 0).any() and (point_dens > 0).any() and max(nz, ny, nx) == res + 1
+    whole = runner.density_grid(lo, hi, res)
+    runner.density_slab_points = 3 * nx * ny
+    try:
+        assert -(-nz // 3) >= 3  # at least three z-slabs
+        slabs = _qnp(runner.density_grid(lo, hi, res))
+    finally:
+        runner.density_slab_points = 1 << 22
+    assert _bits(slabs, point_dens) and _bits(_qnp(whole), point_dens)
+    level = float(np.quantile(point_dens[point_dens > 0], 0.5))  # a level the scene crosses
+    v, f = runner.extract_mesh(lo, hi, res, level)
+    kv, kf, ksrc = h.mesh_filter_components(v, f, 2)
+    assert len(kf) > 0 and _bits(_qnp(kv), _qnp(v)[_qnp(ksrc)])
+    grid_n = _qnp(h.grid_normals(whole, kv, lo, step))
+    field_n = _qnp(runner.field_normals(kv))
+    zero = (field_n == 0).all(1)
+    for source in ("grid", "field"):
+        m = {k: _qnp(x) for k, x in runner.extract_mesh_attrs(lo, hi, res, level, 2, True, True, source).items()}
+        assert sorted(m) == ["colors", "faces", "normals", "verts"]
+        assert _bits(m["verts"], _qnp(kv)) and _bits(m["faces"], _qnp(kf))
+        if source == "grid":
+            assert _bits(m["normals"], grid_n)
+        else:
+            assert _bits(m["normals"][~zero], field_n[~zero]) and _bits(m["normals"][zero], grid_n[zero]) and (~zero).any()
+        assert _bits(m["colors"], _qnp(runner.query_radiance(kv, torch.from_numpy(_view_dirs(m["normals"])))[1]))
+    assert sorted(runner.extract_mesh_attrs(lo, hi, res, level, 2, False, False)) == ["faces", "verts"]
+    with pytest.raises(RuntimeError):
+        runner.extract_mesh_attrs(lo, hi, res, level, normal_source="mesh")
+    # a box the scene does not reach: an empty grid, an empty mesh with empty attributes
+    far_lo, far_hi = [1000.0, 1000.0, 1000.0], [1001.0, 1001.0, 1001.0]
+    assert (runner.density_grid(far_lo, far_hi, 3) == 0).all()
+    m = runner.extract_mesh_attrs(far_lo, far_hi, 3, level, 2, True, True, "field")
+    assert [tuple(m[k].shape) for k in ("verts", "faces", "normals", "colors")] == [(0, 3)] * 4
+
+
+def _df0_dw_of_the_samples(capi, arrays, pts, anchors, fused):
+    """df0/dw [M,3] at the warped points a render returned, from the entry points the driver calls, called directly: the pre-pass's own
+    features and f2n_field_density_grad (fused), or f2n_hash_fwd -> f2n_mlp_bwd (dy = e_0, loss scale 1) -> f2n_hash_pos_grad."""
+    from oracle import capi as oc, pipeline as op
+    grid = op.HashGrid(arrays[4], arrays[5], arrays[6], int(arrays[7][0]), 14)
+    T = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt))
+    params = np.asarray(arrays[8], np.float32)
+    M = len(pts)
+    table = (M, grid.n_volumes, T(grid.table_h.view(np.float16), np.float16), T(grid.prim_pool, np.int32), T(grid.local_idx, np.int32),
+             T(grid.local_size, np.int32), T(grid.bias_pool, np.float32), T(grid.scales, np.float32), T(pts, np.float32))
+    vol, ph = T(anchors[:, 0], np.int32), T(oc.f2h(params).view(np.float16), np.float16)
+    x_h, g = torch.empty((M, 32), dtype=torch.float16), torch.full((M, 3), float("nan"))
+    if fused:
+        capi.field_fwd(*table, vol, 1, ph, None, torch.empty(M), x_h)
+        capi.field_density_grad(*table, vol, 1, ph, x_h, None, g)
+    else:
+        capi.hash_fwd(*table, 1, vol, 1, x_h)
+        d_hidden = len(params) // (32 + 16)  # (32 -> d_hidden -> 16)
+        dy = torch.zeros((M, 16))
+        dy[:, 0] = 1.0
+        dx = torch.empty((M, 32))
+        capi.mlp_bwd(M, 32, d_hidden, 1, 1.0, ph, x_h.float().contiguous(), dy, torch.zeros(len(params)), dx)
+        capi.hash_pos_grad(*table, vol, 1, dx, g)
+    return g.numpy()
+
+
+@pytest.mark.parametrize("shape", list(_QUERY_SHAPES))
+def test_render_geometry_driver_on_the_emulator(rt, hip, fox_state, shape):
+    from oracle import capi as oc
+    import geometry_ref as gr
+    st = fox_state
+    runner, arrays = _query_runner(rt, st, shape)
+    n_rays = 24
+    ro, rd, bounds = ggeo._camera_rays(st, int(st["train_set"][0]), n_rays)
+    d = rt.to_dev(ro, rd, bounds)
+    base = [_qnp(x) for x in runner.render_rays(*d)]  # colors, disparity, first_oct_dis, depth
+    g = {k: _qnp(x) for k, x in runner.render_geometry(*d, return_samples=True).items()}
+    assert sorted(g) == sorted(["colors", "disparity", "depth", "opacity", "normals", "surf_idx", "surf_t", "surf_points", "surf_normals", "pts", "anchors",
+                                "t", "dt", "weights", "idx_start_end", "sample_grad", "sample_normals"])
+    assert _bits(g["colors"], base[0]) and _bits(g["disparity"], base[1]) and _bits(g["depth"], base[3])
+    plain = {k: _qnp(x) for k, x in runner.render_geometry(*d).items()}
+    assert sorted(plain) == sorted(["colors", "disparity", "depth", "opacity", "normals", "surf_idx", "surf_t", "surf_points", "surf_normals"])
+    assert all(_bits(x, g[k]) for k, x in plain.items())  # keeping the samples changes nothing; a second call gives the same bits
+    se, M = g["idx_start_end"], len(g["t"])
+    assert se.shape == (n_rays, 2) and se[-1, 1] == M and M > 0 and (se[:, 1] > se[:, 0]).any()
+    assert g["pts"].shape == (M, 3) and g["anchors"].shape == (M, 3) and g["weights"].shape == (M,) and g["dt"].shape == (M,)
+    # the kept samples' gradient and normals, and the per-ray buffers: f2n_composite_geometry fed the returned samples and the df0/dw
+    # the driver's entry points give at the returned warped points
+    c = dict(se=se, weights=g["weights"], t=g["t"], rays_o=ro, rays_d=oc.normalize_dirs(rd), anchors=g["anchors"], transes=st["pers_trans"],
+             df0_dw=_df0_dw_of_the_samples(hip, arrays, g["pts"], g["anchors"], shape == "fused"), tau=0.5)
+    direct = ggeo.device_geometry(c)
+    assert (np.abs(g["sample_grad"]).max(0) > 0).all()
+    for k in ("sample_grad", "sample_normals", "surf_idx") + ggeo.PER_RAY:
+        assert gr.same_bits(g[k], direct[k]), k
+    ref = gr.ray_buffers(se, g["weights"], g["t"], ro, c["rays_d"], g["sample_normals"], 0.5)
+    assert (g["surf_idx"] == ref["surf_idx"]).all() and all(gr.same_bits(g[k], ref[k]) for k in ggeo.PER_RAY)
+    # rays that miss the scene: render_rays' empty result, zeros and -1
+    far, away, b5 = torch.full((5, 3), 1.0e4), torch.tensor([[1.0, 0.0, 0.0]]).repeat(5, 1), d[2][:5].contiguous()
+    e = {k: _qnp(x) for k, x in runner.render_geometry(far, away, b5, return_samples=True).items()}
+    b = [_qnp(x) for x in runner.render_rays(far, away, b5)]
+    assert _bits(e["colors"], b[0]) and _bits(e["disparity"], b[1]) and _bits(e["depth"], b[3])
+    assert (e["surf_idx"] == -1).all() and all((e[k] == 0).all() for k in ggeo.PER_RAY)
+    assert [e[k].shape for k in ("pts", "anchors", "t", "dt", "weights", "sample_grad", "sample_normals", "idx_start_end")] == \
+        [(0, 3), (0, 3), (0,), (0,), (0,), (0, 3), (0, 3), (5, 2)]
+    with pytest.raises(RuntimeError):
+        runner.render_geometry(*d, tau=0.0)
+
+
+def test_queries_have_no_effect_on_a_training_step_in_flight_on_the_emulator(rt, fox_state):
+    """Streaming steps with the next batch handed over (sampled ahead), every query entry point between two of them (each flushes the
+    step in flight, as the GPU modules' *_has_no_effect_on_training tests have it), then the remaining steps: losses and every state
+    tensor equal those of the run without the queries."""
+    import test_gpu_e2e as e2e
+    st = fox_state
+    rng = np.random.default_rng(5)
+    R, STEPS = 24, 3
+    batches = []
+    for _ in range(STEPS + 1):
+        ro, rd, bounds, cam = e2e.fox_batch(st, rng, R)
+        batches.append([torch.from_numpy(np.ascontiguousarray(a)) for a in (ro, rd, bounds, rng.random((R, 3), dtype=np.float32), cam)])
+    pts, dirs = _query_points(100, 7)
+    pd, dd = torch.from_numpy(pts), torch.from_numpy(dirs)
+    view = rt.to_dev(*ggeo._camera_rays(st, int(st["train_set"][1]), 8))
+    lo, hi = _QUERY_BOX
+
+    def run(query):
+        runner, cfg, _ = rt.make_runner(st, "wanjinyou", ["field.log2_table_size=12"], seed=3, table_init=0.3)
+        runner.n_edge_pts = 64
+        torch.manual_seed(11)
+        losses = []
+        for k in range(STEPS):
+            if query and k == 1:
+                assert (runner.query_density(pd) > 0).any() and (runner.query_density_grad(pd)[1] != 0).any()
+                assert (runner.query_radiance(pd, dd)[1] != 0).any() and (runner.field_normals(pd) != 0).any()
+                g = runner.density_grid(lo, hi, 6).numpy()
+                level = float(np.quantile(g[g > 0], 0.5))
+                for source in ("grid", "field"):
+                    assert len(runner.extract_mesh_attrs(lo, hi, 6, level, 2, True, True, source)["faces"]) > 0
+                assert len(runner.render_geometry(*view, return_samples=True)["t"]) > 0
+            b, nb = batches[k], batches[k + 1]
+            s = runner.train_step(b[0], b[1], b[2], b[3], b[4], True, nb[0], nb[1], nb[2])
+            losses.append((float(s["loss"]), float(s["mse"])))
+        runner.flush()
+        return losses, [t.detach().numpy().copy() for t in runner.states()], dict(runner.counters())
+
+    l0, s0, c0 = run(False)
+    l1, s1, c1 = run(True)
+    assert l0 == l1 and c0 == c1 and all(np.isfinite(v) for pair in l0 for v in pair)
+    assert len(s0) == len(s1) and all(_bits(a, b) for a, b in zip(s0, s1))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # SURVEY 8(e) without hardware: a data-parallel training of TWO ranks -- two processes, each the emulated host on the emulated
 # kernels, attached through DataParallel::Attach (csrc/host/DataParallel.cpp as it stands) over a shared-memory <rccl/rccl.h> -- the
 # program bench.py --gpus 2 runs: replicas built from different seeds, rank 0's state broadcast at the attach, per-rank ray batches,
