@@ -36,7 +36,7 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-_DT = {"f32": torch.float32, "i32": torch.int32, "u8": torch.uint8, "h16": torch.float16}
+_DT = {"f32": torch.float32, "i32": torch.int32, "i64": torch.int64, "u8": torch.uint8, "h16": torch.float16}
 
 
 def _p(t, kind=None, allow_none=False):
@@ -868,6 +868,78 @@ def mesh_filter_components(verts, faces, min_faces):
                                        _p(vse, "i32"), _p(fkeep, "i32", nf == 0), _p(fse, "i32", nf == 0), _p(ov, "f32", kv == 0),
                                        _p(src, "i32", kv == 0), _p(of, "i32", kf == 0)), "f2n_mesh_filter_emit")
     return ov, of, src
+
+
+def mesh_simplify(verts, faces, cell, lo=None, lam=1e-3):
+    """Vertex clustering with quadric-error placement (f2n_mesh_cluster_keys -> sorted unique -> f2n_mesh_cluster_accumulate ->
+    f2n_mesh_cluster_place -> f2n_mesh_cluster_faces -> unique rows -> f2n_mesh_filter_count / _emit): (verts, faces, vert_map [V] int32,
+    the output vertex of every input vertex or -1).  lo None: the minimum of the finite coordinates.  The sorted uniques are
+    torch ops (plumbing); reads back three scalars and the two totals."""
+    import numpy as np
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    dev = verts.device
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    f32 = np.float32
+    cell = float(f32(cell))
+    lo3 = [f32(0.0)] * 3 if lo is None else [f32(x) for x in lo]
+    dims = [1, 1, 1]
+    if nv > 0 and cell > 0.0 and cell < float("inf"):
+        fin = torch.isfinite(verts)  # (per coordinate, over its finite values)
+        lows, highs = torch.where(fin, verts, verts.new_full((1,), float("inf"))), torch.where(fin, verts, verts.new_full((1,), float("-inf")))
+        box = torch.stack([lows[:, k].min() for k in range(3)] + [highs[:, k].max() for k in range(3)]).cpu().numpy()
+        mn, mx = box[:3], box[3:]
+        for k in range(3):
+            if mn[k] <= mx[k]:  # (the coordinate has a finite value)
+                if lo is None:
+                    lo3[k] = mn[k]
+                with np.errstate(all="ignore"):
+                    u = f32(f32(mx[k] - lo3[k]) / f32(cell))  # (two fp32 roundings, as the keys' u)
+                if u >= 1048575.0:
+                    raise F2nError("cell %g is too small for the extent of the mesh (at most 2^20 cells per axis)" % cell)
+                dims[k] = int(np.floor(u)) + 1 if u >= 0 else 1
+    lo_c, dims_c = _lo3(lo3), (ctypes.c_int32 * 3)(*dims)
+    keys = torch.empty(nv, dtype=torch.int64, device=dev)
+    _ck(lib().f2n_mesh_cluster_keys(_stream(), _i(nv), _p(verts, "f32", nv == 0), lo_c, _f(cell), dims_c, _p(keys, "i64", nv == 0)),
+        "f2n_mesh_cluster_keys")
+    uk, inv = torch.unique(keys, sorted=True, return_inverse=True)
+    bad = 1 if len(uk) > 0 and int(uk[0]) < 0 else 0  # key -1 sorts first
+    ckeys = uk[bad:].contiguous()
+    cluster_of = (inv - bad).to(torch.int32).contiguous()
+    nc = int(ckeys.shape[0])
+    none_v, none_f = torch.empty((0, 3), dtype=torch.float32, device=dev), i32(0, 3)
+    vert_map = torch.full((nv,), -1, dtype=torch.int32, device=dev)
+    if nc == 0:
+        return none_v, none_f, vert_map
+    acc = torch.zeros((nc, 16), dtype=torch.int64, device=dev)
+    _ck(lib().f2n_mesh_cluster_accumulate(_stream(), _i(nv), _i(nf), _p(verts, "f32"), _p(faces, "i32", nf == 0), _p(cluster_of, "i32"),
+                                          _i(nc), lo_c, _f(cell), dims_c, _p(acc, "i64"), _p(i32(1), "i32")), "f2n_mesh_cluster_accumulate")
+    cverts = torch.empty((nc, 3), dtype=torch.float32, device=dev)
+    _ck(lib().f2n_mesh_cluster_place(_stream(), _i(nc), _p(acc, "i64"), _p(ckeys, "i64"), lo_c, _f(cell), dims_c, _d(lam),
+                                     _p(cverts, "f32")), "f2n_mesh_cluster_place")
+    if nf == 0:
+        return none_v, none_f, vert_map
+    rows = i32(nf, 3)
+    _ck(lib().f2n_mesh_cluster_faces(_stream(), _i(nv), _i(nf), _p(faces, "i32"), _p(cluster_of, "i32"), _p(rows, "i32")),
+        "f2n_mesh_cluster_faces")
+    uf = torch.unique(rows, sorted=True, dim=0)
+    if len(uf) > 0 and int(uf[0, 0]) < 0:  # the dropped faces' row sorts first
+        uf = uf[1:]
+    uf = uf.contiguous()
+    kf0 = int(uf.shape[0])
+    if kf0 == 0:
+        return none_v, none_f, vert_map
+    # the clusters no face uses leave, order kept: the component filter with one label and a threshold every face passes
+    labels = torch.zeros(nc, dtype=torch.int32, device=dev)
+    comp, vkeep, vse, fkeep, fse, totals = i32(nc), i32(nc), i32(nc, 2), i32(kf0), i32(kf0, 2), i32(2)
+    _ck(lib().f2n_mesh_filter_count(_stream(), _i(nc), _i(kf0), _p(uf, "i32"), _p(labels, "i32"), _i(1), _p(comp, "i32"), _p(vkeep, "i32"),
+                                    _p(vse, "i32"), _p(fkeep, "i32"), _p(fse, "i32"), _p(totals, "i32")), "f2n_mesh_filter_count")
+    kv, kf = (int(v) for v in totals.cpu())
+    ov, src, of = torch.empty((kv, 3), dtype=torch.float32, device=dev), i32(kv), i32(kf, 3)
+    _ck(lib().f2n_mesh_filter_emit(_stream(), _i(nc), _i(kf0), _p(cverts, "f32"), _p(uf, "i32"), _p(vkeep, "i32"), _p(vse, "i32"),
+                                   _p(fkeep, "i32"), _p(fse, "i32"), _p(ov, "f32"), _p(src, "i32"), _p(of, "i32")), "f2n_mesh_filter_emit")
+    new_of_cluster = torch.where(vkeep != 0, vse[:, 0], torch.full_like(vkeep, -1))
+    vert_map = torch.where(cluster_of >= 0, new_of_cluster[cluster_of.clamp_min(0).long()], vert_map).contiguous()
+    return ov, of, vert_map
 
 
 # ---------------------------------------------------------------- TSDF fusion of depth maps

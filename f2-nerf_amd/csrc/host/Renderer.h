@@ -88,9 +88,14 @@ Tensor MeshComponents(const Tensor& faces, int64_t n_verts, int* rounds = nullpt
 // The mesh without the components of fewer than min_faces faces, order kept (f2n_mesh_filter_count / _emit): (verts, faces re-indexed,
 // vert_src [V'] int32 = the original index of every kept vertex).  min_faces <= 1: the input itself and the identity.
 std::tuple<Tensor, Tensor, Tensor> MeshFilterComponents(const Tensor& verts, const Tensor& faces, int min_faces);
+// Vertex clustering with quadric-error placement on the grid of origin lo (NULL: the minimum of the finite coordinates) and cell size
+// `cell` (f2n_mesh_cluster_*): (verts, faces, vert_map [V] int32 = the output vertex of every input vertex or -1).  One output
+// vertex per occupied cell, collapsed faces dropped, duplicates merged, faces sorted; lambda ties a vertex to its cluster's mean.
+std::tuple<Tensor, Tensor, Tensor> MeshSimplify(const Tensor& verts, const Tensor& faces, float cell, const float* lo, double lambda);
 
 struct MeshAttrs {  // Renderer::ExtractMeshAttrs; normals / colors are undefined unless asked for
   Tensor verts, faces, normals, colors;
+  int64_t verts_in = -1, faces_in = -1;  // simplify >= 2: the size of the mesh that went into MeshSimplify
 };
 
 // Renderer::RenderGeometry: RenderForward's result and the geometry buffers of f2n_composite_geometry
@@ -324,7 +329,7 @@ class Renderer : public Pipe {
   // normal_source "field": the normals are FieldNormals at the kept vertices (a vertex whose field normal is the zero vector takes
   // its grid normal) and the colours follow them; "grid" (the default): the density grid's normals
   MeshAttrs ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
-                             bool normals, bool colors, const std::string& normal_source = "grid");
+                             bool normals, bool colors, const std::string& normal_source = "grid", int simplify = 0);
   // (density [n], grad [n,3]) at world points: the density of QueryDensity, bit for bit, and its analytic gradient with respect to the
   // world position, sigma J^T df0/dw (f2n_field_density_grad / f2n_density_grad_scatter: the hash table's trilinear blend, the
   // density MLP and the leaf's warp differentiated exactly, fp32); zeros where no listed leaf holds the point.  Field shapes

@@ -6,6 +6,7 @@
 // PrepassCacheGuard (the cache contract on every exit path), Df0Dw (df0/dw of rows, fused or op by op), TwoTotals.  A point query
 // is: locate, rows, its own field calls under the guard, its own scatter kernel.
 #include <cmath>
+#include <limits>
 
 #include "Renderer.h"
 
@@ -467,8 +468,99 @@ std::tuple<Tensor, Tensor, Tensor> MeshFilterComponents(const Tensor& verts, con
   return {ov, of, src};
 }
 
+namespace {
+// a stretch of MeshSimplify between two kernels (sorted uniques, selections: torch ops) under a name of its own in the kernel timers
+struct TimedSpan {
+  const char* name;
+  explicit TimedSpan(const char* n) : name(n) { KernelTimers::Get().Begin(name); }
+  ~TimedSpan() { KernelTimers::Get().End(name); }
+};
+}  // namespace
+
+std::tuple<Tensor, Tensor, Tensor> MeshSimplify(const Tensor& verts, const Tensor& faces, float cell, const float* lo_in, double lambda) {
+  torch::NoGradGuard g;
+  Tensor v = Points3(verts);
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  const int64_t nv = v.size(0), nf = f.size(0);
+  TORCH_CHECK(nf <= INT32_MAX, "mesh too large");
+  float lo[3] = {0.f, 0.f, 0.f};
+  int32_t dims[3] = {1, 1, 1};
+  if (lo_in != nullptr)
+    for (int k = 0; k < 3; k++) lo[k] = lo_in[k];
+  Tensor keys = torch::empty({nv}, DevI32().dtype(torch::kInt64));
+  Tensor none_v = torch::empty({0, 3}, DevF32()), none_f = torch::empty({0, 3}, DevI32());
+  if (nv > 0 && cell > 0.f && std::isfinite(cell)) {  // (any other cell: the kernels' own F2N_ERR_INVALID_ARG below)
+    // the bounding box of the vertices' finite coordinates gives lo (unless given) and dims; the keys' clamp then only guards the upper border
+    TimedSpan span("mesh_simplify_bounds");
+    // (per coordinate, over its finite values; three full reductions over a column each -- a reduction of [V,3] over V is slow)
+    Tensor fin = torch::isfinite(v);
+    const float inf = std::numeric_limits<float>::infinity();
+    Tensor lows = torch::where(fin, v, torch::full({1}, inf, DevF32())), highs = torch::where(fin, v, torch::full({1}, -inf, DevF32()));
+    std::vector<Tensor> ends;
+    for (int k = 0; k < 3; k++) ends.push_back(lows.select(1, k).min());
+    for (int k = 0; k < 3; k++) ends.push_back(highs.select(1, k).max());
+    Tensor box = torch::stack(ends).cpu();
+    const float *mn = box.data_ptr<float>(), *mx = mn + 3;
+    for (int k = 0; k < 3; k++) {
+      if (mn[k] <= mx[k]) {  // (the coordinate has a finite value)
+        if (lo_in == nullptr) lo[k] = mn[k];
+        const float u = (mx[k] - lo[k]) / cell;  // (two fp32 roundings, as the keys' u)
+        TORCH_CHECK(!(u >= 1048575.f), "cell ", cell, " is too small for the extent of the mesh (at most 2^20 cells per axis)");
+        dims[k] = u >= 0.f ? (int) std::floor(u) + 1 : 1;
+      }
+    }
+  }
+  F2N_TIMED_CALL("mesh_cluster_keys", f2n_mesh_cluster_keys(CurStream(), (int) nv, F32P(v), lo, cell, dims, keys.data_ptr<int64_t>()));
+  Tensor cluster_of, ckeys;
+  int64_t nc = 0;
+  {
+    TimedSpan span("mesh_simplify_unique_keys");
+    auto uq = at::_unique2(keys, /*sorted=*/true, /*return_inverse=*/true);
+    const Tensor& uk = std::get<0>(uq);
+    const int64_t bad = uk.size(0) > 0 && uk[0].item<int64_t>() < 0 ? 1 : 0;  // key -1 sorts first
+    ckeys = uk.narrow(0, bad, uk.size(0) - bad).contiguous();
+    cluster_of = (std::get<1>(uq) - bad).to(torch::kInt32).contiguous();
+    nc = ckeys.size(0);
+  }
+  TORCH_CHECK(nc <= INT32_MAX, "mesh too large");
+  Tensor vert_map = torch::full({nv}, -1, DevI32());
+  if (nc == 0) return {none_v, none_f, vert_map};
+  Tensor acc = torch::zeros({nc, 16}, DevI32().dtype(torch::kInt64)), flag = torch::empty({1}, DevI32());
+  F2N_TIMED_CALL("mesh_cluster_accumulate",
+                 f2n_mesh_cluster_accumulate(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), I32P(cluster_of), (int) nc, lo, cell, dims,
+                                             acc.data_ptr<int64_t>(), I32P(flag)));
+  Tensor cverts = torch::empty({nc, 3}, DevF32());
+  F2N_TIMED_CALL("mesh_cluster_place", f2n_mesh_cluster_place(CurStream(), (int) nc, acc.data_ptr<int64_t>(), ckeys.data_ptr<int64_t>(), lo,
+                                                              cell, dims, lambda, F32P(cverts)));
+  if (nf == 0) return {none_v, none_f, vert_map};
+  Tensor rows = torch::empty({nf, 3}, DevI32());
+  F2N_TIMED_CALL("mesh_cluster_faces", f2n_mesh_cluster_faces(CurStream(), (int) nv, (int) nf, I32P(f), I32P(cluster_of), I32P(rows)));
+  Tensor uf;
+  {
+    TimedSpan span("mesh_simplify_unique_faces");
+    uf = std::get<0>(at::unique_dim(rows, 0, /*sorted=*/true));
+    if (uf.size(0) > 0 && uf[0][0].item<int>() < 0) uf = uf.narrow(0, 1, uf.size(0) - 1);  // the dropped faces' row sorts first
+    uf = uf.contiguous();
+  }
+  const int64_t kf0 = uf.size(0);
+  if (kf0 == 0) return {none_v, none_f, vert_map};
+  // the clusters no face uses leave, order kept: the component filter with one label and a threshold every face passes
+  Tensor labels = torch::zeros({nc}, DevI32());
+  Tensor comp = torch::empty({nc}, DevI32()), vkeep = torch::empty({nc}, DevI32()), vse = torch::empty({nc, 2}, DevI32());
+  Tensor fkeep = torch::empty({kf0}, DevI32()), fse = torch::empty({kf0, 2}, DevI32()), totals = torch::empty({2}, DevI32());
+  F2N_TIMED_CALL("mesh_simplify_compact", f2n_mesh_filter_count(CurStream(), (int) nc, (int) kf0, I32P(uf), I32P(labels), 1, I32P(comp),
+                                                                I32P(vkeep), I32P(vse), I32P(fkeep), I32P(fse), I32P(totals)));
+  const auto [kv, kf] = TwoTotals(totals);
+  Tensor ov = torch::empty({kv, 3}, DevF32()), src = torch::empty({kv}, DevI32()), of = torch::empty({kf, 3}, DevI32());
+  F2N_TIMED_CALL("mesh_simplify_compact", f2n_mesh_filter_emit(CurStream(), (int) nc, (int) kf0, F32P(cverts), I32P(uf), I32P(vkeep), I32P(vse),
+                                                               I32P(fkeep), I32P(fse), F32P(ov), I32P(src), I32P(of)));
+  Tensor new_of_cluster = torch::where(vkeep != 0, vse.select(1, 0), torch::full({1}, -1, DevI32()));
+  vert_map = torch::where(cluster_of >= 0, new_of_cluster.index_select(0, cluster_of.clamp_min(0).to(torch::kInt64)), vert_map).contiguous();
+  return {ov, of, vert_map};
+}
+
 MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level,
-                                     int min_component_faces, bool normals, bool colors, const std::string& normal_source) {
+                                     int min_component_faces, bool normals, bool colors, const std::string& normal_source, int simplify) {
   torch::NoGradGuard g;
   const bool from_field = normal_source == "field";
   TORCH_CHECK(from_field || normal_source == "grid", "normal_source must be \"grid\" or \"field\", got \"", normal_source, "\"");
@@ -480,6 +572,13 @@ MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::ve
     auto kept = MeshFilterComponents(out.verts, out.faces, min_component_faces);
     out.verts = std::get<0>(kept);
     out.faces = std::get<1>(kept);
+  }
+  if (simplify >= 2) {  // clusters of simplify^3 grid cells; the attributes below are computed at the new vertices
+    out.verts_in = out.verts.size(0);
+    out.faces_in = out.faces.size(0);
+    auto simple = MeshSimplify(out.verts, out.faces, (float) simplify * s.step, s.lo, 1e-3);
+    out.verts = std::get<0>(simple);
+    out.faces = std::get<1>(simple);
   }
   if (!normals && !colors) return out;
   Tensor nrm = GridNormals(grid, out.verts, s.lo, s.step);

@@ -160,6 +160,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::vector<Tensor>{std::get<0>(t), std::get<1>(t), std::get<2>(t)};
         },
         py::arg("verts"), py::arg("faces"), py::arg("min_faces"));
+  // vertex clustering with quadric-error placement on cells of size `cell` from `lo` (None: the vertices' bounding-box minimum):
+  // [verts, faces, vert_map] (f2n_mesh_cluster_*); lam ties a vertex to its cluster's mean where the planes leave it free
+  m.def("mesh_simplify",
+        [](const Tensor& verts, const Tensor& faces, float cell, const c10::optional<std::vector<float>>& lo, double lam) {
+          TORCH_CHECK(!lo.has_value() || lo->size() == 3, "lo must have three coordinates");
+          auto t = MeshSimplify(verts, faces, cell, lo.has_value() ? lo->data() : nullptr, lam);
+          return std::vector<Tensor>{std::get<0>(t), std::get<1>(t), std::get<2>(t)};
+        },
+        py::arg("verts"), py::arg("faces"), py::arg("cell"), py::arg("lo") = py::none(), py::arg("lam") = 1e-3);
   m.def("dp_set_table_buckets", [](int n) { DataParallel::table_buckets = n; });  // table all-reduce buckets of the next attach (A/B)
   // data-parallel replicas draw stream `rank` of every keyed purpose (KeyedDraws.h; the native attach sets it itself)
   m.def("dp_set_replica", [](int rank) { KeyedUniforms::SetReplica(rank); });
@@ -350,22 +359,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("world"), py::arg("dirs"))
       .def("extract_mesh_attrs",  // extract_mesh + floater removal, normals from the density grid, colours along the inward normal
            [](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
-              bool normals, bool colors, const std::string& normal_source) {
+              bool normals, bool colors, const std::string& normal_source, int simplify) {
              MeshAttrs a;
              {
                py::gil_scoped_release no_gil;
                r.FinishPending();
-               a = r.renderer_->ExtractMeshAttrs(lo, hi, res, level, min_component_faces, normals, colors, normal_source);
+               a = r.renderer_->ExtractMeshAttrs(lo, hi, res, level, min_component_faces, normals, colors, normal_source, simplify);
              }
              py::dict d;
              d["verts"] = a.verts;
              d["faces"] = a.faces;
              if (normals) d["normals"] = a.normals;
              if (colors) d["colors"] = a.colors;
+             if (simplify >= 2) {  // the size of the mesh before the simplification
+               d["verts_in"] = a.verts_in;
+               d["faces_in"] = a.faces_in;
+             }
              return d;
            },
            py::arg("lo"), py::arg("hi"), py::arg("res"), py::arg("level"), py::arg("min_component_faces") = 0, py::arg("normals") = true,
-           py::arg("colors") = true, py::arg("normal_source") = "grid")  // "field": normals (and colours) from the field's own gradient
+           py::arg("colors") = true, py::arg("normal_source") = "grid",  // "field": normals (and colours) from the field's own gradient
+           py::arg("simplify") = 0)  // k >= 2: mesh_simplify on clusters of k^3 grid cells before the attributes are computed
       .def("query_density_grad",  // world [n,3] -> [density [n] (= query_density), grad [n,3] = its analytic world-space gradient]
            [](ExpRunner& r, const Tensor& world) {
              py::gil_scoped_release no_gil;

@@ -981,3 +981,337 @@ int f2n_mesh_filter_emit(void* stream, int n_verts, int n_faces, const float* ve
                        vert_start_end, out_faces);
   return f2n_launch_status();
 }
+
+// =====================================================================================================================
+// Mesh simplification (include/f2n_abi.h, "Mesh simplification by vertex clustering"): cluster keys, the exact fixed-point
+// accumulation of the clusters' plane quadrics, the fp64 placement, the re-indexed faces.
+//   accumulate: one thread per vertex / per face; the lanes of a wave that add to the same cluster are summed across the wave first
+//               (wave_fold, over integers: any order gives the same sum), then lanes 0..N-1 add the N sums to the cluster's row
+//               with one atomic instruction -- one 128-byte row segment per cluster and wave instead of N atomics per lane.
+//   place:      one thread per cluster, the adjugate of the regularised 3x3 system in named scalars (no private array)
+// =====================================================================================================================
+namespace {
+
+#define F2N_CLUSTER_SLOTS 16
+#define F2N_CLUSTER_MAX_RECORDS (1 << 18)
+
+struct ClusterGrid {
+  float lo[3];
+  float cell;
+  int dims[3];
+};
+
+__device__ __forceinline__ bool finite3(const float* p) {
+  const float inf = __builtin_huge_valf();
+  return fabsf(p[0]) < inf && fabsf(p[1]) < inf && fabsf(p[2]) < inf;  // (false for NaN as well)
+}
+
+// cell index of coordinate p along axis k
+__device__ __forceinline__ int cluster_cell(const ClusterGrid& g, int k, float p) {
+  const float u = floorf(F2N_DIV_RN(F2N_SUB_RN(p, g.lo[k]), g.cell));
+  return (int) fminf(fmaxf(u, 0.f), (float) (g.dims[k] - 1));
+}
+
+__device__ __forceinline__ float cluster_centre(const ClusterGrid& g, int k, int i) {
+  return F2N_ADD_RN(g.lo[k], F2N_MUL_RN(F2N_ADD_RN((float) i, 0.5f), g.cell));
+}
+
+// local coordinates of p in its own cell
+__device__ __forceinline__ void cluster_local(const ClusterGrid& g, const float* p, float* q) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const float c = cluster_centre(g, k, cluster_cell(g, k, p[k]));
+    q[k] = fminf(fmaxf(F2N_DIV_RN(F2N_SUB_RN(p[k], c), g.cell), -0.5f), 0.5f);
+  }
+}
+
+__device__ __forceinline__ long long cluster_quant(float x) { return __double2ll_rn((double) x * 1099511627776.0); }
+
+__global__ void __launch_bounds__(256) cluster_keys_kernel(int n_verts, const float* __restrict__ verts, ClusterGrid g,
+                                                          long long* __restrict__ keys) {
+  const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_verts) return;
+  const float p[3] = {verts[v * 3], verts[v * 3 + 1], verts[v * 3 + 2]};
+  long long key = -1;
+  if (finite3(p))
+    key = ((long long) cluster_cell(g, 2, p[2]) * g.dims[1] + cluster_cell(g, 1, p[1])) * g.dims[0] + cluster_cell(g, 0, p[0]);
+  keys[v] = key;
+}
+
+// The wave's sums of val[0..N), N a power of two: lane l returns the sum of val[l % N] over all 64 lanes (every lane of the wave must
+// call this).  Each of the first log2(N) steps halves what a lane carries -- the lanes of a pair keep one half of the values each
+// and send the other, so after the step over lane bit D a lane holds the values whose index agrees with its lane number in the bits
+// up to D -- and the remaining steps sum the one value left: N - 1 + (6 - log2 N) shuffles instead of 6 N.  Integers: any order
+// gives the same sum.
+template <int N, int D>
+__device__ __forceinline__ long long wave_fold(long long (&val)[N], int lane) {
+  if constexpr (N == 1) {
+    long long s = val[0];
+#pragma unroll
+    for (int d = D; d < 64; d <<= 1) s += __shfl_xor(s, d);
+    return s;
+  } else {
+    const bool up = (lane & D) != 0;
+    long long half[N / 2];
+#pragma unroll
+    for (int j = 0; j < N / 2; j++) {
+      const long long keep = up ? val[2 * j + 1] : val[2 * j], send = up ? val[2 * j] : val[2 * j + 1];
+      half[j] = keep + __shfl_xor(send, D);
+    }
+    return wave_fold<N / 2, D * 2>(half, lane);
+  }
+}
+
+// ... then lanes 0..N-1 add sum j to row[first + j] with one atomic instruction.  row is wave-uniform.
+template <int N>
+__device__ __forceinline__ void wave_sum_add(unsigned long long* row, int first, long long (&val)[N]) {
+  const int lane = threadIdx.x & 63;
+  const long long mine = wave_fold<N, 1>(val, lane);
+  if (lane < N && mine != 0) atomicAdd(row + first + lane, (unsigned long long) mine);
+}
+
+__global__ void __launch_bounds__(256) cluster_vert_accumulate_kernel(int n_verts, const float* __restrict__ verts,
+                                                                     const int32_t* __restrict__ cluster_of, int n_clusters,
+                                                                     ClusterGrid g, unsigned long long* acc) {
+  const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  int c = -1;
+  long long qq[3] = {0, 0, 0};
+  if (v < n_verts) {
+    c = cluster_of[v];
+    if (c >= 0 && c < n_clusters) {
+      const float p[3] = {verts[v * 3], verts[v * 3 + 1], verts[v * 3 + 2]};
+      float q[3];
+      cluster_local(g, p, q);
+#pragma unroll
+      for (int k = 0; k < 3; k++) qq[k] = cluster_quant(q[k]);
+    } else {
+      c = -1;
+    }
+  }
+  bool todo = c >= 0;
+  for (;;) {  // (no lane leaves before the wave is done: the sums are taken over all 64 lanes)
+    const unsigned long long rem = __ballot(todo);
+    if (rem == 0) break;
+    const int c0 = __shfl(c, __ffsll((long long) rem) - 1);
+    const bool same = todo && c == c0;
+    long long val[4] = {same ? qq[0] : 0, same ? qq[1] : 0, same ? qq[2] : 0, same ? 1 : 0};
+    wave_sum_add<4>(acc + (int64_t) c0 * F2N_CLUSTER_SLOTS, 12, val);
+    todo = todo && !same;
+  }
+}
+
+__global__ void __launch_bounds__(256) cluster_face_accumulate_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                                     const int32_t* __restrict__ faces,
+                                                                     const int32_t* __restrict__ cluster_of, int n_clusters,
+                                                                     ClusterGrid g, unsigned long long* acc) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  int c[3] = {-1, -1, -1};
+  long long qa[7] = {0, 0, 0, 0, 0, 0, 0};  // quant of A_xx, A_xy, A_xz, A_yy, A_yz, A_zz, w: shared by the face's three corners
+  long long qb[3][4];                       // quant of b_x, b_y, b_z, cc per corner
+#pragma unroll
+  for (int x = 0; x < 3; x++)
+#pragma unroll
+    for (int k = 0; k < 4; k++) qb[x][k] = 0;
+  int ia, ib, ic;
+  if (f < n_faces && face_in_range(faces, f, n_verts, &ia, &ib, &ic)) {
+    const int id[3] = {ia, ib, ic};
+    float p[3][3];
+    bool ok = true;
+#pragma unroll
+    for (int x = 0; x < 3; x++) {
+      c[x] = cluster_of[id[x]];
+      ok = ok && c[x] >= 0 && c[x] < n_clusters;
+#pragma unroll
+      for (int k = 0; k < 3; k++) p[x][k] = verts[(int64_t) id[x] * 3 + k];
+    }
+    float e1[3], e2[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      e1[k] = F2N_DIV_RN(F2N_SUB_RN(p[1][k], p[0][k]), g.cell);
+      e2[k] = F2N_DIV_RN(F2N_SUB_RN(p[2][k], p[0][k]), g.cell);
+    }
+    const float n[3] = {F2N_SUB_RN(F2N_MUL_RN(e1[1], e2[2]), F2N_MUL_RN(e1[2], e2[1])),
+                        F2N_SUB_RN(F2N_MUL_RN(e1[2], e2[0]), F2N_MUL_RN(e1[0], e2[2])),
+                        F2N_SUB_RN(F2N_MUL_RN(e1[0], e2[1]), F2N_MUL_RN(e1[1], e2[0]))};
+    const float l = sqrtf(F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(n[0], n[0]), F2N_MUL_RN(n[1], n[1])), F2N_MUL_RN(n[2], n[2])));
+    ok = ok && l > 0.f && l < __builtin_huge_valf();
+    if (ok) {
+      const float w = fminf(F2N_MUL_RN(l, 0.5f), 16.f);
+      const float u[3] = {F2N_DIV_RN(n[0], l), F2N_DIV_RN(n[1], l), F2N_DIV_RN(n[2], l)};
+      const float wu[3] = {F2N_MUL_RN(w, u[0]), F2N_MUL_RN(w, u[1]), F2N_MUL_RN(w, u[2])};
+      qa[0] = cluster_quant(F2N_MUL_RN(wu[0], u[0]));
+      qa[1] = cluster_quant(F2N_MUL_RN(wu[0], u[1]));
+      qa[2] = cluster_quant(F2N_MUL_RN(wu[0], u[2]));
+      qa[3] = cluster_quant(F2N_MUL_RN(wu[1], u[1]));
+      qa[4] = cluster_quant(F2N_MUL_RN(wu[1], u[2]));
+      qa[5] = cluster_quant(F2N_MUL_RN(wu[2], u[2]));
+      qa[6] = cluster_quant(w);
+#pragma unroll
+      for (int x = 0; x < 3; x++) {
+        float q[3];
+        cluster_local(g, p[x], q);
+        const float d = -F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(u[0], q[0]), F2N_MUL_RN(u[1], q[1])), F2N_MUL_RN(u[2], q[2]));
+        const float wd = F2N_MUL_RN(w, d);
+#pragma unroll
+        for (int k = 0; k < 3; k++) qb[x][k] = cluster_quant(F2N_MUL_RN(wd, u[k]));
+        qb[x][3] = cluster_quant(F2N_MUL_RN(wd, d));
+      }
+    } else {
+      c[0] = c[1] = c[2] = -1;
+    }
+  }
+  // One round per distinct cluster among the wave's pending corners (the three corners of a face together: neighbouring faces and
+  // the corners of one face mostly share their cluster).  A lane with k corners in the round's cluster adds k times the face's
+  // shared terms and the sum of those corners' own terms: integers, so this is what k single records would have added.
+  bool t0 = c[0] >= 0, t1 = c[1] >= 0, t2 = c[2] >= 0;
+  for (;;) {
+    const unsigned long long rem = __ballot(t0 || t1 || t2);
+    if (rem == 0) break;
+    const int c0 = __shfl(t0 ? c[0] : t1 ? c[1] : c[2], __ffsll((long long) rem) - 1);
+    const bool m0 = t0 && c[0] == c0, m1 = t1 && c[1] == c0, m2 = t2 && c[2] == c0;
+    const long long k = (m0 ? 1 : 0) + (m1 ? 1 : 0) + (m2 ? 1 : 0);
+    long long val[16];  // (12 sums, padded to a power of two)
+#pragma unroll
+    for (int j = 12; j < 16; j++) val[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 6; j++) val[j] = k * qa[j];
+#pragma unroll
+    for (int j = 0; j < 4; j++) val[6 + j] = (m0 ? qb[0][j] : 0) + (m1 ? qb[1][j] : 0) + (m2 ? qb[2][j] : 0);
+    val[10] = k * qa[6];
+    val[11] = k;
+    wave_sum_add<16>(acc + (int64_t) c0 * F2N_CLUSTER_SLOTS, 0, val);
+    t0 = t0 && !m0;
+    t1 = t1 && !m1;
+    t2 = t2 && !m2;
+  }
+}
+
+__global__ void __launch_bounds__(256) cluster_guard_kernel(int n_clusters, const long long* __restrict__ acc, int32_t* flag) {
+  const int64_t c = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_clusters) return;
+  if (acc[c * F2N_CLUSTER_SLOTS + 11] > F2N_CLUSTER_MAX_RECORDS || acc[c * F2N_CLUSTER_SLOTS + 15] > F2N_CLUSTER_MAX_RECORDS)
+    *flag = 1;  // (benign race: every writer stores 1)
+}
+
+__global__ void __launch_bounds__(256) cluster_place_kernel(int n_clusters, const long long* __restrict__ acc,
+                                                           const long long* __restrict__ cluster_keys, ClusterGrid g, double lambda,
+                                                           float* __restrict__ out) {
+  const int64_t c = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_clusters) return;
+  const long long* a = acc + c * F2N_CLUSTER_SLOTS;
+  const double s = 1.0 / 1099511627776.0;  // 2^-40
+  const double cnt = (double) a[15];
+  const double mx = ((double) a[12] * s) / cnt, my = ((double) a[13] * s) / cnt, mz = ((double) a[14] * s) / cnt;
+  const double W = (double) a[10] * s;
+  double qx = mx, qy = my, qz = mz;
+  if (W > 0.0) {
+    const double gl = lambda * W;
+    const double Mxx = (double) a[0] * s + gl, Mxy = (double) a[1] * s, Mxz = (double) a[2] * s;
+    const double Myy = (double) a[3] * s + gl, Myz = (double) a[4] * s, Mzz = (double) a[5] * s + gl;
+    const double rx = gl * mx - (double) a[6] * s, ry = gl * my - (double) a[7] * s, rz = gl * mz - (double) a[8] * s;
+    const double C00 = Myy * Mzz - Myz * Myz, C01 = Mxz * Myz - Mxy * Mzz, C02 = Mxy * Myz - Mxz * Myy;
+    const double C11 = Mxx * Mzz - Mxz * Mxz, C12 = Mxy * Mxz - Mxx * Myz, C22 = Mxx * Myy - Mxy * Mxy;
+    const double det = Mxx * C00 + (Mxy * C01 + Mxz * C02);
+    if (det > 0.0 && det < __builtin_huge_val()) {
+      qx = (C00 * rx + (C01 * ry + C02 * rz)) / det;
+      qy = (C01 * rx + (C11 * ry + C12 * rz)) / det;
+      qz = (C02 * rx + (C12 * ry + C22 * rz)) / det;
+    }
+  }
+  const long long key = cluster_keys[c];
+  const int ix = (int) (key % g.dims[0]), iy = (int) ((key / g.dims[0]) % g.dims[1]), iz = (int) (key / ((long long) g.dims[0] * g.dims[1]));
+  out[c * 3 + 0] = F2N_ADD_RN(cluster_centre(g, 0, ix), F2N_MUL_RN(g.cell, (float) fmin(fmax(qx, -0.5), 0.5)));
+  out[c * 3 + 1] = F2N_ADD_RN(cluster_centre(g, 1, iy), F2N_MUL_RN(g.cell, (float) fmin(fmax(qy, -0.5), 0.5)));
+  out[c * 3 + 2] = F2N_ADD_RN(cluster_centre(g, 2, iz), F2N_MUL_RN(g.cell, (float) fmin(fmax(qz, -0.5), 0.5)));
+}
+
+__global__ void __launch_bounds__(256) cluster_faces_kernel(int n_verts, int n_faces, const int32_t* __restrict__ faces,
+                                                           const int32_t* __restrict__ cluster_of, int32_t* __restrict__ out) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  int a, b, c;
+  int r0 = -1, r1 = -1, r2 = -1;
+  if (face_in_range(faces, f, n_verts, &a, &b, &c)) {
+    const int ca = cluster_of[a], cb = cluster_of[b], cc = cluster_of[c];
+    if (ca >= 0 && cb >= 0 && cc >= 0 && ca != cb && cb != cc && ca != cc) {
+      if (ca < cb && ca < cc) {
+        r0 = ca; r1 = cb; r2 = cc;
+      } else if (cb < cc) {
+        r0 = cb; r1 = cc; r2 = ca;
+      } else {
+        r0 = cc; r1 = ca; r2 = cb;
+      }
+    }
+  }
+  out[f * 3 + 0] = r0;
+  out[f * 3 + 1] = r1;
+  out[f * 3 + 2] = r2;
+}
+
+bool cluster_grid_ok(const float* lo, float cell, const int32_t* dims, ClusterGrid* g) {
+  if (lo == nullptr || dims == nullptr || !(cell > 0.f) || !(cell < __builtin_huge_valf())) return false;
+  for (int k = 0; k < 3; k++) {
+    if (!(fabsf(lo[k]) < __builtin_huge_valf()) || dims[k] < 1 || dims[k] > (1 << 20)) return false;
+    g->lo[k] = lo[k];
+    g->dims[k] = dims[k];
+  }
+  g->cell = cell;
+  return true;
+}
+
+}  // namespace
+
+int f2n_mesh_cluster_keys(void* stream, int n_verts, const float* verts, const float* lo, float cell, const int32_t* dims, int64_t* keys) {
+  ClusterGrid g;
+  if (n_verts < 0 || !cluster_grid_ok(lo, cell, dims, &g) || (n_verts > 0 && (verts == nullptr || keys == nullptr))) return F2N_ERR_INVALID_ARG;
+  if (n_verts == 0) return F2N_OK;
+  hipLaunchKernelGGL(cluster_keys_kernel, dim3(f2n_div_up(n_verts, 256)), dim3(256), 0, (hipStream_t) stream, n_verts, verts, g,
+                     (long long*) keys);
+  return f2n_launch_status();
+}
+
+int f2n_mesh_cluster_accumulate(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, const int32_t* cluster_of,
+                                int n_clusters, const float* lo, float cell, const int32_t* dims, int64_t* acc, int32_t* flag) {
+  ClusterGrid g;
+  if (n_verts < 0 || n_faces < 0 || n_clusters < 0 || !cluster_grid_ok(lo, cell, dims, &g) ||
+      (n_verts > 0 && (verts == nullptr || cluster_of == nullptr)) || (n_faces > 0 && (n_verts == 0 || faces == nullptr)) ||
+      (n_clusters > 0 && (acc == nullptr || flag == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n_clusters == 0) return F2N_OK;  // (no cluster: no vertex has one, nothing to add)
+  hipStream_t st = (hipStream_t) stream;
+  if (hipMemsetAsync(flag, 0, sizeof(int32_t), st) != hipSuccess) return f2n_launch_status();
+  if (n_verts > 0)
+    hipLaunchKernelGGL(cluster_vert_accumulate_kernel, dim3(f2n_div_up(n_verts, 256)), dim3(256), 0, st, n_verts, verts, cluster_of,
+                       n_clusters, g, (unsigned long long*) acc);
+  if (n_faces > 0)
+    hipLaunchKernelGGL(cluster_face_accumulate_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, st, n_verts, n_faces, verts, faces,
+                       cluster_of, n_clusters, g, (unsigned long long*) acc);
+  hipLaunchKernelGGL(cluster_guard_kernel, dim3(f2n_div_up(n_clusters, 256)), dim3(256), 0, st, n_clusters, (const long long*) acc, flag);
+  int e = f2n_launch_status();
+  if (e != F2N_OK) return e;
+  int32_t over = 0;
+  if (hipMemcpyAsync(&over, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return f2n_launch_status();
+  return over != 0 ? F2N_ERR_UNSUPPORTED : F2N_OK;
+}
+
+int f2n_mesh_cluster_place(void* stream, int n_clusters, const int64_t* acc, const int64_t* cluster_keys, const float* lo, float cell,
+                           const int32_t* dims, double lambda, float* out_verts) {
+  ClusterGrid g;
+  if (n_clusters < 0 || !cluster_grid_ok(lo, cell, dims, &g) || !(lambda >= 0.0) || !(lambda < __builtin_huge_val()) ||
+      (n_clusters > 0 && (acc == nullptr || cluster_keys == nullptr || out_verts == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n_clusters == 0) return F2N_OK;
+  hipLaunchKernelGGL(cluster_place_kernel, dim3(f2n_div_up(n_clusters, 256)), dim3(256), 0, (hipStream_t) stream, n_clusters,
+                     (const long long*) acc, (const long long*) cluster_keys, g, lambda, out_verts);
+  return f2n_launch_status();
+}
+
+int f2n_mesh_cluster_faces(void* stream, int n_verts, int n_faces, const int32_t* faces, const int32_t* cluster_of, int32_t* out_faces) {
+  if (n_verts < 0 || n_faces < 0 || (n_faces > 0 && (faces == nullptr || out_faces == nullptr || (n_verts > 0 && cluster_of == nullptr))))
+    return F2N_ERR_INVALID_ARG;
+  if (n_faces == 0) return F2N_OK;
+  hipLaunchKernelGGL(cluster_faces_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, (hipStream_t) stream, n_verts, n_faces, faces,
+                     cluster_of, out_faces);
+  return f2n_launch_status();
+}

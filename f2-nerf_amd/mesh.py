@@ -16,6 +16,10 @@ Options (hydra-style overrides, no `mesh` group in the configs):
   mesh.colors      true: per-vertex colours (uchar red, green, blue; default false): the radiance AT the vertex seen along the
                    inward normal -- a single-point query, not a volume-rendered pixel
   mesh.min_component_faces  N > 1: connected components of fewer than N faces ("floaters") are dropped (default 0: none)
+  mesh.simplify    k >= 2: the mesh is simplified by vertex clustering on cells of k grid steps with quadric-error placement
+                   (host.mesh_simplify; default 0: off) after the floater removal and before normals and colours, which are computed
+                   at the new vertices -> <iter>_<res>_s<k>.ply (<iter>_<res>_tsdf_s<k>.ply).  One vertex per occupied cell: features
+                   thinner than a cell become two-sided sheets or non-manifold edges, never holes
   mesh.source      density | tsdf (default density): the iso-surface of the raw density at mesh.level, or the zero crossing of a
                    truncated signed distance field fused from the training views' rendered depth (fuse_tsdf; mesh.level is not
                    used, normals of source "grid" come from the TSDF) -> <exp>/meshes/<iter>_<res>_tsdf.ply
@@ -58,7 +62,16 @@ def options(cfg):
     return {"resolution": int(m.get("resolution", 256)), "level": float(m.get("level", DEFAULT_LEVEL)), "bbox_min": lo,
             "bbox_max": hi, "normals": _flag(m.get("normals", False)), "colors": _flag(m.get("colors", False)),
             "min_component_faces": int(m.get("min_component_faces", 0)), "normal_source": _normal_source(m.get("normal_source", "grid")),
-            "source": _source(m.get("source", "density"))}
+            "source": _source(m.get("source", "density")), "simplify": _simplify(m.get("simplify", 0))}
+
+
+def _simplify(v):
+    if v is None or isinstance(v, bool) or (isinstance(v, float) and v != int(v)):
+        raise ValueError("mesh.simplify must be an integer >= 0, got %r" % (v,))
+    k = int(v)  # (ValueError for a string that is not an integer)
+    if k < 0:
+        raise ValueError("mesh.simplify must be an integer >= 0 (cells of k grid steps; 0 or 1: off), got %r" % (v,))
+    return k
 
 
 SOURCES = ("density", "tsdf")
@@ -306,6 +319,9 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
     verts, faces = host.mesh_from_grid_masked(t["g"], t["valid"], t["lo"], t["step"], 0.0)
     if o["min_component_faces"] > 1:
         verts, faces, _ = host.mesh_filter_components(verts, faces, o["min_component_faces"])
+    k, faces_in = o["simplify"], len(faces)
+    if k >= 2:  # (cell = k * step as ONE float32 product: what extract_mesh_attrs uses)
+        verts, faces, _ = host.mesh_simplify(verts, faces, float(np.float32(k) * np.float32(t["step"])), t["lo"])
     normals = colors = None
     if (o["normals"] or o["colors"]) and len(verts) > 0:
         nrm = host.grid_normals(t["g"], verts, t["lo"], t["step"])  # (g is positive inside, as a density is: the same sign)
@@ -321,12 +337,16 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
     elif o["normals"] or o["colors"]:
         normals = np.zeros((0, 3), np.float32) if o["normals"] else None
         colors = np.zeros((0, 3), np.float32) if o["colors"] else None
-    path = os.path.join(exp_dir, "meshes", "%d_%d_tsdf.ply" % (runner.iter_step, o["resolution"]))
+    path = os.path.join(exp_dir, "meshes", "%d_%d_tsdf%s.ply" % (runner.iter_step, o["resolution"], "_s%d" % k if k >= 2 else ""))
     v = to_world(verts.cpu().numpy(), scene["center"], scene["radius"])
     write_ply(path, v, faces.cpu().numpy(), normals, colors)
-    print("Mesh: %d vertices, %d faces from the TSDF of %d views (%d of %d grid points known, truncation %g) -> %s" % (
-        len(v), len(faces), t["n_views"], int(t["valid"].sum()), t["valid"].numel(), t["trunc"], path))
+    print("Mesh: %d vertices, %d faces%s from the TSDF of %d views (%d of %d grid points known, truncation %g) -> %s" % (
+        len(v), len(faces), _simplified(k, faces_in), t["n_views"], int(t["valid"].sum()), t["valid"].numel(), t["trunc"], path))
     return path
+
+
+def _simplified(k, faces_in):
+    return " (simplified from %d faces, mesh.simplify=%d)" % (faces_in, k) if k >= 2 else ""
 
 
 def extract(runner, cfg, scene, exp_dir, dataset=None):
@@ -335,18 +355,19 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
     o = options(cfg)
     if o["source"] == "tsdf":
         return extract_tsdf(runner, cfg, scene, dataset, exp_dir)
-    path = os.path.join(exp_dir, "meshes", "%d_%d.ply" % (runner.iter_step, o["resolution"]))
-    if not (o["normals"] or o["colors"] or o["min_component_faces"] > 1):
+    k, faces_in = o["simplify"], 0
+    path = os.path.join(exp_dir, "meshes", "%d_%d%s.ply" % (runner.iter_step, o["resolution"], "_s%d" % k if k >= 2 else ""))
+    if not (o["normals"] or o["colors"] or o["min_component_faces"] > 1 or k >= 2):
         verts, faces = runner.extract_mesh(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"])
         v = to_world(verts.cpu().numpy(), scene["center"], scene["radius"])
         write_ply(path, v, faces.cpu().numpy())
     else:
         m = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"], o["normals"],
-                                      o["colors"], o["normal_source"])
-        verts, faces = m["verts"], m["faces"]
+                                      o["colors"], o["normal_source"], *((k,) if k >= 2 else ()))
+        verts, faces, faces_in = m["verts"], m["faces"], m.get("faces_in", 0)
         v = to_world(verts.cpu().numpy(), scene["center"], scene["radius"])
         # (the world frame is a uniform scale and a shift of the normalised one: normals are the same in both)
         write_ply(path, v, faces.cpu().numpy(), m["normals"].cpu().numpy() if o["normals"] else None,
                   m["colors"].cpu().numpy() if o["colors"] else None)
-    print("Mesh: %d vertices, %d faces at level %g -> %s" % (len(v), len(faces), o["level"], path))
+    print("Mesh: %d vertices, %d faces%s at level %g -> %s" % (len(v), len(faces), _simplified(k, faces_in), o["level"], path))
     return path

@@ -988,6 +988,67 @@ int f2n_mesh_count_masked(void* stream, int nx, int ny, int nz, const float* gri
                           uint8_t* edge_mask /*[N]*/, int32_t* vert_counts /*[N]*/, int32_t* vert_start_end /*[N,2]*/,
                           int32_t* face_counts /*[C]*/, int32_t* face_start_end /*[C,2]*/, int32_t* totals /*[2]*/);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Mesh simplification by vertex clustering with quadric-error placement (additive; the ABI version is unchanged).  Lindstrom 2000
+ * with Garland-Heckbert plane quadrics.  No reference counterpart.  csrc/octree.hip.
+ * ------------------------------------------------------------------------------------------------- */
+/* The cluster grid: origin lo (HOST [3], finite), cell size `cell` (finite, > 0), dims (HOST [3], each in [1, 2^20]).  Every call below
+ * returns F2N_ERR_INVALID_ARG for a grid outside these ranges, a negative size or a NULL pointer it needs.  All fp32 operations are ONE
+ * rounding each, never an FMA; "fp64" likewise.
+ *   cell of a point p:   u_k = (p_k - lo_k) / cell;  i_k = min(max(floor(u_k), 0), dims_k - 1)        (clamped as floats, then cast)
+ *   centre of cell i:    c_k = lo_k + ((float) i_k + 0.5) * cell
+ *   local coordinates:   q_k = min(max((p_k - c_k) / cell, -0.5), 0.5)   -- the clamp only acts on the last bit of a vertex on its
+ *                        cell's border and on vertices that the grid does not cover (which the dims clamp pulled into a border cell)
+ *   quant(x) = __double2ll_rn((double) x * 2^40)    (round to nearest even; the product is exact)
+ * f2n_mesh_cluster_keys: keys[v] = ((int64) i_z * dims_y + i_y) * dims_x + i_x, or -1 for a vertex with a coordinate that is not finite.
+ *
+ * The caller numbers the occupied keys in ascending order: cluster ids 0..C-1, cluster_keys [C] int64 = those keys, cluster_of [V] int32
+ * = the id of every vertex's key, -1 for key -1 (a sorted unique with its inverse: plumbing, not a kernel here).
+ *
+ * f2n_mesh_cluster_accumulate: acc [C,16] int64, ZEROED BY THE CALLER, receives exact integer sums (64-bit integer atomics that wrap):
+ *   slots 0..5 = sum of quant(w n_i n_j) for (i,j) = xx, xy, xz, yy, yz, zz;  6..8 = sum of quant(w d n_i);  9 = sum of quant(w d d);
+ *   10 = sum of quant(w);  11 = corner records;  12..14 = sum of quant(q_k) over the cluster's vertices;  15 = its vertex count.
+ *   Per vertex v with cluster_of[v] >= 0: q of p_v in its own cell -> slots 12..15 of its cluster.
+ *   Per face (a, b, c), all fp32:  e1 = (p_b - p_a) / cell, e2 = (p_c - p_a) / cell (componentwise: a subtraction, a division);
+ *     n = (e1_y e2_z - e1_z e2_y, e1_z e2_x - e1_x e2_z, e1_x e2_y - e1_y e2_x);  l = sqrt((n_x n_x + n_y n_y) + n_z n_z);
+ *     the face contributes nothing if an index is outside [0, V), a corner has cluster_of < 0, or l is zero or not finite.
+ *     w = min(l * 0.5, 16);  u_k = n_k / l;  wu_k = w * u_k;  A_ij = wu_i * u_j.
+ *     For each corner x of the face, with q = the local coordinates of p_x in ITS OWN cell:  d = -((u_x q_x + u_y q_y) + u_z q_z);
+ *     wd = w * d;  b_k = wd * u_k;  cc = wd * d;  quant of (A_xx..A_zz, b_x, b_y, b_z, cc, w) and a 1 go to slots 0..11 of the corner's
+ *     cluster.  |q_k| <= 0.5 bounds |d| by 0.87 and every summand by 16 (1 + 2^-20).
+ *   Lanes of a wave that add to the same cluster are summed first (integers: the order is immaterial), one row segment of atomics per
+ *   cluster and wave.  The sums are integers, so acc does not depend on face order, vertex numbering, scheduling or run.
+ *   Guard: if a cluster holds more than 2^18 corner records or more than 2^18 vertices, the call returns F2N_ERR_UNSUPPORTED (below
+ *   that, 2^18 * 16 (1 + 2^-20) * 2^40 < 2^63: no sum wraps).  `flag` is one DEVICE word of scratch; the call READS IT BACK, so it
+ *   synchronises the stream.
+ *
+ * f2n_mesh_cluster_place: out_verts [C,3] f32, one thread per cluster, fp64 in this order (s = 2^-40, exact):
+ *   cnt = (double) acc[15];  m_k = ((double) acc[12+k] * s) / cnt;  W = (double) acc[10] * s;  A.. = (double) acc[0..5] * s;
+ *   b_k = (double) acc[6+k] * s.   If W > 0:  g = lambda * W;  M = A with g added to xx, yy, zz;  r_k = g * m_k - b_k;
+ *     the cofactors  C00 = Myy Mzz - Myz Myz,  C01 = Mxz Myz - Mxy Mzz,  C02 = Mxy Myz - Mxz Myy,  C11 = Mxx Mzz - Mxz Mxz,
+ *                    C12 = Mxy Mxz - Mxx Myz,  C22 = Mxx Myy - Mxy Mxy;    det = Mxx C00 + (Mxy C01 + Mxz C02);
+ *     t_x = C00 r_x + (C01 r_y + C02 r_z),  t_y = C01 r_x + (C11 r_y + C12 r_z),  t_z = C02 r_x + (C12 r_y + C22 r_z);  q*_k = t_k / det.
+ *     M is symmetric positive definite (A is a sum of w u u^T), so there is no rank decision and no threshold; only if the rounded
+ *     det is not a positive finite number (sums of a few 2^-40 quanta) does q* fall back to m, as it does for W = 0.
+ *   q*_k = min(max(q*_k, -0.5), 0.5);  out_k = c_k + cell * (float) q*_k   (c = the centre of the cell of cluster_keys[c], fp32).
+ *   lambda (a double, >= 0 and finite) ties the minimiser to the mean of the cluster's vertices where the planes leave it free.
+ *
+ * f2n_mesh_cluster_faces: out_faces [F,3] int32 = the corners' cluster ids rotated so that the smallest comes first (orientation
+ *   kept), or (-1, -1, -1) for a dropped face: an index outside [0, V), a cluster id of -1, or two equal ids.  The caller merges equal
+ *   rows and sorts them lexicographically (a unique over rows: plumbing), so a face and its reversed twin both survive -- a wall
+ *   thinner than a cell becomes a two-sided sheet, not a hole -- and then drops the clusters no face uses, keeping their order
+ *   (f2n_mesh_filter_count with all labels 0 and min_faces 1, f2n_mesh_filter_emit). */
+int f2n_mesh_cluster_keys(void* stream, int n_verts, const float* verts /*[V,3]*/, const float* lo /*host [3]*/, float cell,
+                          const int32_t* dims /*host [3]*/, int64_t* keys /*[V]*/);
+int f2n_mesh_cluster_accumulate(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/,
+                                const int32_t* cluster_of /*[V]*/, int n_clusters, const float* lo /*host [3]*/, float cell,
+                                const int32_t* dims /*host [3]*/, int64_t* acc /*[C,16], zeroed*/, int32_t* flag /*[1]*/);
+int f2n_mesh_cluster_place(void* stream, int n_clusters, const int64_t* acc /*[C,16]*/, const int64_t* cluster_keys /*[C]*/,
+                           const float* lo /*host [3]*/, float cell, const int32_t* dims /*host [3]*/, double lambda,
+                           float* out_verts /*[C,3]*/);
+int f2n_mesh_cluster_faces(void* stream, int n_verts, int n_faces, const int32_t* faces /*[F,3]*/, const int32_t* cluster_of /*[V]*/,
+                           int32_t* out_faces /*[F,3]*/);
+
 #ifdef __cplusplus
 }
 #endif
