@@ -942,6 +942,111 @@ def mesh_simplify(verts, faces, cell, lo=None, lam=1e-3):
     return ov, of, vert_map
 
 
+# ---------------------------------------------------------------- ray casting against a triangle mesh
+RAYCAST_MAX_CELLS = 1 << 27
+RAYCAST_DOMAIN_CELLS = 32768.0  # the grid traversal is exact for coordinates up to 2^15 cells (include/f2n_abi.h)
+
+
+def _finite_box(verts):
+    """(min [3], max [3]) per coordinate over its finite values (min > max for a coordinate without one)"""
+    fin = torch.isfinite(verts)
+    lows, highs = torch.where(fin, verts, verts.new_full((1,), float("inf"))), torch.where(fin, verts, verts.new_full((1,), float("-inf")))
+    box = torch.stack([lows[:, k].min() for k in range(3)] + [highs[:, k].max() for k in range(3)]).cpu().numpy()
+    return box[:3], box[3:]
+
+
+def mesh_raycast_default_cell(mn, mx, n_faces):
+    """sqrt(10 A / F), A = the area of the vertices' bounding box (about ten faces per occupied cell if the surface had the box's area),
+    at least 1/500 of the box's longest side; 1 for an empty or flat box.  A heuristic, not measured on a trained scene."""
+    import numpy as np
+    e = [float(mx[k]) - float(mn[k]) if mn[k] <= mx[k] else 0.0 for k in range(3)]
+    area = 2.0 * (e[0] * e[1] + e[1] * e[2] + e[2] * e[0])
+    cell = max(np.sqrt(10.0 * area / max(int(n_faces), 1)), max(e) / 500.0)
+    c32 = float(np.float32(cell))
+    return c32 if c32 > 0.0 and c32 < float("inf") else 1.0
+
+
+def mesh_raycast_build(verts, faces, cell=None, lo=None):
+    """The acceleration grid of mesh_raycast (f2n_mesh_raycast_count -> prefix sum -> f2n_mesh_raycast_fill -> sort -> searchsorted):
+    (lo [3], cell, dims [3], cell_start [ncells + 1] int32, cell_faces [E] int32).  cell None: mesh_raycast_default_cell; lo None: the
+    minimum of the vertices' finite coordinates (a given lo must not lie above it).  ValueError for a grid that is too fine."""
+    import numpy as np
+    f32 = np.float32
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    dev = verts.device
+    mn, mx = (np.ones(3, f32), np.zeros(3, f32)) if nv == 0 else _finite_box(verts)
+    cell = mesh_raycast_default_cell(mn, mx, nf) if cell is None else float(f32(cell))
+    if not (cell > 0.0 and cell < float("inf")):
+        raise ValueError("mesh_raycast_build: cell must be positive and finite, got %r" % (cell,))
+    lo3, dims = [f32(0.0) if lo is None else f32(x) for x in (lo if lo is not None else (0, 0, 0))], [1, 1, 1]
+    for k in range(3):
+        if not np.isfinite(lo3[k]):
+            raise ValueError("mesh_raycast_build: lo must be finite")
+        if mn[k] <= mx[k]:
+            if lo is None:
+                lo3[k] = mn[k]
+            if lo3[k] > mn[k]:
+                raise ValueError("mesh_raycast_build: the grid must cover the mesh (lo above a vertex)")
+            with np.errstate(all="ignore"):
+                u = f32(f32(mx[k] - lo3[k]) / f32(cell))
+            if not u < 1048575.0:
+                raise ValueError("mesh_raycast_build: cell is too small for the extent of the mesh")
+            dims[k] = int(np.floor(u)) + 1
+    nc = dims[0] * dims[1] * dims[2]
+    if nc > RAYCAST_MAX_CELLS:
+        raise ValueError("mesh_raycast_build: more than 2^27 cells (cell is too small for the mesh)")
+    lo_c, dims_c = _lo3(lo3), (ctypes.c_int32 * 3)(*dims)
+    counts = torch.zeros(nf, dtype=torch.int32, device=dev)
+    _ck(lib().f2n_mesh_raycast_count(_stream(), _i(nv), _i(nf), _p(verts, "f32", nf == 0), _p(faces, "i32", nf == 0), lo_c, _f(cell), dims_c,
+                                     _p(counts, "i32", nf == 0), _p(torch.empty(1, dtype=torch.int32, device=dev), "i32")),
+        "f2n_mesh_raycast_count")
+    ends = counts.cumsum(0, dtype=torch.int64)
+    total = int(ends[-1]) if nf else 0
+    if total > 2 ** 31 - 1:
+        raise ValueError("mesh_raycast_build: more than 2^31 list entries (cell is too small for the mesh)")
+    offsets = (ends - counts).contiguous()
+    keys = torch.empty(total, dtype=torch.int64, device=dev)
+    if total:
+        _ck(lib().f2n_mesh_raycast_fill(_stream(), _i(nv), _i(nf), _p(verts, "f32"), _p(faces, "i32"), lo_c, _f(cell), dims_c,
+                                        _p(offsets, "i64"), _p(keys, "i64")), "f2n_mesh_raycast_fill")
+    keys = torch.sort(keys)[0]
+    m = max(nf, 1)
+    cell_start = torch.searchsorted(keys, torch.arange(nc + 1, dtype=torch.int64, device=dev) * m).to(torch.int32).contiguous()
+    cell_faces = torch.remainder(keys, m).to(torch.int32).contiguous()
+    return [float(x) for x in lo3], cell, dims, cell_start, cell_faces
+
+
+def mesh_raycast(verts, faces, accel, rays_o, rays_d, bounds=None):
+    """(t [R], face [R] int32, bary [R,3]): the rays' first hit on the mesh inside their window (f2n_mesh_raycast); accel =
+    mesh_raycast_build's tuple, or None for the brute-force mode.  ValueError for rays outside the grid traversal's domain."""
+    nv, nf, R = int(verts.shape[0]), int(faces.shape[0]), int(rays_o.shape[0])
+    dev = rays_o.device
+    if int(rays_d.shape[0]) != R or (bounds is not None and int(bounds.shape[0]) != R):
+        raise F2nError("rays_o [R,3], rays_d [R,3] and bounds [R,2] must agree")
+    t = torch.zeros(R, dtype=torch.float32, device=dev)
+    face = torch.full((R,), -1, dtype=torch.int32, device=dev)
+    bary = torch.zeros((R, 3), dtype=torch.float32, device=dev)
+    lo_c = dims_c = None
+    cell, cs, cf = 0.0, None, None
+    if accel is not None:
+        lo, cell, dims, cs, cf = accel
+        if cs.numel() != int(dims[0]) * int(dims[1]) * int(dims[2]) + 1:
+            raise ValueError("mesh_raycast: cell_start does not match dims")
+        far = max(max(abs(float(lo[k])), abs(float(lo[k]) + dims[k] * float(cell))) for k in range(3))
+        if R:
+            fo = float(rays_o.abs().max())
+            far = fo if fo != fo else max(far, fo)  # (an origin that is not finite is outside the domain)
+        if not far <= RAYCAST_DOMAIN_CELLS * cell:
+            raise ValueError("mesh_raycast: a ray origin (or the grid) lies more than 2^15 cells from the frame's origin: outside the domain "
+                             "in which the grid traversal is exact; use a larger cell or accel=None")
+        lo_c, dims_c = _lo3(lo), (ctypes.c_int32 * 3)(*(int(x) for x in dims))
+    _ck(lib().f2n_mesh_raycast(_stream(), _i(nv), _i(nf), _p(verts, "f32", nf == 0), _p(faces, "i32", nf == 0), lo_c, _f(cell), dims_c,
+                               _p(cs, "i32", True), _p(cf if cf is not None and cf.numel() else None, "i32", True), _i(R),
+                               _p(rays_o, "f32", R == 0), _p(rays_d, "f32", R == 0), _p(bounds, "f32", True), _p(t, "f32", R == 0),
+                               _p(face, "i32", R == 0), _p(bary, "f32", R == 0)), "f2n_mesh_raycast")
+    return t, face, bary
+
+
 # ---------------------------------------------------------------- TSDF fusion of depth maps
 def tsdf_integrate(S, W, lo, step, poses, intri, dist_params, depth, conf, trunc):
     """Adds the depth maps depth [V,h,w] (conf [V,h,w] or None: weight 1) seen from poses [V,3,4] / intri [V,3,3] / dist_params [V,4] into

@@ -93,6 +93,25 @@ std::tuple<Tensor, Tensor, Tensor> MeshFilterComponents(const Tensor& verts, con
 // vertex per occupied cell, collapsed faces dropped, duplicates merged, faces sorted; lambda ties a vertex to its cluster's mean.
 std::tuple<Tensor, Tensor, Tensor> MeshSimplify(const Tensor& verts, const Tensor& faces, float cell, const float* lo, double lambda);
 
+// Ray casting against a triangle mesh (f2n_mesh_raycast*; include/f2n_abi.h states the test rounding by rounding).  The accel is a
+// uniform grid of face lists that covers the mesh: lo (NULL: the minimum of the finite coordinates; given: it must not lie above it),
+// cell (NaN: MeshRaycastDefaultCell), dims, cell_start [ncells + 1] and cell_faces [E] int32.  std::invalid_argument for a grid
+// that does not cover the mesh, holds more than 2^27 cells or 2^31 entries, and for rays outside the traversal's domain.
+struct MeshRaycastAccel {
+  float lo[3] = {0.f, 0.f, 0.f}, cell = 1.f;
+  int32_t dims[3] = {1, 1, 1};
+  Tensor cell_start, cell_faces;
+};
+// The default cell: sqrt(10 A / F) with A the area of the vertices' bounding box -- about ten faces per occupied cell if the surface
+// had the box's area -- and at least 1/500 of the box's longest side; 1 for an empty or flat box.  A heuristic, not measured on a
+// trained scene.
+float MeshRaycastDefaultCell(const float mn[3], const float mx[3], int64_t n_faces);
+MeshRaycastAccel MeshRaycastBuild(const Tensor& verts, const Tensor& faces, float cell, const float* lo);
+// (t [R], face [R] int32 (-1: none), bary [R,3]) of the rays' first hit inside their window bounds [R,2] (undefined: (0, inf));
+// accel NULL: the brute-force mode, every ray against every face
+std::tuple<Tensor, Tensor, Tensor> MeshRaycast(const Tensor& verts, const Tensor& faces, const MeshRaycastAccel* accel, const Tensor& rays_o,
+                                               const Tensor& rays_d, const Tensor& bounds);
+
 struct MeshAttrs {  // Renderer::ExtractMeshAttrs; normals / colors are undefined unless asked for
   Tensor verts, faces, normals, colors;
   int64_t verts_in = -1, faces_in = -1;  // simplify >= 2: the size of the mesh that went into MeshSimplify

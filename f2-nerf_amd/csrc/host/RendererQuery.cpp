@@ -559,6 +559,124 @@ std::tuple<Tensor, Tensor, Tensor> MeshSimplify(const Tensor& verts, const Tenso
   return {ov, of, vert_map};
 }
 
+namespace {
+// per coordinate, over its finite values: (min [3], max [3]) on the host; min > max for a coordinate without a finite value
+void FiniteBox(const Tensor& v, float mn[3], float mx[3]) {
+  Tensor fin = torch::isfinite(v);
+  const float inf = std::numeric_limits<float>::infinity();
+  Tensor lows = torch::where(fin, v, torch::full({1}, inf, DevF32())), highs = torch::where(fin, v, torch::full({1}, -inf, DevF32()));
+  std::vector<Tensor> ends;
+  for (int k = 0; k < 3; k++) ends.push_back(lows.select(1, k).min());
+  for (int k = 0; k < 3; k++) ends.push_back(highs.select(1, k).max());
+  Tensor box = torch::stack(ends).cpu();
+  for (int k = 0; k < 3; k++) {
+    mn[k] = box.data_ptr<float>()[k];
+    mx[k] = box.data_ptr<float>()[3 + k];
+  }
+}
+}  // namespace
+
+float MeshRaycastDefaultCell(const float mn[3], const float mx[3], int64_t n_faces) {
+  double e[3], longest = 0.0;
+  for (int k = 0; k < 3; k++) {
+    e[k] = mn[k] <= mx[k] ? (double) mx[k] - (double) mn[k] : 0.0;
+    longest = std::max(longest, e[k]);
+  }
+  const double area = 2.0 * (e[0] * e[1] + e[1] * e[2] + e[2] * e[0]);
+  const double cell = std::max(std::sqrt(10.0 * area / (double) std::max<int64_t>(n_faces, 1)), longest / 500.0);
+  return cell > 0.0 && std::isfinite(cell) && (float) cell > 0.f && std::isfinite((float) cell) ? (float) cell : 1.f;
+}
+
+MeshRaycastAccel MeshRaycastBuild(const Tensor& verts, const Tensor& faces, float cell_in, const float* lo_in) {
+  torch::NoGradGuard g;
+  Tensor v = Points3(verts);
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  const int64_t nv = v.size(0), nf = f.size(0);
+  TORCH_CHECK(nf <= INT32_MAX, "mesh too large");
+  MeshRaycastAccel a;
+  float mn[3] = {1.f, 1.f, 1.f}, mx[3] = {0.f, 0.f, 0.f};
+  if (nv > 0) FiniteBox(v, mn, mx);
+  const bool given = !std::isnan(cell_in);  // (NaN: the default)
+  a.cell = given ? cell_in : MeshRaycastDefaultCell(mn, mx, nf);
+  if (!(a.cell > 0.f) || !std::isfinite(a.cell)) throw std::invalid_argument("mesh_raycast_build: cell must be positive and finite");
+  double ncells = 1.0;
+  for (int k = 0; k < 3; k++) {
+    a.lo[k] = lo_in != nullptr ? lo_in[k] : 0.f;
+    a.dims[k] = 1;
+    if (!std::isfinite(a.lo[k])) throw std::invalid_argument("mesh_raycast_build: lo must be finite");
+    if (mn[k] <= mx[k]) {  // (the coordinate has a finite value)
+      if (lo_in == nullptr) a.lo[k] = mn[k];
+      if (a.lo[k] > mn[k]) throw std::invalid_argument("mesh_raycast_build: the grid must cover the mesh (lo above a vertex)");
+      const float u = (mx[k] - a.lo[k]) / a.cell;  // (two fp32 roundings, as the cell index's u)
+      if (!(u < 1048575.f)) throw std::invalid_argument("mesh_raycast_build: cell is too small for the extent of the mesh");
+      a.dims[k] = (int) std::floor(u) + 1;
+    }
+    ncells *= (double) a.dims[k];
+  }
+  if (ncells > (double) (1 << 27)) throw std::invalid_argument("mesh_raycast_build: more than 2^27 cells (cell is too small for the mesh)");
+  const int64_t nc = (int64_t) ncells;
+  Tensor counts = torch::zeros({nf}, DevI32()), flag = torch::empty({1}, DevI32());
+  F2N_TIMED_CALL("mesh_raycast_count", f2n_mesh_raycast_count(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), a.lo, a.cell, a.dims,
+                                                              I32P(counts), I32P(flag)));
+  Tensor keys;
+  {
+    TimedSpan span("mesh_raycast_sort");
+    Tensor ends = counts.cumsum(0, torch::kInt64);
+    const int64_t total = nf > 0 ? ends[nf - 1].item<int64_t>() : 0;
+    if (total > INT32_MAX) throw std::invalid_argument("mesh_raycast_build: more than 2^31 list entries (cell is too small for the mesh)");
+    Tensor offsets = (ends - counts).contiguous();
+    keys = torch::empty({total}, DevI32().dtype(torch::kInt64));
+    if (total > 0)
+      F2N_CALL(f2n_mesh_raycast_fill(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), a.lo, a.cell, a.dims, offsets.data_ptr<int64_t>(),
+                                     keys.data_ptr<int64_t>()));
+    keys = std::get<0>(torch::sort(keys));
+    const int64_t m = std::max<int64_t>(nf, 1);
+    Tensor firsts = torch::arange(nc + 1, DevI32().dtype(torch::kInt64)) * m;
+    a.cell_start = torch::searchsorted(keys, firsts).to(torch::kInt32).contiguous();
+    a.cell_faces = torch::remainder(keys, m).to(torch::kInt32).contiguous();
+  }
+  return a;
+}
+
+std::tuple<Tensor, Tensor, Tensor> MeshRaycast(const Tensor& verts, const Tensor& faces, const MeshRaycastAccel* accel, const Tensor& rays_o,
+                                               const Tensor& rays_d, const Tensor& bounds) {
+  torch::NoGradGuard g;
+  Tensor v = Points3(verts), o = Points3(rays_o), d = Points3(rays_d);
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  const int64_t nv = v.size(0), nf = f.size(0), R = o.size(0);
+  TORCH_CHECK(nf <= INT32_MAX && d.size(0) == R, "mesh too large, or rays_o and rays_d differ in size");
+  Tensor b;
+  if (bounds.defined()) {
+    b = bounds.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 2});
+    TORCH_CHECK(b.size(0) == R, "bounds must be [R,2]");
+  }
+  Tensor t = torch::zeros({R}, DevF32()), face = torch::full({R}, -1, DevI32()), bary = torch::zeros({R, 3}, DevF32());
+  if (accel != nullptr) {
+    TORCH_CHECK(accel->cell_start.defined() && accel->cell_faces.defined(), "mesh_raycast: the accel has no cell lists");
+    const int64_t nc = (int64_t) accel->dims[0] * accel->dims[1] * accel->dims[2];
+    if (accel->cell_start.numel() != nc + 1) throw std::invalid_argument("mesh_raycast: cell_start does not match dims");
+    // the traversal's domain (include/f2n_abi.h): every coordinate of the box and of the origins within 2^15 cells of the frame's origin
+    float far = 0.f;
+    for (int k = 0; k < 3; k++)
+      far = std::max(far, std::max(std::fabs(accel->lo[k]), std::fabs(accel->lo[k] + (float) accel->dims[k] * accel->cell)));
+    if (R > 0) {
+      const float fo = o.abs().max().item<float>();  // (NaN propagates: an origin that is not finite is outside the domain)
+      far = std::isnan(fo) ? fo : std::max(far, fo);
+    }
+    if (!(far <= 32768.f * accel->cell))
+      throw std::invalid_argument("mesh_raycast: a ray origin (or the grid) lies more than 2^15 cells from the frame's origin: outside the "
+                                  "domain in which the grid traversal is exact; use a larger cell or accel=None");
+  }
+  Tensor cs = accel != nullptr ? DevArg(accel->cell_start, torch::kInt32, "cell_start") : Tensor();
+  Tensor cf = accel != nullptr ? DevArg(accel->cell_faces, torch::kInt32, "cell_faces") : Tensor();
+  F2N_TIMED_CALL(accel != nullptr ? "mesh_raycast" : "mesh_raycast_brute",
+                 f2n_mesh_raycast(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), accel != nullptr ? accel->lo : nullptr,
+                                  accel != nullptr ? accel->cell : 0.f, accel != nullptr ? accel->dims : nullptr,
+                                  accel != nullptr ? I32P(cs) : nullptr, accel != nullptr && cf.numel() > 0 ? I32P(cf) : nullptr, (int) R,
+                                  F32P(o), F32P(d), b.defined() ? F32P(b) : nullptr, F32P(t), I32P(face), F32P(bary)));
+  return {t, face, bary};
+}
+
 MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level,
                                      int min_component_faces, bool normals, bool colors, const std::string& normal_source, int simplify) {
   torch::NoGradGuard g;

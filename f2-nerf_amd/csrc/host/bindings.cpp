@@ -169,6 +169,43 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::vector<Tensor>{std::get<0>(t), std::get<1>(t), std::get<2>(t)};
         },
         py::arg("verts"), py::arg("faces"), py::arg("cell"), py::arg("lo") = py::none(), py::arg("lam") = 1e-3);
+  // the acceleration grid of mesh_raycast over a mesh: (lo [3], cell, dims [3], cell_start, cell_faces); cell None: the documented
+  // default (Renderer.h: MeshRaycastDefaultCell), lo None: the vertices' bounding-box minimum.  ValueError for a grid that is too fine
+  m.def("mesh_raycast_build",
+        [](const Tensor& verts, const Tensor& faces, const c10::optional<float>& cell, const c10::optional<std::vector<float>>& lo) {
+          if (lo.has_value() && lo->size() != 3) throw std::invalid_argument("lo must have three coordinates");
+          if (cell.has_value() && std::isnan(*cell)) throw std::invalid_argument("mesh_raycast_build: cell must be positive and finite");
+          MeshRaycastAccel a = MeshRaycastBuild(verts, faces, cell.has_value() ? *cell : std::numeric_limits<float>::quiet_NaN(),
+                                                lo.has_value() ? lo->data() : nullptr);
+          return py::make_tuple(std::vector<float>{a.lo[0], a.lo[1], a.lo[2]}, a.cell, std::vector<int>{a.dims[0], a.dims[1], a.dims[2]},
+                                a.cell_start, a.cell_faces);
+        },
+        py::arg("verts"), py::arg("faces"), py::arg("cell") = py::none(), py::arg("lo") = py::none());
+  // the rays' first hit on the mesh: [t, face, bary]; accel = mesh_raycast_build's tuple, or None for the brute-force mode.
+  // ValueError for rays outside the traversal's domain (origins more than 2^15 cells from the frame's origin)
+  m.def("mesh_raycast",
+        [](const Tensor& verts, const Tensor& faces, const py::object& accel, const Tensor& rays_o, const Tensor& rays_d,
+           const c10::optional<Tensor>& bounds) {
+          MeshRaycastAccel a;
+          const bool have = !accel.is_none();
+          if (have) {
+            py::tuple t = accel.cast<py::tuple>();
+            if (t.size() != 5) throw std::invalid_argument("accel must be mesh_raycast_build's (lo, cell, dims, cell_start, cell_faces)");
+            const auto lo = t[0].cast<std::vector<float>>();
+            const auto dims = t[2].cast<std::vector<int>>();
+            if (lo.size() != 3 || dims.size() != 3) throw std::invalid_argument("accel: lo and dims must have three entries");
+            for (int k = 0; k < 3; k++) {
+              a.lo[k] = lo[k];
+              a.dims[k] = dims[k];
+            }
+            a.cell = t[1].cast<float>();
+            a.cell_start = t[3].cast<Tensor>();
+            a.cell_faces = t[4].cast<Tensor>();
+          }
+          auto r = MeshRaycast(verts, faces, have ? &a : nullptr, rays_o, rays_d, bounds.has_value() ? *bounds : Tensor());
+          return std::vector<Tensor>{std::get<0>(r), std::get<1>(r), std::get<2>(r)};
+        },
+        py::arg("verts"), py::arg("faces"), py::arg("accel"), py::arg("rays_o"), py::arg("rays_d"), py::arg("bounds") = py::none());
   m.def("dp_set_table_buckets", [](int n) { DataParallel::table_buckets = n; });  // table all-reduce buckets of the next attach (A/B)
   // data-parallel replicas draw stream `rank` of every keyed purpose (KeyedDraws.h; the native attach sets it itself)
   m.def("dp_set_replica", [](int rank) { KeyedUniforms::SetReplica(rank); });

@@ -1315,3 +1315,307 @@ int f2n_mesh_cluster_faces(void* stream, int n_verts, int n_faces, const int32_t
                      cluster_of, out_faces);
   return f2n_launch_status();
 }
+
+// =====================================================================================================================
+// Mesh ray casting (include/f2n_abi.h, "Ray casting against a triangle mesh"): the Woop-Benthin-Wald test with fp64 edge
+// functions, a uniform grid of face lists built without atomics, and two drivers of the one test:
+//   brute:    every ray tests every face; a block stages 256 faces at a time in LDS (every lane reads the same face: a broadcast)
+//   traverse: one lane per ray walks the grid layer by layer along kz, the axis the test itself picked
+// The axis permutation is done with selects (sel3): a private array under a runtime index would live in scratch memory.
+// =====================================================================================================================
+namespace {
+
+#define F2N_RAYCAST_MAX_CELLS (1 << 27)
+#define F2N_RAYCAST_TILE 256
+#define F2N_RAYCAST_DOMAIN_CELLS 32768.f  // the traversal is proven for coordinates up to this many cells (f2n_abi.h)
+
+__device__ __forceinline__ float sel3(int k, float a, float b, float c) { return k == 0 ? a : (k == 1 ? b : c); }
+__device__ __forceinline__ int sel3i(int k, int a, int b, int c) { return k == 0 ? a : (k == 1 ? b : c); }
+
+struct RayFrame {
+  int kx, ky, kz;
+  float ox, oy, oz;  // the origin, permuted
+  float Sx, Sy, Sz;
+  float t_min, t_max;
+  bool ok;  // false: the ray hits nothing
+};
+
+struct RayHit {
+  float t, b0, b1, b2;
+  int face;
+};
+
+__device__ __forceinline__ RayFrame ray_frame(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                              const float* __restrict__ bounds, int64_t r) {
+  const float o0 = rays_o[r * 3], o1 = rays_o[r * 3 + 1], o2 = rays_o[r * 3 + 2];
+  const float d[3] = {rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};  // (only constant indices below: registers)
+  RayFrame f;
+  int kz = 0;
+  float m = fabsf(d[0]);
+  if (fabsf(d[1]) > m) { kz = 1; m = fabsf(d[1]); }
+  if (fabsf(d[2]) > m) kz = 2;
+  int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
+  const float dz = sel3(kz, d[0], d[1], d[2]);
+  if (dz < 0.f) { const int s = kx; kx = ky; ky = s; }
+  f.ok = finite3(d) && dz != 0.f;
+  f.kx = kx; f.ky = ky; f.kz = kz;
+  f.Sx = F2N_DIV_RN(sel3(kx, d[0], d[1], d[2]), dz);
+  f.Sy = F2N_DIV_RN(sel3(ky, d[0], d[1], d[2]), dz);
+  f.Sz = F2N_DIV_RN(1.f, dz);
+  f.ox = sel3(kx, o0, o1, o2); f.oy = sel3(ky, o0, o1, o2); f.oz = sel3(kz, o0, o1, o2);
+  f.t_min = bounds != nullptr ? bounds[r * 2] : 0.f;
+  f.t_max = bounds != nullptr ? bounds[r * 2 + 1] : __builtin_huge_valf();
+  return f;
+}
+
+// steps 3-8 of the contract for one face (p0, p1, p2: its vertices' x, y, z); keeps the nearer hit, the lower index among equals
+__device__ __forceinline__ void ray_face(const RayFrame& f, int face, float a0, float a1, float a2, float b0, float b1, float b2, float c0,
+                                         float c1, float c2, RayHit* h) {
+#define F2N_RAY_VERT(P0, P1, P2, X, Y, Z)                                     \
+  float X, Y, Z;                                                              \
+  {                                                                           \
+    const float qx = F2N_SUB_RN(sel3(f.kx, P0, P1, P2), f.ox);                \
+    const float qy = F2N_SUB_RN(sel3(f.ky, P0, P1, P2), f.oy);                \
+    const float qz = F2N_SUB_RN(sel3(f.kz, P0, P1, P2), f.oz);                \
+    X = F2N_SUB_RN(qx, F2N_MUL_RN(f.Sx, qz));                                 \
+    Y = F2N_SUB_RN(qy, F2N_MUL_RN(f.Sy, qz));                                 \
+    Z = F2N_MUL_RN(f.Sz, qz);                                                 \
+  }
+  F2N_RAY_VERT(a0, a1, a2, Ax, Ay, Az)
+  F2N_RAY_VERT(b0, b1, b2, Bx, By, Bz)
+  F2N_RAY_VERT(c0, c1, c2, Cx, Cy, Cz)
+#undef F2N_RAY_VERT
+  const double U = (double) Cx * (double) By - (double) Cy * (double) Bx;
+  const double V = (double) Ax * (double) Cy - (double) Ay * (double) Cx;
+  const double W = (double) Bx * (double) Ay - (double) By * (double) Ax;
+  if (!((U >= 0.0 && V >= 0.0 && W >= 0.0) || (U <= 0.0 && V <= 0.0 && W <= 0.0))) return;  // (a NaN is outside)
+  const double det = (U + V) + W;
+  if (det == 0.0) return;
+  const double T = (U * (double) Az + V * (double) Bz) + W * (double) Cz;
+  const float t = (float) (T / det);
+  if (!(t > f.t_min && t < f.t_max)) return;
+  if (h->face >= 0 && !(t < h->t || (t == h->t && face < h->face))) return;
+  h->t = t;
+  h->face = face;
+  h->b0 = (float) (U / det);
+  h->b1 = (float) (V / det);
+  h->b2 = (float) (W / det);
+}
+
+__device__ __forceinline__ void ray_store(const RayHit& h, int64_t r, float* __restrict__ out_t, int32_t* __restrict__ out_face,
+                                          float* __restrict__ out_bary) {
+  out_t[r] = h.t;
+  out_face[r] = h.face;
+  out_bary[r * 3] = h.b0;
+  out_bary[r * 3 + 1] = h.b1;
+  out_bary[r * 3 + 2] = h.b2;
+}
+
+__global__ void __launch_bounds__(256) raycast_check_faces_kernel(int n_verts, int n_faces, const int32_t* __restrict__ faces, int32_t* flag) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  int a, b, c;
+  if (!face_in_range(faces, f, n_verts, &a, &b, &c)) *flag = 1;  // (benign race: every writer stores 1)
+}
+
+__global__ void __launch_bounds__(F2N_RAYCAST_TILE) raycast_brute_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                                        const int32_t* __restrict__ faces, int n_rays,
+                                                                        const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                                        const float* __restrict__ bounds, float* __restrict__ out_t,
+                                                                        int32_t* __restrict__ out_face, float* __restrict__ out_bary) {
+  __shared__ float tile[9][F2N_RAYCAST_TILE];
+  const int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = r < n_rays;
+  RayFrame fr = ray_frame(rays_o, rays_d, bounds, live ? r : 0);
+  RayHit h = {0.f, 0.f, 0.f, 0.f, -1};
+  for (int base = 0; base < n_faces; base += F2N_RAYCAST_TILE) {
+    const int mine = base + (int) threadIdx.x;
+    int a, b, c;
+    const bool ok = mine < n_faces && face_in_range(faces, mine, n_verts, &a, &b, &c);
+    const float nan = __builtin_nanf("");  // (a face that is not there fails every test)
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      tile[k][threadIdx.x] = ok ? verts[(int64_t) a * 3 + k] : nan;
+      tile[3 + k][threadIdx.x] = ok ? verts[(int64_t) b * 3 + k] : nan;
+      tile[6 + k][threadIdx.x] = ok ? verts[(int64_t) c * 3 + k] : nan;
+    }
+    __syncthreads();
+    const int n = min(F2N_RAYCAST_TILE, n_faces - base);
+    if (live && fr.ok)
+      for (int j = 0; j < n; j++)
+        ray_face(fr, base + j, tile[0][j], tile[1][j], tile[2][j], tile[3][j], tile[4][j], tile[5][j], tile[6][j], tile[7][j], tile[8][j], &h);
+    __syncthreads();
+  }
+  if (live) ray_store(h, r, out_t, out_face, out_bary);
+}
+
+// cell index of coordinate p along an axis of origin lo and n cells (cluster_cell with the axis already selected): monotone in p
+__device__ __forceinline__ int ray_cell(float lo, float cell, int n, float p) {
+  const float u = floorf(F2N_DIV_RN(F2N_SUB_RN(p, lo), cell));
+  return (int) fminf(fmaxf(u, 0.f), (float) (n - 1));
+}
+
+__device__ __forceinline__ float ray_guard(float cell) { return F2N_MUL_RN(cell, 0.0625f); }
+
+// the cells [lo_i, hi_i] per axis that list face f (its bounding box dilated by the guard); false: the face is listed nowhere
+__device__ __forceinline__ bool face_cells(const ClusterGrid& g, int n_verts, const float* __restrict__ verts,
+                                           const int32_t* __restrict__ faces, int64_t f, int* i0, int* i1) {
+  int a, b, c;
+  if (!face_in_range(faces, f, n_verts, &a, &b, &c)) return false;
+  const float* pa = verts + (int64_t) a * 3;
+  const float* pb = verts + (int64_t) b * 3;
+  const float* pc = verts + (int64_t) c * 3;
+  if (!finite3(pa) || !finite3(pb) || !finite3(pc)) return false;
+  const float guard = ray_guard(g.cell);
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    i0[k] = ray_cell(g.lo[k], g.cell, g.dims[k], F2N_SUB_RN(fminf(fminf(pa[k], pb[k]), pc[k]), guard));
+    i1[k] = ray_cell(g.lo[k], g.cell, g.dims[k], F2N_ADD_RN(fmaxf(fmaxf(pa[k], pb[k]), pc[k]), guard));
+  }
+  return true;
+}
+
+__global__ void __launch_bounds__(256) raycast_count_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                           const int32_t* __restrict__ faces, ClusterGrid g, int32_t* __restrict__ counts,
+                                                           int32_t* flag) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  int a, b, c;
+  if (!face_in_range(faces, f, n_verts, &a, &b, &c)) *flag = 1;  // (benign race: every writer stores 1)
+  int i0[3], i1[3];
+  counts[f] = face_cells(g, n_verts, verts, faces, f, i0, i1) ? (i1[0] - i0[0] + 1) * (i1[1] - i0[1] + 1) * (i1[2] - i0[2] + 1) : 0;
+}
+
+__global__ void __launch_bounds__(256) raycast_fill_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                          const int32_t* __restrict__ faces, ClusterGrid g,
+                                                          const long long* __restrict__ offsets, long long* __restrict__ keys) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  int i0[3], i1[3];
+  if (!face_cells(g, n_verts, verts, faces, f, i0, i1)) return;
+  long long at = offsets[f];
+  for (int z = i0[2]; z <= i1[2]; z++)
+    for (int y = i0[1]; y <= i1[1]; y++)
+      for (int x = i0[0]; x <= i1[0]; x++) keys[at++] = (((long long) z * g.dims[1] + y) * g.dims[0] + x) * n_faces + f;
+}
+
+__global__ void __launch_bounds__(256) raycast_traverse_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                              const int32_t* __restrict__ faces, ClusterGrid g,
+                                                              const int32_t* __restrict__ cell_start, const int32_t* __restrict__ cell_faces,
+                                                              int n_rays, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                              const float* __restrict__ bounds, float* __restrict__ out_t,
+                                                              int32_t* __restrict__ out_face, float* __restrict__ out_bary) {
+  const int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rays) return;
+  const RayFrame fr = ray_frame(rays_o, rays_d, bounds, r);
+  RayHit h = {0.f, 0.f, 0.f, 0.f, -1};
+  if (fr.ok) {
+    const float lox = sel3(fr.kx, g.lo[0], g.lo[1], g.lo[2]), loy = sel3(fr.ky, g.lo[0], g.lo[1], g.lo[2]);
+    const float loz = sel3(fr.kz, g.lo[0], g.lo[1], g.lo[2]);
+    const int nx = sel3i(fr.kx, g.dims[0], g.dims[1], g.dims[2]), ny = sel3i(fr.ky, g.dims[0], g.dims[1], g.dims[2]);
+    const int nz = sel3i(fr.kz, g.dims[0], g.dims[1], g.dims[2]);
+    const int s1 = g.dims[0], s2 = g.dims[0] * g.dims[1];
+    const int sx = sel3i(fr.kx, 1, s1, s2), sy = sel3i(fr.ky, 1, s1, s2), sz = sel3i(fr.kz, 1, s1, s2);
+    const float guard = ray_guard(g.cell), margin = F2N_MUL_RN(fabsf(fr.Sz), guard);
+    const bool up = fr.Sz > 0.f;
+    for (int step = 0; step < nz; step++) {
+      const int L = up ? step : nz - 1 - step;
+      const float z_lo = F2N_ADD_RN(loz, F2N_MUL_RN((float) L, g.cell)), z_hi = F2N_ADD_RN(loz, F2N_MUL_RN((float) (L + 1), g.cell));
+      const float q_in = F2N_SUB_RN(up ? z_lo : z_hi, fr.oz), q_out = F2N_SUB_RN(up ? z_hi : z_lo, fr.oz);
+      const float t_in = F2N_MUL_RN(fr.Sz, q_in), t_out = F2N_MUL_RN(fr.Sz, q_out);
+      // every comparison is false for a NaN: the walk then goes on, which is the conservative side
+      if (F2N_SUB_RN(t_in, margin) > fr.t_max) break;                   // the window ends before this layer
+      if (h.face >= 0 && h.t < F2N_SUB_RN(t_in, margin)) break;         // no face of this or a later layer can be nearer, or as near
+      if (F2N_ADD_RN(t_out, margin) < fr.t_min) continue;               // the window begins behind this layer
+      const float x_in = F2N_ADD_RN(fr.ox, F2N_MUL_RN(fr.Sx, q_in)), x_out = F2N_ADD_RN(fr.ox, F2N_MUL_RN(fr.Sx, q_out));
+      const float y_in = F2N_ADD_RN(fr.oy, F2N_MUL_RN(fr.Sy, q_in)), y_out = F2N_ADD_RN(fr.oy, F2N_MUL_RN(fr.Sy, q_out));
+      const int ix0 = ray_cell(lox, g.cell, nx, F2N_SUB_RN(fminf(x_in, x_out), guard));
+      const int ix1 = ray_cell(lox, g.cell, nx, F2N_ADD_RN(fmaxf(x_in, x_out), guard));
+      const int iy0 = ray_cell(loy, g.cell, ny, F2N_SUB_RN(fminf(y_in, y_out), guard));
+      const int iy1 = ray_cell(loy, g.cell, ny, F2N_ADD_RN(fmaxf(y_in, y_out), guard));
+      for (int iy = iy0; iy <= iy1; iy++)
+        for (int ix = ix0; ix <= ix1; ix++) {
+          const int c = L * sz + iy * sy + ix * sx;
+          const int e1 = cell_start[c + 1];
+          for (int e = cell_start[c]; e < e1; e++) {
+            const int f = cell_faces[e];
+            int a, b, cc;
+            if (f < 0 || f >= n_faces || !face_in_range(faces, f, n_verts, &a, &b, &cc)) continue;
+            const float* pa = verts + (int64_t) a * 3;
+            const float* pb = verts + (int64_t) b * 3;
+            const float* pc = verts + (int64_t) cc * 3;
+            ray_face(fr, f, pa[0], pa[1], pa[2], pb[0], pb[1], pb[2], pc[0], pc[1], pc[2], &h);
+          }
+        }
+    }
+  }
+  ray_store(h, r, out_t, out_face, out_bary);
+}
+
+bool raycast_grid_ok(const float* lo, float cell, const int32_t* dims, ClusterGrid* g) {
+  if (!cluster_grid_ok(lo, cell, dims, g)) return false;
+  return (int64_t) dims[0] * dims[1] * dims[2] <= F2N_RAYCAST_MAX_CELLS;
+}
+
+}  // namespace
+
+int f2n_mesh_raycast_count(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, const float* lo, float cell,
+                           const int32_t* dims, int32_t* counts, int32_t* flag) {
+  ClusterGrid g;
+  if (n_verts < 0 || n_faces < 0 || !raycast_grid_ok(lo, cell, dims, &g) ||
+      (n_faces > 0 && (n_verts == 0 || verts == nullptr || faces == nullptr || counts == nullptr || flag == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n_faces == 0) return F2N_OK;
+  hipStream_t st = (hipStream_t) stream;
+  if (hipMemsetAsync(flag, 0, sizeof(int32_t), st) != hipSuccess) return f2n_launch_status();
+  hipLaunchKernelGGL(raycast_count_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, st, n_verts, n_faces, verts, faces, g, counts, flag);
+  int e = f2n_launch_status();
+  if (e != F2N_OK) return e;
+  int32_t bad = 0;
+  if (hipMemcpyAsync(&bad, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return f2n_launch_status();
+  return bad != 0 ? F2N_ERR_INVALID_ARG : F2N_OK;
+}
+
+int f2n_mesh_raycast_fill(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, const float* lo, float cell,
+                          const int32_t* dims, const int64_t* offsets, int64_t* keys) {
+  ClusterGrid g;
+  if (n_verts < 0 || n_faces < 0 || !raycast_grid_ok(lo, cell, dims, &g) ||
+      (n_faces > 0 && (n_verts == 0 || verts == nullptr || faces == nullptr || offsets == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n_faces == 0 || keys == nullptr) return F2N_OK;  // (keys may be NULL when no face is listed anywhere)
+  hipLaunchKernelGGL(raycast_fill_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, (hipStream_t) stream, n_verts, n_faces, verts, faces,
+                     g, (const long long*) offsets, (long long*) keys);
+  return f2n_launch_status();
+}
+
+int f2n_mesh_raycast(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, const float* lo, float cell,
+                     const int32_t* dims, const int32_t* cell_start, const int32_t* cell_faces, int n_rays, const float* rays_o,
+                     const float* rays_d, const float* bounds, float* out_t, int32_t* out_face, float* out_bary) {
+  ClusterGrid g;
+  if (n_verts < 0 || n_faces < 0 || n_rays < 0 || (cell_start != nullptr && !raycast_grid_ok(lo, cell, dims, &g)) ||
+      (n_faces > 0 && (n_verts == 0 || verts == nullptr || faces == nullptr)) ||
+      (n_rays > 0 && (rays_o == nullptr || rays_d == nullptr || out_t == nullptr || out_face == nullptr || out_bary == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (cell_start != nullptr)  // the part of the traversal's domain that is host data: the box within 2^15 cells of the origin of the frame
+    for (int k = 0; k < 3; k++)
+      if (!(fmaxf(fabsf(lo[k]), fabsf(lo[k] + (float) dims[k] * cell)) <= F2N_RAYCAST_DOMAIN_CELLS * cell)) return F2N_ERR_UNSUPPORTED;
+  if (n_rays == 0) return F2N_OK;
+  hipStream_t st = (hipStream_t) stream;
+  if (n_faces > 0) {  // the index check, with out_face[0] as its flag word
+    if (hipMemsetAsync(out_face, 0, sizeof(int32_t), st) != hipSuccess) return f2n_launch_status();
+    hipLaunchKernelGGL(raycast_check_faces_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, st, n_verts, n_faces, faces, out_face);
+    int32_t bad = 0;
+    if (hipMemcpyAsync(&bad, out_face, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return f2n_launch_status();
+    if (bad != 0) return F2N_ERR_INVALID_ARG;
+  }
+  const dim3 grid(f2n_div_up(n_rays, 256)), block(256);
+  if (cell_start == nullptr || n_faces == 0)
+    hipLaunchKernelGGL(raycast_brute_kernel, grid, block, 0, st, n_verts, n_faces, verts, faces, n_rays, rays_o, rays_d, bounds, out_t, out_face,
+                       out_bary);
+  else  // (cell_faces may be NULL when every list is empty: it is then never read)
+    hipLaunchKernelGGL(raycast_traverse_kernel, grid, block, 0, st, n_verts, n_faces, verts, faces, g, cell_start, cell_faces, n_rays, rays_o,
+                       rays_d, bounds, out_t, out_face, out_bary);
+  return f2n_launch_status();
+}

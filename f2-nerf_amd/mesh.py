@@ -20,6 +20,10 @@ Options (hydra-style overrides, no `mesh` group in the configs):
                    (host.mesh_simplify; default 0: off) after the floater removal and before normals and colours, which are computed
                    at the new vertices -> <iter>_<res>_s<k>.ply (<iter>_<res>_tsdf_s<k>.ply).  One vertex per occupied cell: features
                    thinner than a cell become two-sided sheets or non-manifold edges, never holes
+  mesh.check       true: after the .ply is written the mesh is compared with the field it came from, seen from the training cameras
+                   (check_mesh: the field's surface distance per ray against a ray cast at the mesh, host.mesh_raycast) ->
+                   <same name>_check.json and one printed line; options check.res_level (4), check.tau (0.5), check.min_opacity (0.5),
+                   check.max_views (0: all), with the meaning of their tsdf.* namesakes.  Default false: nothing changes
   mesh.source      density | tsdf (default density): the iso-surface of the raw density at mesh.level, or the zero crossing of a
                    truncated signed distance field fused from the training views' rendered depth (fuse_tsdf; mesh.level is not
                    used, normals of source "grid" come from the TSDF) -> <exp>/meshes/<iter>_<res>_tsdf.ply
@@ -342,7 +346,136 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
     write_ply(path, v, faces.cpu().numpy(), normals, colors)
     print("Mesh: %d vertices, %d faces%s from the TSDF of %d views (%d of %d grid points known, truncation %g) -> %s" % (
         len(v), len(faces), _simplified(k, faces_in), t["n_views"], int(t["valid"].sum()), t["valid"].numel(), t["trunc"], path))
+    if check_options(cfg)["check"]:
+        _run_check(runner, cfg, scene, dataset, verts, faces, t["step"], path)
     return path
+
+
+def check_options(cfg):
+    """mesh.check and the check.* options.  The defaults mirror tsdf.*; none of them is measured on a scene."""
+    m = cfg.get("mesh") or {}
+    c = cfg.get("check") or {}
+    o = {"check": _flag(m.get("check", False)), "res_level": int(c.get("res_level", 4)), "tau": float(c.get("tau", 0.5)),
+         "min_opacity": float(c.get("min_opacity", 0.5)), "max_views": int(c.get("max_views", 0))}
+    if o["res_level"] < 1 or o["max_views"] < 0 or not 0.0 < o["tau"] <= 1.0 or not o["min_opacity"] >= 0.0:
+        raise ValueError("check.res_level must be >= 1, check.max_views >= 0, check.tau in (0, 1] and check.min_opacity >= 0, got %r" % (o,))
+    return o
+
+
+def render_mesh(verts, faces, rays_o, rays_d, bounds=None, accel=None, normals=None, colors=None):
+    """The mesh seen along rays (host.mesh_raycast; accel None: one is built with the default cell): dict of hit [R] bool, t [R],
+    face [R] int32 (-1: none), bary [R,3], points (o + t d), face_normals (the unit geometric normal of the hit face, (B - A) x (C - A)),
+    facing (-n.d > 0: the ray meets the face's front) and, for per-vertex normals / colors [V,3], their barycentric blend at the hit
+    (the normal renormalised).  Rows without a hit are zero.  Everything but the ray cast is plain torch."""
+    import torch
+    from . import runtime
+    host = runtime.host()
+    if accel is None:
+        accel = host.mesh_raycast_build(verts, faces)
+    t, face, bary = host.mesh_raycast(verts, faces, accel, rays_o, rays_d, bounds)
+    hit = face >= 0
+    out = {"hit": hit, "t": t, "face": face, "bary": bary}
+    R = int(t.shape[0])
+    zero3 = torch.zeros((R, 3), dtype=torch.float32, device=t.device)
+    if int(faces.shape[0]) == 0 or R == 0:
+        out.update(points=zero3, face_normals=zero3.clone(), facing=torch.zeros_like(hit))
+        for name, attr in (("normals", normals), ("colors", colors)):
+            if attr is not None:
+                out[name] = zero3.clone()
+        return out
+    v = verts.to(torch.float32).reshape(-1, 3)
+    corners = faces.reshape(-1, 3).long()[face.clamp_min(0).long()]  # [R,3]
+    P = v[corners]  # [R,3,3]
+    n = torch.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0], dim=1)
+    ln = n.norm(dim=1, keepdim=True)
+    n = torch.where(hit[:, None] & (ln > 0), n / ln.clamp_min(1e-38), zero3)
+    rd = rays_d.to(torch.float32).reshape(-1, 3)
+    out["points"] = torch.where(hit[:, None], rays_o.to(torch.float32).reshape(-1, 3) + t[:, None] * rd, zero3)
+    out["face_normals"] = n
+    out["facing"] = hit & (-(n * rd).sum(1) > 0)
+    for name, attr in (("normals", normals), ("colors", colors)):
+        if attr is not None:
+            x = (attr.to(torch.float32).reshape(-1, 3)[corners] * bary[:, :, None]).sum(1)
+            if name == "normals":
+                lx = x.norm(dim=1, keepdim=True)
+                x = torch.where(lx > 0, x / lx.clamp_min(1e-38), zero3)
+            out[name] = torch.where(hit[:, None], x, zero3)
+    return out
+
+
+def compare_depth(t_field, has_field, t_mesh, has_mesh, step):
+    """Depth of a mesh against the field's along the same rays, a pure function of its tensors: counts n_rays, n_field, n_mesh, n_both;
+    completeness = n_both / n_field; extra = the share of rays where only the mesh has a surface; over the rays where both have one,
+    e = |t_mesh - t_field| / step (float32): mean, median, p90, max, within_1 / within_2 (the share with e <= 1 / e <= 2).  The quantile q
+    is the element min(n - 1, floor(q n)) of the ascending errors: a sort, no interpolation.  Empty classes give 0, never NaN."""
+    import torch
+    tf, tm = t_field.reshape(-1).to(torch.float32), t_mesh.reshape(-1).to(torch.float32)
+    hf, hm = has_field.reshape(-1).bool(), has_mesh.reshape(-1).bool()
+    both = hf & hm
+    e = torch.sort((tm[both] - tf[both]).abs() / torch.tensor(float(step), dtype=torch.float32, device=tf.device))[0]
+    n, nf, nm, nb = int(tf.numel()), int(hf.sum()), int(hm.sum()), int(both.sum())
+    share = lambda a, b: float(a) / float(b) if b else 0.0  # noqa: E731
+    at = lambda q: float(e[min(nb - 1, int(np.floor(q * nb)))]) if nb else 0.0  # noqa: E731
+    return {"n_rays": n, "n_field": nf, "n_mesh": nm, "n_both": nb, "completeness": share(nb, nf), "extra": share(int((hm & ~hf).sum()), n),
+            "mean": float(e.double().mean()) if nb else 0.0, "median": at(0.5), "p90": at(0.9), "max": float(e[-1]) if nb else 0.0,
+            "within_1": share(int((e <= 1).sum()), nb), "within_2": share(int((e <= 2).sum()), nb)}
+
+
+def check_mesh(runner, dataset, scene, verts, faces, o):
+    """A mesh (verts, faces in the NORMALISED frame, before to_world) against the field it came from, seen from the training cameras: for
+    every checked camera the rays of tsdf_camera_rays at o["res_level"] are rendered (runner.render_geometry: has_field = a surface
+    sample with opacity >= o["min_opacity"], t_field = surf_t) and cast at the mesh (render_mesh, the same rays and bounds).  Returns the
+    pooled compare_depth statistics in grid steps of o["step"], plus faces_seen (the share of faces that are some checked ray's first
+    hit), normal_agreement (the mean |face normal . surface normal| where both have a surface), n_views, n_faces and views (the
+    per-view statistics).  No side effect on training: nothing is drawn, no vote is cast, a pending step is flushed first."""
+    import torch
+    from . import runtime
+    host = runtime.host()
+    runner.flush()
+    views = [int(v) for v in scene["train_set"]]
+    if o["max_views"] > 0:
+        views = views[:o["max_views"]]
+    nf = int(faces.shape[0])
+    accel = host.mesh_raycast_build(verts, faces)
+    seen = torch.zeros(nf + 1, dtype=torch.bool, device=verts.device)
+    pool = {k: [] for k in ("tf", "hf", "tm", "hm", "agree")}
+    per_view = []
+    for idx in views:
+        ro, rd, b, _, _ = tsdf_camera_rays(dataset, scene["bounds"], idx, int(o["res_level"]))
+        g = runner.render_geometry(ro, rd, b, tau=o["tau"])
+        hf = (g["surf_idx"] >= 0) & (g["opacity"] >= o["min_opacity"])
+        m = render_mesh(verts, faces, ro, rd, b, accel=accel)
+        seen[torch.where(m["hit"], m["face"], torch.full_like(m["face"], nf)).long()] = True
+        agree = (m["face_normals"] * g["surf_normals"]).sum(1).abs()[hf & m["hit"]]
+        stats = compare_depth(g["surf_t"], hf, m["t"], m["hit"], o["step"])
+        stats["view"] = idx
+        stats["normal_agreement"] = float(agree.double().mean()) if agree.numel() else 0.0
+        per_view.append(stats)
+        for k, x in (("tf", g["surf_t"]), ("hf", hf), ("tm", m["t"]), ("hm", m["hit"]), ("agree", agree)):
+            pool[k].append(x)
+    cat = lambda k, dt: torch.cat(pool[k]) if pool[k] else torch.zeros(0, dtype=dt, device=verts.device)  # noqa: E731
+    out = compare_depth(cat("tf", torch.float32), cat("hf", torch.bool), cat("tm", torch.float32), cat("hm", torch.bool), o["step"])
+    agree = cat("agree", torch.float32)
+    out.update(faces_seen=float(int(seen[:nf].sum())) / nf if nf else 0.0, normal_agreement=float(agree.double().mean()) if agree.numel() else 0.0,
+               n_views=len(views), n_faces=nf, step=float(o["step"]), res_level=int(o["res_level"]), tau=float(o["tau"]),
+               min_opacity=float(o["min_opacity"]), views=per_view)
+    return out
+
+
+def _run_check(runner, cfg, scene, dataset, verts, faces, step, path):
+    """mesh.check=true: check_mesh of the mesh just written -> <path without .ply>_check.json and one printed line."""
+    import json
+    if dataset is None:
+        raise ValueError("mesh.check=true casts the training cameras' rays at the mesh: it needs the data set")
+    o = check_options(cfg)
+    o["step"] = float(step)
+    res = check_mesh(runner, dataset, scene, verts, faces, o)
+    out = path[:-4] + "_check.json"
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1, sort_keys=True)
+    print("Check: completeness %.4f, depth error median %.3f / p90 %.3f grid steps, extra %.4f, faces seen %.4f (%d views at 1/%d) -> %s" % (
+        res["completeness"], res["median"], res["p90"], res["extra"], res["faces_seen"], res["n_views"], o["res_level"], out))
+    return out
 
 
 def _simplified(k, faces_in):
@@ -370,4 +503,8 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
         write_ply(path, v, faces.cpu().numpy(), m["normals"].cpu().numpy() if o["normals"] else None,
                   m["colors"].cpu().numpy() if o["colors"] else None)
     print("Mesh: %d vertices, %d faces%s at level %g -> %s" % (len(v), len(faces), _simplified(k, faces_in), o["level"], path))
+    if check_options(cfg)["check"]:
+        from . import runtime
+        step = runtime.host().grid_spec([float(x) for x in o["bbox_min"]], [float(x) for x in o["bbox_max"]], int(o["resolution"]))[0]
+        _run_check(runner, cfg, scene, dataset, verts, faces, step, path)
     return path

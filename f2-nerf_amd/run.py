@@ -202,7 +202,8 @@ def main(argv=None):
                 save_png(os.path.join(exp_dir, "images", "%d_%d.png" % (runner.iter_step, idx)), runner.visualize_image(ds, idx))
         elif mode == "extract_mesh":  # no reference counterpart: <exp>/meshes/<iter>_<res>.ply (mesh.py; options mesh.*)
             from . import mesh
-            if mesh.options(cfg)["source"] == "tsdf":  # (fused from renders of the training cameras: the one source that needs them)
+            # (the TSDF is fused from renders of the training cameras, and mesh.check casts their rays at the mesh: both need them)
+            if mesh.options(cfg)["source"] == "tsdf" or mesh.check_options(cfg)["check"]:
                 mesh.extract(runner, cfg, sc, exp_dir, dataset=ds)
             else:
                 mesh.extract(runner, cfg, sc, exp_dir)

@@ -1049,6 +1049,63 @@ int f2n_mesh_cluster_place(void* stream, int n_clusters, const int64_t* acc /*[C
 int f2n_mesh_cluster_faces(void* stream, int n_verts, int n_faces, const int32_t* faces /*[F,3]*/, const int32_t* cluster_of /*[V]*/,
                            int32_t* out_faces /*[F,3]*/);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Ray casting against a triangle mesh (additive; the ABI version is unchanged).  The Woop-Benthin-Wald watertight test with the edge
+ * functions in fp64.  No reference counterpart.  csrc/octree.hip.
+ * ------------------------------------------------------------------------------------------------- */
+/* A ray is x = o + t d; d need not be unit length and t counts in units of d.  Its window (t_min, t_max) is bounds[r] or (0, +inf) for
+ * bounds == NULL.  For ray r and face (a, b, c) with vertices A, B, C every operation is ONE rounding of the stated width, never an FMA:
+ *   1. kz = the axis of the largest |d_k|, the first among equals in the order x, y, z (kz = 0; |d_1| > |d_kz|: kz = 1; |d_2| > |d_kz|:
+ *      kz = 2); kx = (kz + 1) % 3, ky = (kz + 2) % 3, swapped when d_kz < 0.  A ray with a component of d that is not finite, or with
+ *      d_kz == 0, hits nothing.
+ *   2. fp32: Sx = d_kx / d_kz, Sy = d_ky / d_kz, Sz = 1 / d_kz.
+ *   3. per vertex P, fp32: q = P - o;  x = q_kx - Sx q_kz;  y = q_ky - Sy q_kz;  z = Sz q_kz.
+ *   4. fp64: U = Cx By - Cy Bx;  V = Ax Cy - Ay Cx;  W = Bx Ay - By Ax  (the products of two floats are exact: every sign is exact).
+ *   5. inside iff (U, V, W all >= 0 or all <= 0) and det = (U + V) + W != 0  (a NaN is outside).
+ *   6. fp64: T = (U Az + V Bz) + W Cz;  t = (float) (T / det);  accepted iff t_min < t < t_max (a NaN fails).
+ *   7. bary = ((float) (U / det), (float) (V / det), (float) (W / det)).
+ *   8. the ray's result is its accepted face of the smallest t, of the lowest index among equal t: out_t, out_face, out_bary [R,3];
+ *      no accepted face: face = -1, t = 0, bary = 0.
+ * Consequences: two faces that share an edge see the same two transformed vertices and edge functions of exactly opposite sign, so
+ * no ray passes between them; a degenerate face (det == 0) and a face with a vertex that is not finite (t is a NaN) are never hit.
+ * The outputs of a ray are a function of that ray and the face list alone: not of the grid, its cell size, the rays' order or the
+ * schedule (no atomics: one lane owns one ray).
+ *
+ * The acceleration grid: origin lo (HOST [3]), cell size `cell`, dims (HOST [3]) as for f2n_mesh_cluster_keys, and additionally
+ * dims_x dims_y dims_z <= 2^27 (F2N_ERR_INVALID_ARG beyond).  i_k(p) = min(max(floor((p - lo_k) / cell), 0), dims_k - 1) (two fp32
+ * roundings, clamped as floats) is the cell of a coordinate; guard = cell * 2^-4.
+ *   f2n_mesh_raycast_count: counts [F] int32 = the number of cells that list face f: the box i_k(min_k - guard) .. i_k(max_k + guard) per
+ *     axis (min / max over its three vertices, one fp32 rounding each); 0 for a face with a vertex that is not finite.  A face index
+ *     outside [0, V): F2N_ERR_INVALID_ARG.  `flag` is one DEVICE word of scratch; the call READS IT BACK, so it synchronises the stream.
+ *   The caller forms offsets [F] int64 = the exclusive prefix sum of counts (plumbing), E = their total.
+ *   f2n_mesh_raycast_fill: keys [E] int64; face f writes (((int64) z dims_y + y) dims_x + x) * F + f for its cells (z, then y, then x
+ *     ascending) from keys[offsets[f]] on.  No atomics: keys is a function of the inputs.
+ *   The caller sorts keys ascending, cell_faces [E] int32 = key % F, cell_start [ncells + 1] int32 = the first position whose key is
+ *     >= cell * F (a searchsorted: plumbing).  E must fit an int32.
+ * f2n_mesh_raycast with cell_start == NULL (lo, cell, dims, cell_faces are then not read) is the BRUTE-FORCE mode: every ray tests every
+ * face (a block stages 256 faces at a time in LDS).  Otherwise one lane per ray walks the grid's layers along kz in the ray's
+ * direction; in layer L (planes z0 = lo_kz + L cell, z1 = lo_kz + (L + 1) cell; "in" the one the ray meets first) with q = z - o_kz:
+ *     t_in = Sz q_in, t_out = Sz q_out;  margin = |Sz| guard
+ *     stop if t_in - margin > t_max, or if a face is held and its t < t_in - margin;  skip the layer if t_out + margin < t_min
+ *     x_in = o_kx + Sx q_in, x_out = o_kx + Sx q_out (likewise y): the cells i_kx(min(x_in, x_out) - guard) .. i_kx(max + guard) times the
+ *     same range in ky are tested, every face of their lists by the steps above.
+ *   Domain (DESIGN.md section 3 gives the argument): every face vertex lies inside the grid box, and M = the largest absolute value among
+ *   the coordinates of lo, lo + dims cell and the ray origins is at most 2^15 cell.  Within it the traversal tests every face that the
+ *   brute-force mode could return, ties of equal t included, so the two modes agree bit for bit.  The box part of the domain is checked
+ *   here (F2N_ERR_UNSUPPORTED); the origins are device data and are the caller's to check (the host layer does, with one reduction).
+ * A face index outside [0, V): F2N_ERR_INVALID_ARG (out_face[0] is the flag word of that check before the rays are cast; the call READS
+ * IT BACK, so it synchronises the stream).  n_rays == 0: F2N_OK, nothing is touched.  F == 0: every ray misses. */
+int f2n_mesh_raycast_count(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/,
+                           const float* lo /*host [3]*/, float cell, const int32_t* dims /*host [3]*/, int32_t* counts /*[F]*/,
+                           int32_t* flag /*[1]*/);
+int f2n_mesh_raycast_fill(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/,
+                          const float* lo /*host [3]*/, float cell, const int32_t* dims /*host [3]*/, const int64_t* offsets /*[F]*/,
+                          int64_t* keys /*[E]*/);
+int f2n_mesh_raycast(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/,
+                     const float* lo /*host [3]*/, float cell, const int32_t* dims /*host [3]*/, const int32_t* cell_start /*[ncells+1] or NULL*/,
+                     const int32_t* cell_faces /*[E]*/, int n_rays, const float* rays_o /*[R,3]*/, const float* rays_d /*[R,3]*/,
+                     const float* bounds /*[R,2] or NULL*/, float* out_t /*[R]*/, int32_t* out_face /*[R]*/, float* out_bary /*[R,3]*/);
+
 #ifdef __cplusplus
 }
 #endif
