@@ -376,6 +376,17 @@ def field_fwd(n, n_volumes, table_h, prim_pool, local_idx, local_size, bias_pool
                             _p(out_f0, "f32", True), _p(save_x_h, "h16", True)), "f2n_field_fwd")
 
 
+def field_fwd_ex(n, n_volumes, table_h, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped, volume_idx,
+                 vol_stride, mlp_params_h, out_feat, out_f0, save_x_h, out_feat_h, fused=False):
+    """f2n_field_fwd_ex / f2n_field_fwd_fused_ex (include/f2n_abi.h, "Reuse of the density pre-pass's field outputs"): field_fwd
+    with out_feat_h [n,16] h16, the network's outputs at their f16 output precision."""
+    fn, name = (lib().f2n_field_fwd_fused_ex, "f2n_field_fwd_fused_ex") if fused else (lib().f2n_field_fwd_ex, "f2n_field_fwd_ex")
+    _ck(fn(_stream(), _i(n), _i(n_volumes), _p(table_h, "h16"), _p(prim_pool, "i32"), _p(local_idx, "i32"),
+           _p(local_size, "i32"), _p(bias_pool, "f32"), _p(level_scale, "f32"), _p(pts_warped, "f32"),
+           _p(volume_idx, "i32"), _i(vol_stride), _p(mlp_params_h, "h16"), _p(out_feat, "f32", True),
+           _p(out_f0, "f32", True), _p(save_x_h, "h16", True), _p(out_feat_h, "h16", True)), name)
+
+
 def hash_gather_planes(n, n_volumes, table_h, prim_pool, local_idx, local_size, bias_pool, level_scale, pts, pts_are_warped,
                        volume_idx, vol_stride, planes_h):
     _ck(lib().f2n_hash_gather_planes(_stream(), _i(n), _i(n_volumes), _p(table_h, "h16"), _p(prim_pool, "i32"),
@@ -421,6 +432,13 @@ def field_mlp_planes(n, planes_h, mlp_params_h, out_feat, out_f0, save_x_h):
                                    _p(out_f0, "f32", True), _p(save_x_h, "h16", True)), "f2n_field_mlp_planes")
 
 
+def field_mlp_planes_ex(n, planes_h, mlp_params_h, out_feat, out_f0, save_x_h, out_feat_h):
+    """f2n_field_mlp_planes_ex: field_mlp_planes with out_feat_h [n,16] h16 (the pre-pass's field outputs, kept for shade_fwd_feat)."""
+    _ck(lib().f2n_field_mlp_planes_ex(_stream(), _i(n), _p(planes_h, "h16"), _p(mlp_params_h, "h16"), _p(out_feat, "f32", True),
+                                      _p(out_f0, "f32", True), _p(save_x_h, "h16", True), _p(out_feat_h, "h16", True)),
+        "f2n_field_mlp_planes_ex")
+
+
 def field_fwd_cached(n, n_cache, src_rows, x_cache_h, mlp_params_h, out_feat, out_f0, save_x_h):
     _ck(lib().f2n_field_fwd_cached(_stream(), _i(n), _i(n_cache), _p(src_rows, "i32", True), _p(x_cache_h, "h16"),
                                    _p(mlp_params_h, "h16"), _p(out_feat, "f32", True), _p(out_f0, "f32", True),
@@ -461,6 +479,17 @@ def field_shade_fwd(n, src_rows, x_cache_h, field_params_h, dirs, app_emb, sampl
                                         _p(save_field_x_h, "h16", True), _p(save_shade_x_h, "h16", True), _p(rgb, "f32"), _i(n_extra),
                                         _p(x_extra_h, "h16", True), _p(feat_extra, "f32", True), _p(save_x_extra_h, "h16", True)),
         "f2n_field_shade_fwd_extra")
+
+
+def shade_fwd_feat(n, src_rows, feat_cache_h, dirs, app_emb, sample_emb_idx, color_params_h, out_f0, save_shade_x_h, rgb, n_dev=None,
+                   feat_extra_h=None, feat_extra=None):
+    """f2n_shade_fwd_feat: field_shade_fwd's colour path from the pre-pass's cached field outputs feat_cache_h [*,16] h16 (no field
+    network); the extra (edge) rows feat_extra_h [n_extra,16] h16 are widened into feat_extra fp32."""
+    n_extra = 0 if feat_extra_h is None else feat_extra_h.shape[0]
+    _ck(lib().f2n_shade_fwd_feat(_stream(), _i(n), _p(n_dev, "i32", True), _p(src_rows, "i32", True), _p(feat_cache_h, "h16"),
+                                 _p(dirs, "f32"), _p(app_emb, "f32", True), _p(sample_emb_idx, "i32", True), _p(color_params_h, "h16"),
+                                 _p(out_f0, "f32", True), _p(save_shade_x_h, "h16", True), _p(rgb, "f32"), _i(n_extra),
+                                 _p(feat_extra_h, "h16", True), _p(feat_extra, "f32", True)), "f2n_shade_fwd_feat")
 
 
 def shade_bwd(n, drgb, sample_emb_idx, mlp_params_h, saved_x_h, loss_scale, dfeat, dparams_scaled, dapp_emb, df0=None):
@@ -639,6 +668,19 @@ def field_bwd_dyn(n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_si
                                 _p(grad_table_h, "h16"), _i(level_entries), _i(int(defer_reduce))), "f2n_field_bwd_dyn")
 
 
+def field_bwd_dyn_rows(n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped, volume_idx,
+                       vol_stride, mlp_params_h, x_edge_h, x_cache_h, src_rows, dfeat, loss_scale, dparams_scaled, grad_table_h,
+                       level_entries, defer_reduce):
+    """f2n_field_bwd_dyn_rows: field_bwd_dyn whose input rows are read in place -- rows < n_off from x_edge_h [n_off,32] (None when
+    n_off == 0), row s >= n_off = row src_rows[s - n_off] of x_cache_h (the pre-pass feature cache)."""
+    _ck(lib().f2n_field_bwd_dyn_rows(_stream(), _i(n_max), _p(n_dev, "i32", True), _i(n_off), _i(n_volumes), _p(prim_pool, "i32"),
+                                     _p(local_idx, "i32"), _p(local_size, "i32"), _p(bias_pool, "f32"), _p(level_scale, "f32"),
+                                     _p(pts_warped, "f32"), _p(volume_idx, "i32"), _i(vol_stride), _p(mlp_params_h, "h16"),
+                                     _p(x_edge_h, "h16", True), _p(x_cache_h, "h16"), _p(src_rows, "i32"), _p(dfeat, "f32"),
+                                     _f(loss_scale), _p(dparams_scaled, "f32"), _p(grad_table_h, "h16"), _i(level_entries),
+                                     _i(int(defer_reduce))), "f2n_field_bwd_dyn_rows")
+
+
 class _StepTail(ctypes.Structure):
     _fields_ = [("n_flags_a", ctypes.c_int), ("flags_grad_a", ctypes.c_void_p), ("n_flags_b", ctypes.c_int), ("flags_grad_b", ctypes.c_void_p),
                 ("flags", ctypes.c_void_p), ("flags_mirror", ctypes.c_void_p), ("n_groups", ctypes.c_int), ("groups", ctypes.c_void_p),
@@ -651,10 +693,11 @@ class _StepTail(ctypes.Structure):
 def field_bwd_step_tail(n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped, volume_idx,
                         vol_stride, mlp_params_h, saved_x_h, dfeat, loss_scale, dparams_scaled, grad_table_h, level_entries, flags_a,
                         flags_b, flags, groups, table, step, lr, beta1, beta2, eps, tail_stream=None, flags_mirror=None, leave_table_to_caller=False,
-                        after_reduce=None):
+                        after_reduce=None, x_cache_h=None, src_rows=None):
     """f2n_field_bwd_step_tail: the field backward + the rest of the training step (deferred reductions, finiteness flags, Adam of
     `groups` (as adam_fused) and of `table` = {param, exp_avg, exp_avg_sq, param_h, grad_scale, n}) re-ordered around the scatter.
-    Returns 1 when the scatter's owners stepped the table."""
+    Returns 1 when the scatter's owners stepped the table.  x_cache_h / src_rows given: f2n_field_bwd_step_tail_rows, with
+    saved_x_h as its x_edge_h (rows < n_off; None when n_off == 0) -- see field_bwd_dyn_rows."""
     arr = (_AdamGroup * max(len(groups), 1))()
     for a, g in zip(arr, groups):
         a.param = _p(g["param"], "f32").value
@@ -683,6 +726,14 @@ def field_bwd_step_tail(n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, lo
         t.after_reduce = ctypes.cast(cb, ctypes.c_void_p).value
     by_owners = ctypes.c_int(0)
     ts = ctypes.c_void_p(tail_stream.cuda_stream) if tail_stream is not None else ctypes.c_void_p(0)
+    if x_cache_h is not None:
+        _ck(lib().f2n_field_bwd_step_tail_rows(_stream(), ts, _i(n_max), _p(n_dev, "i32", True), _i(n_off), _i(n_volumes), _p(prim_pool, "i32"),
+                                               _p(local_idx, "i32"), _p(local_size, "i32"), _p(bias_pool, "f32"), _p(level_scale, "f32"),
+                                               _p(pts_warped, "f32"), _p(volume_idx, "i32"), _i(vol_stride), _p(mlp_params_h, "h16"),
+                                               _p(saved_x_h, "h16", True), _p(x_cache_h, "h16"), _p(src_rows, "i32"), _p(dfeat, "f32"),
+                                               _f(loss_scale), _p(dparams_scaled, "f32"), _p(grad_table_h, "h16"), _i(level_entries),
+                                               ctypes.byref(t), ctypes.byref(by_owners)), "f2n_field_bwd_step_tail_rows")
+        return by_owners.value
     _ck(lib().f2n_field_bwd_step_tail(_stream(), ts, _i(n_max), _p(n_dev, "i32", True), _i(n_off), _i(n_volumes), _p(prim_pool, "i32"),
                                       _p(local_idx, "i32"), _p(local_size, "i32"), _p(bias_pool, "f32"), _p(level_scale, "f32"),
                                       _p(pts_warped, "f32"), _p(volume_idx, "i32"), _i(vol_stride), _p(mlp_params_h, "h16"),

@@ -1247,14 +1247,17 @@ union F2nBwdSmem {
 
 // HASH: 0 = MLP only (dL/dx to fp32), 1 = chained into the packed-f16 atomic scatter (small batches), 2 = dL/dx leaves as
 // f16 planes + non-zero mask for the owner-binned scatter.  BPC = resident blocks per CU the register budget is cut for.
-template <int NH, int HASH, int BPC>
-__global__ __launch_bounds__(F2N_BWD_THREADS, BPC) void field_bwd_kernel(
+// ROWS: the saved input is not a compact copy but the pre-pass feature cache read through a row index (f2n_field_bwd_dyn_rows):
+// row s >= n_off is x_cache row src_rows[s - n_off], row s < n_off (the edge samples in front) is x_h row s.
+template <int NH, int HASH, bool ROWS>
+__device__ __forceinline__ void f2n_field_bwd_body(
     int n, F2nHashArgs h, const int32_t* __restrict__ local_idx, const int32_t* __restrict__ local_size,
     const float* __restrict__ level_scale, const float* __restrict__ pts, int pts_are_warped,
     const int32_t* __restrict__ volume_idx, int vol_stride, const half_t* __restrict__ params,
     const half_t* __restrict__ x_h, const float* __restrict__ x_f32, const float* __restrict__ dy, float loss_scale,
     float* __restrict__ dparams, float* __restrict__ dx_f32, half_t* __restrict__ grad_table, half_t* __restrict__ dx_planes,
-    uint16_t* __restrict__ nz_mask, const int32_t* __restrict__ n_dev, int n_off) {
+    uint16_t* __restrict__ nz_mask, const int32_t* __restrict__ n_dev, int n_off, const half_t* __restrict__ x_cache,
+    const int32_t* __restrict__ src_rows) {
   F2N_RAISE_PRIO();
   const int n_alloc = n;  // plane stride / mask words: the allocated row count
   if (n_dev != nullptr) n = min(n, *n_dev + n_off);  // the row count is still on the device (f2n_field_bwd_dyn)
@@ -1276,18 +1279,33 @@ __global__ __launch_bounds__(F2N_BWD_THREADS, BPC) void field_bwd_kernel(
     half8_t xf;
     float4_t d4;
   };
-  auto fetch = [&](int tile, In& o) {
+  // ROWS: the cache row of a tile's sample is loaded a tile EARLIER than the row itself (as field_shade_fwd_kernel's fetch_idx /
+  // fetch), so that no load waits for another inside a round; -1 = an edge row, read from x_h
+  auto fetch_row = [&](int tile) {
     const int s = tile * 16 + c;
     const int sc = s < n ? s : n - 1;
-    o.xf = (x_h != nullptr) ? f2n_load_xfrag_h(x_h, sc, g, true) : f2n_load_xfrag_f32(x_f32, sc, g, true);
+    return sc < n_off ? -1 : src_rows[sc - n_off];
+  };
+  auto fetch = [&](int tile, int row, In& o) {
+    const int s = tile * 16 + c;
+    const int sc = s < n ? s : n - 1;
+    if (ROWS) o.xf = f2n_rowfrag(row >= 0 ? x_cache + (size_t) row * F2N_D_IN : x_h + (size_t) sc * F2N_D_IN, F2N_D_IN, 0, 0, g);
+    else o.xf = (x_h != nullptr) ? f2n_load_xfrag_h(x_h, sc, g, true) : f2n_load_xfrag_f32(x_f32, sc, g, true);
     o.d4 = *(const float4_t*) (dy + (size_t) sc * F2N_D_OUT + 4 * g);
   };
   const int n_tiles = (n + 15) / 16;
   In cur;
-  if (wave_global < n_tiles) fetch(wave_global, cur);
+  int row_next = 0;
+  if (wave_global < n_tiles) {
+    if (ROWS) row_next = fetch_row(wave_global);
+    fetch(wave_global, row_next, cur);
+    if (ROWS) row_next = fetch_row(wave_global + wave_stride < n_tiles ? wave_global + wave_stride : wave_global);
+  }
   for (int tile = wave_global; tile < n_tiles; tile += wave_stride) {
     In nxt;
-    fetch(tile + wave_stride < n_tiles ? tile + wave_stride : tile, nxt);  // last round: a harmless re-read
+    const int t1 = tile + wave_stride < n_tiles ? tile + wave_stride : tile;
+    fetch(t1, row_next, nxt);  // last round: a harmless re-read
+    if (ROWS) row_next = fetch_row(t1 + wave_stride < n_tiles ? t1 + wave_stride : t1);
     __builtin_amdgcn_sched_barrier(0);
     {
       F2nHalfBwd<NH> hb;
@@ -1341,6 +1359,33 @@ __global__ __launch_bounds__(F2N_BWD_THREADS, BPC) void field_bwd_kernel(
   }
   __syncthreads();  // everyone is done with the LDS weights: reuse the space for the block reduction
   f2n_mlp_flush_dw<NH>(acc, sm.acc, dparams, c, g, tid, F2N_BWD_THREADS);
+}
+
+template <int NH, int HASH, int BPC>
+__global__ __launch_bounds__(F2N_BWD_THREADS, BPC) void field_bwd_kernel(
+    int n, F2nHashArgs h, const int32_t* __restrict__ local_idx, const int32_t* __restrict__ local_size,
+    const float* __restrict__ level_scale, const float* __restrict__ pts, int pts_are_warped,
+    const int32_t* __restrict__ volume_idx, int vol_stride, const half_t* __restrict__ params,
+    const half_t* __restrict__ x_h, const float* __restrict__ x_f32, const float* __restrict__ dy, float loss_scale,
+    float* __restrict__ dparams, float* __restrict__ dx_f32, half_t* __restrict__ grad_table, half_t* __restrict__ dx_planes,
+    uint16_t* __restrict__ nz_mask, const int32_t* __restrict__ n_dev, int n_off) {
+  f2n_field_bwd_body<NH, HASH, false>(n, h, local_idx, local_size, level_scale, pts, pts_are_warped, volume_idx, vol_stride, params, x_h,
+                                      x_f32, dy, loss_scale, dparams, dx_f32, grad_table, dx_planes, nz_mask, n_dev, n_off, nullptr,
+                                      nullptr);
+}
+
+// The streaming step's field backward on the pre-pass cache itself (no compact copy of the survivors' rows exists).
+template <int HASH, int BPC>
+__global__ __launch_bounds__(F2N_BWD_THREADS, BPC) void field_bwd_rows_kernel(
+    int n, F2nHashArgs h, const int32_t* __restrict__ local_idx, const int32_t* __restrict__ local_size,
+    const float* __restrict__ level_scale, const float* __restrict__ pts, int pts_are_warped,
+    const int32_t* __restrict__ volume_idx, int vol_stride, const half_t* __restrict__ params,
+    const half_t* __restrict__ x_edge, const half_t* __restrict__ x_cache, const int32_t* __restrict__ src_rows,
+    const float* __restrict__ dy, float loss_scale, float* __restrict__ dparams, half_t* __restrict__ grad_table,
+    half_t* __restrict__ dx_planes, uint16_t* __restrict__ nz_mask, const int32_t* __restrict__ n_dev, int n_off) {
+  f2n_field_bwd_body<1, HASH, true>(n, h, local_idx, local_size, level_scale, pts, pts_are_warped, volume_idx, vol_stride, params, x_edge,
+                                    nullptr, dy, loss_scale, dparams, nullptr, grad_table, dx_planes, nz_mask, n_dev, n_off, x_cache,
+                                    src_rows);
 }
 
 // Stand-alone hash scatter (seam-level f2n_hash_bwd): grad_in is h16 [n,32].
@@ -1818,13 +1863,22 @@ int f2n_field_fwd(void* stream, int n, int n_volumes, const void* table_h, const
                   const int32_t* local_idx, const int32_t* local_size, const float* bias_pool, const float* level_scale,
                   const float* pts_warped, const int32_t* volume_idx, int vol_stride, const void* mlp_params_h,
                   float* out_feat_f32, float* out_f0, void* save_x_h) {
+  return f2n_field_fwd_ex(stream, n, n_volumes, table_h, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped, volume_idx,
+                          vol_stride, mlp_params_h, out_feat_f32, out_f0, save_x_h, nullptr);
+}
+
+int f2n_field_fwd_ex(void* stream, int n, int n_volumes, const void* table_h, const int32_t* prim_pool,
+                     const int32_t* local_idx, const int32_t* local_size, const float* bias_pool, const float* level_scale,
+                     const float* pts_warped, const int32_t* volume_idx, int vol_stride, const void* mlp_params_h,
+                     float* out_feat_f32, float* out_f0, void* save_x_h, void* out_feat_h) {
   if (n < 0 || n_volumes <= 0 || vol_stride < 1) return F2N_ERR_INVALID_ARG;
   if (n == 0) return F2N_OK;
   F2nHashArgs h = {(const half_t*) table_h, prim_pool, bias_pool, n_volumes};
   if (n < F2N_PARTITION_MIN_N) {  // small batches: one launch, features stay in registers between gather and MFMA
     hipLaunchKernelGGL((field_fwd_kernel<1, true, true>), dim3(f2n_wave_grid((n + 15) / 16, 4)), dim3(F2N_FWD_THREADS), 0,
                        (hipStream_t) stream, n, h, local_idx, local_size, level_scale, pts_warped, 1, volume_idx, vol_stride,
-                       nullptr, (const half_t*) mlp_params_h, out_feat_f32, nullptr, out_f0, (half_t*) save_x_h, nullptr, nullptr, nullptr, nullptr);
+                       nullptr, (const half_t*) mlp_params_h, out_feat_f32, (half_t*) out_feat_h, out_f0, (half_t*) save_x_h, nullptr, nullptr, nullptr,
+                       nullptr);
     return f2n_launch_status();
   }
   // large batches: XCD-aware level-partitioned gather into f16 planes (64 B/sample of internal workspace), then the
@@ -1834,7 +1888,7 @@ int f2n_field_fwd(void* stream, int n, int n_volumes, const void* table_h, const
   int rc = f2n_hash_gather_planes(stream, n, n_volumes, table_h, prim_pool, local_idx, local_size, bias_pool, level_scale,
                                   pts_warped, 1, volume_idx, vol_stride, planes);
   if (rc != F2N_OK) return rc;
-  return f2n_field_mlp_planes(stream, n, planes, mlp_params_h, out_feat_f32, out_f0, save_x_h);
+  return f2n_field_mlp_planes_ex(stream, n, planes, mlp_params_h, out_feat_f32, out_f0, save_x_h, out_feat_h);
 }
 
 // The one-kernel gather -> MLP of the small-batch path at ANY size (the north star's "features staged on-chip as the MFMA tile"):
@@ -1845,12 +1899,21 @@ int f2n_field_fwd_fused(void* stream, int n, int n_volumes, const void* table_h,
                         const int32_t* local_size, const float* bias_pool, const float* level_scale, const float* pts_warped,
                         const int32_t* volume_idx, int vol_stride, const void* mlp_params_h, float* out_feat_f32, float* out_f0,
                         void* save_x_h) {
+  return f2n_field_fwd_fused_ex(stream, n, n_volumes, table_h, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped,
+                                volume_idx, vol_stride, mlp_params_h, out_feat_f32, out_f0, save_x_h, nullptr);
+}
+
+int f2n_field_fwd_fused_ex(void* stream, int n, int n_volumes, const void* table_h, const int32_t* prim_pool, const int32_t* local_idx,
+                           const int32_t* local_size, const float* bias_pool, const float* level_scale, const float* pts_warped,
+                           const int32_t* volume_idx, int vol_stride, const void* mlp_params_h, float* out_feat_f32, float* out_f0,
+                           void* save_x_h, void* out_feat_h) {
   if (n < 0 || n_volumes <= 0 || vol_stride < 1) return F2N_ERR_INVALID_ARG;
   if (n == 0) return F2N_OK;
   F2nHashArgs h = {(const half_t*) table_h, prim_pool, bias_pool, n_volumes};
   hipLaunchKernelGGL((field_fwd_kernel<1, true, true>), dim3(f2n_wave_grid((n + 15) / 16, 4)), dim3(F2N_FWD_THREADS), 0,
                      (hipStream_t) stream, n, h, local_idx, local_size, level_scale, pts_warped, 1, volume_idx, vol_stride, nullptr,
-                     (const half_t*) mlp_params_h, out_feat_f32, nullptr, out_f0, (half_t*) save_x_h, nullptr, nullptr, nullptr, nullptr);
+                     (const half_t*) mlp_params_h, out_feat_f32, (half_t*) out_feat_h, out_f0, (half_t*) save_x_h, nullptr, nullptr, nullptr,
+                     nullptr);
   return f2n_launch_status();
 }
 
@@ -1991,12 +2054,17 @@ int f2n_hash_gather_planes_binned(void* stream, int n, int n_volumes, const void
 
 int f2n_field_mlp_planes(void* stream, int n, const void* planes_h, const void* mlp_params_h, float* out_feat_f32, float* out_f0,
                          void* save_x_h) {
+  return f2n_field_mlp_planes_ex(stream, n, planes_h, mlp_params_h, out_feat_f32, out_f0, save_x_h, nullptr);
+}
+
+int f2n_field_mlp_planes_ex(void* stream, int n, const void* planes_h, const void* mlp_params_h, float* out_feat_f32, float* out_f0,
+                            void* save_x_h, void* out_feat_h) {
   if (n < 0 || (n > 0 && planes_h == nullptr)) return F2N_ERR_INVALID_ARG;
   if (n == 0) return F2N_OK;
   F2nHashArgs h = {nullptr, nullptr, nullptr, 1};
   hipLaunchKernelGGL((field_fwd_kernel<1, false, true>), dim3(f2n_wave_grid((n + 15) / 16, 4)), dim3(F2N_FWD_THREADS), 0,
                      (hipStream_t) stream, n, h, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, nullptr,
-                     (const half_t*) mlp_params_h, out_feat_f32, nullptr, out_f0, (half_t*) save_x_h, (const half_t*) planes_h,
+                     (const half_t*) mlp_params_h, out_feat_f32, (half_t*) out_feat_h, out_f0, (half_t*) save_x_h, (const half_t*) planes_h,
                      nullptr, nullptr, nullptr);
   return f2n_launch_status();
 }
@@ -2067,11 +2135,14 @@ static int f2n_field_bwd_impl(void* stream, void* tail_stream, int n_max, const 
                               const float* level_scale, const float* pts_warped, const int32_t* volume_idx, int vol_stride,
                               const void* mlp_params_h, const void* saved_x_h, const float* dfeat, float loss_scale,
                               float* dparams_f32_scaled, void* grad_table_h, int level_entries, int defer_reduce,
-                              const F2nStepTail* tail, int* table_stepped) {
+                              const F2nStepTail* tail, int* table_stepped, const void* x_cache_h = nullptr,
+                              const int32_t* src_rows = nullptr) {
   const int n = n_max;
   if (table_stepped != nullptr) *table_stepped = 0;
   if (n < 0 || n_volumes <= 0 || vol_stride < 1 || !(loss_scale > 0.f) || level_entries < 0 || ((uintptr_t) mlp_params_h & 15))
     return F2N_ERR_INVALID_ARG;
+  // (the row-indexed input of the _rows entry points: edge rows [0, n_off) from saved_x_h, the rest through src_rows)
+  if (x_cache_h != nullptr && (src_rows == nullptr || n_off < 0 || n_off > n || (n_off > 0 && saved_x_h == nullptr))) return F2N_ERR_INVALID_ARG;
   if (tail != nullptr && (tail->flags == nullptr || tail->n_groups < 0 || tail->n_groups > 4 || tail->step < 1 || tail->n_table < 0 ||
                           (tail->n_table > 0 && (tail->table_param == nullptr || tail->table_exp_avg == nullptr ||
                                                  tail->table_exp_avg_sq == nullptr || tail->table_param_h == nullptr))))
@@ -2098,9 +2169,18 @@ static int f2n_field_bwd_impl(void* stream, void* tail_stream, int n_max, const 
                      local_idx, local_size, level_scale, pts_warped, 1, volume_idx, vol_stride, (const half_t*) mlp_params_h, \
                      (const half_t*) saved_x_h, nullptr, dfeat, loss_scale, partials, nullptr, (half_t*) grad_table_h,       \
                      dx_planes, nz_mask, n_dev, n_off)
-    if (!bins) F2N_LAUNCH_FIELD_BWD(1, 2);
+#define F2N_LAUNCH_FIELD_BWD_ROWS(HASH, BPC)                                                                                   \
+  hipLaunchKernelGGL((field_bwd_rows_kernel<HASH, BPC>), dim3(blocks), dim3(F2N_BWD_THREADS), 0, (hipStream_t) stream, n, h,   \
+                     local_idx, local_size, level_scale, pts_warped, 1, volume_idx, vol_stride, (const half_t*) mlp_params_h,  \
+                     (const half_t*) saved_x_h, (const half_t*) x_cache_h, src_rows, dfeat, loss_scale, partials,             \
+                     (half_t*) grad_table_h, dx_planes, nz_mask, n_dev, n_off)
+    if (x_cache_h != nullptr) {
+      if (!bins) F2N_LAUNCH_FIELD_BWD_ROWS(1, 2);
+      else F2N_LAUNCH_FIELD_BWD_ROWS(2, 3);
+    } else if (!bins) F2N_LAUNCH_FIELD_BWD(1, 2);
     else F2N_LAUNCH_FIELD_BWD(2, 3);
 #undef F2N_LAUNCH_FIELD_BWD
+#undef F2N_LAUNCH_FIELD_BWD_ROWS
     rc = f2n_launch_status();
     if (rc != F2N_OK) return rc;
     if (tail == nullptr && !defer_reduce) {
@@ -2194,6 +2274,29 @@ int f2n_field_bwd_step_tail(void* stream, void* tail_stream, int n_max, const in
   return f2n_field_bwd_impl(stream, tail_stream, n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_size, bias_pool, level_scale,
                             pts_warped, volume_idx, vol_stride, mlp_params_h, saved_x_h, dfeat, loss_scale, dparams_f32_scaled, grad_table_h,
                             level_entries, 1, tail, table_stepped_by_owners);
+}
+
+int f2n_field_bwd_dyn_rows(void* stream, int n_max, const int32_t* n_dev, int n_off, int n_volumes, const int32_t* prim_pool,
+                           const int32_t* local_idx, const int32_t* local_size, const float* bias_pool, const float* level_scale,
+                           const float* pts_warped, const int32_t* volume_idx, int vol_stride, const void* mlp_params_h,
+                           const void* x_edge_h, const void* x_cache_h, const int32_t* src_rows, const float* dfeat, float loss_scale,
+                           float* dparams_f32_scaled, void* grad_table_h, int level_entries, int defer_reduce) {
+  if (x_cache_h == nullptr) return F2N_ERR_INVALID_ARG;
+  return f2n_field_bwd_impl(stream, nullptr, n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped,
+                            volume_idx, vol_stride, mlp_params_h, x_edge_h, dfeat, loss_scale, dparams_f32_scaled, grad_table_h, level_entries,
+                            defer_reduce, nullptr, nullptr, x_cache_h, src_rows);
+}
+
+int f2n_field_bwd_step_tail_rows(void* stream, void* tail_stream, int n_max, const int32_t* n_dev, int n_off, int n_volumes,
+                                 const int32_t* prim_pool, const int32_t* local_idx, const int32_t* local_size, const float* bias_pool,
+                                 const float* level_scale, const float* pts_warped, const int32_t* volume_idx, int vol_stride,
+                                 const void* mlp_params_h, const void* x_edge_h, const void* x_cache_h, const int32_t* src_rows,
+                                 const float* dfeat, float loss_scale, float* dparams_f32_scaled, void* grad_table_h, int level_entries,
+                                 const F2nStepTail* tail, int* table_stepped_by_owners) {
+  if (tail == nullptr || x_cache_h == nullptr) return F2N_ERR_INVALID_ARG;
+  return f2n_field_bwd_impl(stream, tail_stream, n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_size, bias_pool, level_scale,
+                            pts_warped, volume_idx, vol_stride, mlp_params_h, x_edge_h, dfeat, loss_scale, dparams_f32_scaled, grad_table_h,
+                            level_entries, 1, tail, table_stepped_by_owners, x_cache_h, src_rows);
 }
 
 }  // extern "C"

@@ -294,27 +294,30 @@ Tensor Hash3DAnchored::AnchoredQueryReuse(const Tensor& points, const Tensor& an
   CheckDev(rows, torch::kInt32, "src_rows");
   TORCH_CHECK(n_reuse >= 0 && n_reuse <= pts.size(0) && rows.numel() >= n_reuse, "bad reuse range");
   if (!fused_ok_) {  // (no feature cache on the unfused path)
-    prepass_x_ = Tensor();
+    DropPrepassCache();
     return AnchoredQuery(pts, anchors);
   }
   Tensor feat = FieldFunction::apply(feat_pool_, mlp_->params_, pts, anchors, rows.slice(0, 0, n_reuse), (int64_t) n_reuse,
                                      reinterpret_cast<int64_t>(this))[0];
-  prepass_x_ = Tensor();  // one consumer per pre-pass; the table may change after this step
+  DropPrepassCache();  // one consumer per pre-pass; the table may change after this step
   return mlp_out_dim_ == F2N_MLP_OUT_PAD ? feat : feat.index({Slc(), Slc(0, mlp_out_dim_)}).contiguous();
 }
 
-Tensor Hash3DAnchored::QueryDensityPreAct(const Tensor& points, const Tensor& anchors, bool keep_features) {
+Tensor Hash3DAnchored::QueryDensityPreAct(const Tensor& points, const Tensor& anchors, bool keep_features, bool keep_outputs) {
   torch::NoGradGuard g;
   Tensor pts = points.contiguous();
   CheckDev(pts, torch::kFloat32, "points");
   AnchorView av = ViewAnchors(anchors);
   const int n = pts.size(0);
   if (!fused_ok_) {
-    prepass_x_ = Tensor();
+    DropPrepassCache();
     return mlp_->Query(HashEncode(pts, anchors)).select(1, 0).contiguous();
   }
   Tensor f0 = torch::empty({n}, DevF32());
   prepass_x_ = keep_features ? torch::empty({n, N_LEVELS * N_CHANNELS}, DevF16()) : Tensor();
+  // (only a streaming train step asks for the outputs: every other caller allocates and stores nothing more than before)
+  prepass_feat_h_ = keep_features && keep_outputs ? torch::empty({n, F2N_MLP_OUT_PAD}, DevF16()) : Tensor();
+  void* feat_h = prepass_feat_h_.defined() ? VoidP(prepass_feat_h_) : nullptr;
 #if F2N_DEBUG_BUILD
   static const bool force_fused = []() {  // measurement knob: the one-kernel gather -> MLP at every size (profiles/r04_fused_gather_ab.txt)
     const char* e = std::getenv("F2N_FUSED_GATHER");
@@ -324,9 +327,9 @@ Tensor Hash3DAnchored::QueryDensityPreAct(const Tensor& points, const Tensor& an
   constexpr bool force_fused = false;  // (measured to lose at every training size: profiles/r04_fused_gather_ab.txt)
 #endif
   if (force_fused) {
-    F2N_TIMED_CALL("field_prepass_fused", f2n_field_fwd_fused(CurStream(), n, n_volumes_, VoidP(feat_pool_h_), I32P(prim_pool_),
+    F2N_TIMED_CALL("field_prepass_fused", f2n_field_fwd_fused_ex(CurStream(), n, n_volumes_, VoidP(feat_pool_h_), I32P(prim_pool_),
                            I32P(feat_local_idx_), I32P(feat_local_size_), F32P(bias_pool_), F32P(level_scale_), F32P(pts), I32P(av.t),
-                           av.stride, VoidP(mlp_->params_h_), nullptr, F32P(f0), keep_features ? VoidP(prepass_x_) : nullptr));
+                           av.stride, VoidP(mlp_->params_h_), nullptr, F32P(f0), keep_features ? VoidP(prepass_x_) : nullptr, feat_h));
   } else if (n >= 32768) {  // the two kernels of the large-batch path, issued (and timed) separately
     Tensor planes = torch::empty({8, n, 4}, DevF16());
     // consecutive samples of a ray are one march step apart: sample_l * fineness in warped space (PersSampler.cu:262-270,
@@ -358,12 +361,12 @@ Tensor Hash3DAnchored::QueryDensityPreAct(const Tensor& points, const Tensor& an
                              I32P(feat_local_idx_), I32P(feat_local_size_), F32P(bias_pool_), F32P(level_scale_), F32P(pts), 1,
                              I32P(av.t), av.stride, VoidP(planes), balance_gather_ ? step01 : 0.f, level_scale_host_.data()));
     }
-    F2N_TIMED_CALL("field_mlp_prepass", f2n_field_mlp_planes(CurStream(), n, VoidP(planes), VoidP(mlp_->params_h_), nullptr, F32P(f0),
-                           keep_features ? VoidP(prepass_x_) : nullptr));
+    F2N_TIMED_CALL("field_mlp_prepass", f2n_field_mlp_planes_ex(CurStream(), n, VoidP(planes), VoidP(mlp_->params_h_), nullptr, F32P(f0),
+                           keep_features ? VoidP(prepass_x_) : nullptr, feat_h));
   } else {
-    F2N_TIMED_CALL("field_prepass", f2n_field_fwd(CurStream(), n, n_volumes_, VoidP(feat_pool_h_), I32P(prim_pool_), I32P(feat_local_idx_),
+    F2N_TIMED_CALL("field_prepass", f2n_field_fwd_ex(CurStream(), n, n_volumes_, VoidP(feat_pool_h_), I32P(prim_pool_), I32P(feat_local_idx_),
                            I32P(feat_local_size_), F32P(bias_pool_), F32P(level_scale_), F32P(pts), I32P(av.t), av.stride,
-                           VoidP(mlp_->params_h_), nullptr, F32P(f0), keep_features ? VoidP(prepass_x_) : nullptr));
+                           VoidP(mlp_->params_h_), nullptr, F32P(f0), keep_features ? VoidP(prepass_x_) : nullptr, feat_h));
   }
   return f0;
 }

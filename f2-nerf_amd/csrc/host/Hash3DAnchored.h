@@ -16,7 +16,10 @@ class Hash3DAnchored : public Field {
   Tensor AnchoredQuery(const Tensor& points, const Tensor& anchors) override;
   // no-grad density pre-activation only (channel 0) for Renderer's early-stop pre-pass
   // keep_features: also keep the gathered h16 hash features [n,32] of every point for AnchoredQueryReuse
-  Tensor QueryDensityPreAct(const Tensor& points, const Tensor& anchors, bool keep_features = false);
+  // keep_outputs (with keep_features): also keep the network's 16 f16 outputs [n,16] of every point (prepass_feat_h_) -- a
+  // streaming train step's grad pass starts its colour path from them instead of evaluating the network again
+  Tensor QueryDensityPreAct(const Tensor& points, const Tensor& anchors, bool keep_features = false, bool keep_outputs = false);
+  void DropPrepassCache() { prepass_x_ = Tensor(); prepass_feat_h_ = Tensor(); }
   // AnchoredQuery whose first n_reuse points are points src_rows[i] of the preceding QueryDensityPreAct (same table,
   // same coordinates): their 128 gathers are not repeated.  Bit-identical to AnchoredQuery(points, anchors).
   Tensor AnchoredQueryReuse(const Tensor& points, const Tensor& anchors, const Tensor& src_rows, int n_reuse);
@@ -54,6 +57,7 @@ class Hash3DAnchored : public Field {
   Tensor feat_local_idx_, feat_local_size_, level_scale_;
   bool grad_clean_ = false;  // grad_h_ is known to be all zero
   Tensor prepass_x_;       // h16 [n,32] features of the last QueryDensityPreAct(keep_features = true), or undefined
+  Tensor prepass_feat_h_;  // h16 [n,16] field outputs of the same rows (keep_outputs), or undefined; lives and dies with prepass_x_
   std::unique_ptr<FusedMLP> mlp_;
   int n_volumes_;
   std::vector<float> level_scale_host_;  // the 16 level scales again, for the gather's cost model (host side)

@@ -390,7 +390,7 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
         DigestTap(TAP_DT_PRE, sample_result_.dt);
         DigestTap(TAP_ANCHORS_PRE, sample_result_.anchors.select(1, 0));
       }
-      f0_full = field->QueryDensityPreAct(pts_full, anchors_full, /*keep_features=*/true);
+      f0_full = field->QueryDensityPreAct(pts_full, anchors_full, /*keep_features=*/true, /*keep_outputs=*/keep_prepass_outputs_);
       f0p = F32P(f0_full) + front;
       if (digest_taps_ && train) DigestTap(TAP_EDGE, pts_full.narrow(0, 0, front));
       fr.edge_cache_row = 0;
@@ -403,7 +403,7 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
         DigestTap(TAP_DT_PRE, sample_result_.dt);
         DigestTap(TAP_ANCHORS_PRE, sample_result_.anchors.select(1, 0));
       }
-      f0_full = field->QueryDensityPreAct(sample_result_.pts, sample_result_.anchors, /*keep_features=*/true);
+      f0_full = field->QueryDensityPreAct(sample_result_.pts, sample_result_.anchors, /*keep_features=*/true, /*keep_outputs=*/keep_prepass_outputs_);
       f0p = F32P(f0_full);
     }
     if (digest_taps_ && train) {
@@ -616,7 +616,7 @@ RenderResult Renderer::RenderForward(const Tensor& rays_o, const Tensor& rays_d,
                          static_cast<const void*>(field->prepass_x_.data_ptr<at::Half>() + (int64_t) N_LEVELS * N_CHANNELS * fr.sample_cache_row),
                          VoidP(field->mlp_->params_h_), F32P(es.dirs), nullptr, nullptr, VoidP(shader->mlp_->params_h_), F32P(f0c),
                          nullptr, nullptr, F32P(rgb)));
-  field->prepass_x_ = Tensor();
+  field->DropPrepassCache();
   Tensor colors = torch::empty({n_rays, 3}, DevF32()), disparity = torch::empty({n_rays}, DevF32());
   Tensor depth = torch::empty({n_rays}, DevF32()), weights = torch::empty({n_cap}, DevF32());
   Tensor bg = fr.bg_color.contiguous();

@@ -320,6 +320,13 @@ class Renderer : public Pipe {
   Tensor digest_tap_sums_;  // int64 [kDigestRing, N_TAPS]
   void DigestTap(int tap, const Tensor& t);
   bool async_count_ = false;        // set by ExpRunner::TrainStep for streaming steps
+  // A streaming train step's grad pass starts from the field outputs its own density pre-pass computed (same table, same weights,
+  // same h16 features: the same bits) instead of evaluating the field network a second time, and its field backward reads the
+  // pre-pass feature cache through the survivors' row index instead of a copy (ExpRunner.prepass_feat_reuse; false = the
+  // field_shade_fwd / compact field_x path, bit-identical results).  Host-side and data-independent.
+  bool prepass_feat_reuse_ = true;
+  bool keep_prepass_outputs_ = false;  // TrainForwardBackward -> SampleAndFilter: this pre-pass is a streaming train step's
+  int64_t n_feat_reuse_steps_ = 0;     // steps that took the reuse path (tests: the knob is inert where it must be)
   bool count_pending_ = false;
   int pending_count_rays_ = 0;
   int64_t total_kept_pts_ = 0, total_all_pts_ = 0;  // running totals over training-mode calls (resolved counts only)

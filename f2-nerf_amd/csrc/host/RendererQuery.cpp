@@ -44,12 +44,16 @@ struct LocatedRows {
 };
 
 // The side-effect contract of every query: a batch sampled ahead may still be served from the pre-pass feature cache, so whatever a
-// query's field calls make of Hash3DAnchored::prepass_x_ is undone when the guard goes out of scope -- by return or by exception.
+// query's field calls make of Hash3DAnchored::prepass_x_ -- and of prepass_feat_h_, the field outputs of the same rows that a
+// streaming train step keeps beside it -- is undone when the guard goes out of scope -- by return or by exception.
 struct PrepassCacheGuard {
   Hash3DAnchored* field;
-  Tensor kept;
-  explicit PrepassCacheGuard(Hash3DAnchored* f) : field(f), kept(f->prepass_x_) {}
-  ~PrepassCacheGuard() { field->prepass_x_ = kept; }
+  Tensor kept, kept_feat_h;
+  explicit PrepassCacheGuard(Hash3DAnchored* f) : field(f), kept(f->prepass_x_), kept_feat_h(f->prepass_feat_h_) {}
+  ~PrepassCacheGuard() {
+    field->prepass_x_ = kept;
+    field->prepass_feat_h_ = kept_feat_h;
+  }
 };
 
 // df0/dw [m,3] of the rows (p [m,3] warped, v [m]) into g.  x_h defined: their h16 hash features, the fused route
@@ -283,7 +287,7 @@ GeometryResult Renderer::RenderGeometry(const Tensor& rays_o_in, const Tensor& r
     Tensor p = es.pts.narrow(0, 0, m).contiguous(), v = es.anchors.narrow(0, 0, m).select(1, 0).contiguous();
     Df0Dw(field, p, v, x_h, g);
   }
-  if (fused) field->prepass_x_ = Tensor();  // (as RenderForward: the cache served its render)
+  if (fused) field->DropPrepassCache();  // (as RenderForward: the cache served its render)
   out.render = {colors, es.first_oct_dis, disparity, Tensor(), depth, weights, es.pts_idx_bounds};
   Tensor dirs = torch::empty_like(rays_d);  // the unit directions the march walked along (the sampler's own normalisation)
   F2N_CALL(f2n_normalize_dirs(st, n_rays, F32P(rays_d), F32P(dirs)));

@@ -29,7 +29,17 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
   Tensor gt = gt_colors.contiguous();
   CheckDev(gt, torch::kFloat32, "gt_colors");
   TORCH_CHECK(gt.numel() == (int64_t) n_rays * 3, "gt_colors must be [n_rays,3]");
-  RenderFront fr = SampleAndFilter(rays_o, rays_d, bounds, emb_idx, async_count_);
+  // (the digest taps read field_x, which the reuse path does not write: a tapped step takes the copying path)
+  struct KeepOutputs {
+    bool& flag;
+    KeepOutputs(bool& f, bool on) : flag(f) { flag = on; }
+    ~KeepOutputs() { flag = false; }
+  };
+  RenderFront fr;
+  {
+    KeepOutputs keep(keep_prepass_outputs_, async_count_ && prepass_feat_reuse_ && !digest_taps_);
+    fr = SampleAndFilter(rays_o, rays_d, bounds, emb_idx, async_count_);
+  }
   void* st = CurStream();
   TrainOutputs out;
   out.losses = torch::empty({8}, DevF32());
@@ -49,7 +59,13 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
   const int32_t* n_dev = fr.dyn ? I32P(fr.n_kept_dev) : nullptr;
   // ---- forward ----
   Tensor feat = torch::empty({fr.dyn ? std::max(2 * n_edge, 1) : n, F2N_MLP_OUT_PAD}, DevF32());
-  Tensor field_x = torch::empty({n, N_LEVELS * N_CHANNELS}, DevF16());
+  // reuse (Renderer.h: prepass_feat_reuse_): the pre-pass of this step kept the field network's outputs beside its hash features
+  const bool reuse = fr.dyn && field->prepass_feat_h_.defined() && field->prepass_x_.defined();
+  const bool edges_ride = fr.dyn && n_edge > 0 && fr.edge_cache_row >= 0;  // the edge samples' hash features are in the pre-pass cache too
+  // the field backward's input rows: a compact copy -- or, with reuse, the cache itself (only edge samples that did not go through
+  // the pre-pass keep their 2E rows here)
+  Tensor field_x = torch::empty({reuse ? (edges_ride ? 0 : 2 * n_edge) : n, N_LEVELS * N_CHANNELS}, DevF16());
+  Tensor x_cache, feat_h_cache;  // the two pre-pass caches, held until the backward that reads them has been queued
   // the density pre-activations of the surviving samples also leave as a compact array: compositing then reads 4 B per
   // sample instead of one 64-byte line of `feat` per sample, and its backward writes a compact d f0 that the colour
   // backward merges into the dfeat rows it writes anyway (column 0 written in place was a read-modify-write of every line)
@@ -57,11 +73,11 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
   Tensor rgb = torch::empty({std::max(n_kept, 1), 3}, DevF32()), shade_x = torch::empty({std::max(n_kept, 1), 32}, DevF16());
   Tensor app = fr.emb ? app_emb_ : Tensor();
   if (fr.dyn) {
-    // streaming step: field MLP (cached hash features) and colour path of the survivors in one launch -- their `feat` rows
-    // are never written (only the 2E edge rows of `feat` exist: the TV loss reads them); the synchronous path below keeps
-    // the two separate kernels and is what tests compare this with
+    // streaming step: the colour path of the survivors in one launch, fed by the field network's outputs -- the ones the density
+    // pre-pass of this step kept (reuse), or a second evaluation on the cached hash features in the same launch.  Their `feat` rows
+    // are never written (only the 2E edge rows of `feat` exist: the TV loss reads them); the synchronous path below keeps the two
+    // separate kernels and is what tests compare this with
     TORCH_CHECK(field->prepass_x_.defined(), "no pre-pass feature cache for this query");
-    const bool edges_ride = n_edge > 0 && fr.edge_cache_row >= 0;  // their hash features are in the pre-pass cache too
     if (n_edge > 0 && !edges_ride)
       F2N_TIMED_CALL("field_fwd", f2n_field_fwd(st, 2 * n_edge, field->n_volumes_, VoidP(field->feat_pool_h_), I32P(field->prim_pool_),
                              I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
@@ -69,17 +85,31 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
                              F32P(feat), nullptr, VoidP(field_x)));
     const at::Half* cache = field->prepass_x_.data_ptr<at::Half>();
     const int64_t row = (int64_t) N_LEVELS * N_CHANNELS;
-    // survivors: field MLP -> colour path; edge samples (when cached): field MLP only, fp32 rows for the TV loss -- one launch
-    F2N_TIMED_CALL("field_shade_fwd", f2n_field_shade_fwd_extra(st, n_kept, n_dev, I32P(fr.src_rows),
-                           static_cast<const void*>(cache + row * fr.sample_cache_row), VoidP(field->mlp_->params_h_), F32P(es.dirs),
-                           fr.emb ? F32P(app) : nullptr, fr.emb ? I32P(fr.sample_emb_idx) : nullptr, VoidP(shader->mlp_->params_h_),
-                           F32P(f0c), static_cast<void*>(field_x.data_ptr<at::Half>() + row * so), VoidP(shade_x), F32P(rgb),
-                           edges_ride ? 2 * n_edge : 0, edges_ride ? static_cast<const void*>(cache + row * fr.edge_cache_row) : nullptr,
-                           edges_ride ? F32P(feat) : nullptr, edges_ride ? VoidP(field_x) : nullptr));
-    field->prepass_x_ = Tensor();
+    if (reuse) {
+      x_cache = field->prepass_x_;
+      feat_h_cache = field->prepass_feat_h_;
+      n_feat_reuse_steps_++;
+      const at::Half* fh = feat_h_cache.data_ptr<at::Half>();
+      // survivors: cached field outputs -> colour path; edge samples (when cached): their cached outputs widened to fp32 rows
+      F2N_TIMED_CALL("field_shade_fwd", f2n_shade_fwd_feat(st, n_kept, n_dev, I32P(fr.src_rows),
+                             static_cast<const void*>(fh + (int64_t) F2N_MLP_OUT_PAD * fr.sample_cache_row), F32P(es.dirs),
+                             fr.emb ? F32P(app) : nullptr, fr.emb ? I32P(fr.sample_emb_idx) : nullptr, VoidP(shader->mlp_->params_h_),
+                             F32P(f0c), VoidP(shade_x), F32P(rgb), edges_ride ? 2 * n_edge : 0,
+                             edges_ride ? static_cast<const void*>(fh + (int64_t) F2N_MLP_OUT_PAD * fr.edge_cache_row) : nullptr,
+                             edges_ride ? F32P(feat) : nullptr));
+    } else {
+      // survivors: field MLP -> colour path; edge samples (when cached): field MLP only, fp32 rows for the TV loss -- one launch
+      F2N_TIMED_CALL("field_shade_fwd", f2n_field_shade_fwd_extra(st, n_kept, n_dev, I32P(fr.src_rows),
+                             static_cast<const void*>(cache + row * fr.sample_cache_row), VoidP(field->mlp_->params_h_), F32P(es.dirs),
+                             fr.emb ? F32P(app) : nullptr, fr.emb ? I32P(fr.sample_emb_idx) : nullptr, VoidP(shader->mlp_->params_h_),
+                             F32P(f0c), static_cast<void*>(field_x.data_ptr<at::Half>() + row * so), VoidP(shade_x), F32P(rgb),
+                             edges_ride ? 2 * n_edge : 0, edges_ride ? static_cast<const void*>(cache + row * fr.edge_cache_row) : nullptr,
+                             edges_ride ? F32P(feat) : nullptr, edges_ride ? VoidP(field_x) : nullptr));
+    }
+    field->DropPrepassCache();  // (one consumer per pre-pass; with reuse the step itself holds the two arrays until its backward is queued)
   } else {
     field->ForwardRaw(fr.pts_all, fr.vol_all, 1, fr.src_rows, n_kept, feat, field_x, &f0c);
-    field->prepass_x_ = Tensor();
+    field->DropPrepassCache();
     F2N_TIMED_CALL("shade_fwd", f2n_shade_fwd(st, n_kept, F32P(feat), F32P(es.dirs), fr.emb ? F32P(app) : nullptr,
                            fr.emb ? I32P(fr.sample_emb_idx) : nullptr, VoidP(shader->mlp_->params_h_), F32P(rgb), VoidP(shade_x)));
   }
@@ -126,7 +156,20 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
   }
   F2nStepTail tail;
   const bool fused_tail = fr.dyn && step_tail_builder_ && !digest_taps_ && step_tail_builder_(&tail);
-  if (fused_tail) {
+  // reuse: rows [0, 2E) = the edge samples (their cache rows, or the small field_x), rows [2E, ..) = cache rows through src_rows
+  const int64_t xrow = (int64_t) N_LEVELS * N_CHANNELS;
+  const void* x_edge = !reuse || n_edge == 0 ? nullptr
+                       : edges_ride ? static_cast<const void*>(x_cache.data_ptr<at::Half>() + xrow * fr.edge_cache_row) : VoidP(field_x);
+  const void* x_surv = reuse ? static_cast<const void*>(x_cache.data_ptr<at::Half>() + xrow * fr.sample_cache_row) : nullptr;
+  if (fused_tail && reuse) {
+    field->grad_clean_ = false;
+    F2N_TIMED_CALL("field_bwd", f2n_field_bwd_step_tail_rows(st, TailStream()->stream(), n, n_dev, 2 * n_edge, field->n_volumes_, I32P(field->prim_pool_),
+                           I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
+                           F32P(field->level_scale_), F32P(fr.pts_all), I32P(fr.vol_all), 1, VoidP(field->mlp_->params_h_),
+                           x_edge, x_surv, I32P(fr.src_rows), F32P(dfeat), field->mlp_->loss_scale_, F32P(field->mlp_->grad_scaled_),
+                           VoidP(field->grad_h_), field->pool_size_ / N_LEVELS, &tail, nullptr));
+    step_tail_done_ = true;
+  } else if (fused_tail) {
     // the field backward and the REST of the step in one call: the three deferred reductions, the finiteness flags and the small
     // groups' Adam on the tail stream beside the scatter's producers, the table's Adam inside the scatter's owners
     field->grad_clean_ = false;
@@ -136,6 +179,14 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
                            VoidP(field_x), F32P(dfeat), field->mlp_->loss_scale_, F32P(field->mlp_->grad_scaled_),
                            VoidP(field->grad_h_), field->pool_size_ / N_LEVELS, &tail, nullptr));
     step_tail_done_ = true;
+  } else if (reuse) {
+    field->grad_clean_ = false;
+    F2N_TIMED_CALL("field_bwd", f2n_field_bwd_dyn_rows(st, n, n_dev, 2 * n_edge, field->n_volumes_, I32P(field->prim_pool_),
+                           I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
+                           F32P(field->level_scale_), F32P(fr.pts_all), I32P(fr.vol_all), 1, VoidP(field->mlp_->params_h_),
+                           x_edge, x_surv, I32P(fr.src_rows), F32P(dfeat), field->mlp_->loss_scale_, F32P(field->mlp_->grad_scaled_),
+                           VoidP(field->grad_h_), field->pool_size_ / N_LEVELS, /*defer_reduce=*/1));
+    F2N_TIMED_CALL("reduce_partials", f2n_reduce_deferred(st));
   } else if (fr.dyn) {
     field->grad_clean_ = false;
     F2N_TIMED_CALL("field_bwd", f2n_field_bwd_dyn(st, n, n_dev, 2 * n_edge, field->n_volumes_, I32P(field->prim_pool_),

@@ -371,6 +371,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              r.FinishPending();
              return r.renderer_->QueryDensity(world);
            })
+      // The field's pre-pass caches as a step's consumer would find them (tests of the queries' cache contract, PrepassCacheGuard):
+      // density_prepass runs Hash3DAnchored::QueryDensityPreAct(keep_features = true, keep_outputs) on located points and returns f0;
+      // prepass_caches returns [hash features h16 [n,32], field outputs h16 [n,16]], an empty tensor for a cache that is not held
+      .def("density_prepass",
+           [](ExpRunner& r, const Tensor& warped, const Tensor& anchors, bool keep_outputs) {
+             py::gil_scoped_release no_gil;
+             r.FinishPending();
+             return FieldOf(r)->QueryDensityPreAct(warped, anchors, /*keep_features=*/true, keep_outputs);
+           },
+           py::arg("warped"), py::arg("anchors"), py::arg("keep_outputs") = true)
+      .def("prepass_caches",
+           [](ExpRunner& r) {
+             auto* f = FieldOf(r);
+             Tensor none = torch::empty({0}, torch::kFloat16);
+             return std::vector<Tensor>{f->prepass_x_.defined() ? f->prepass_x_ : none, f->prepass_feat_h_.defined() ? f->prepass_feat_h_ : none};
+           })
       .def("density_grid",  // [nz, ny, nx] densities on the grid of grid_spec(lo, hi, res)
            [](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res) {
              py::gil_scoped_release no_gil;
@@ -575,6 +591,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                     [](ExpRunner& r) { return static_cast<PersSampler*>(r.renderer_->pts_sampler_.get())->tail_repair_; },
                     [](ExpRunner& r, bool on) { static_cast<PersSampler*>(r.renderer_->pts_sampler_.get())->tail_repair_ = on; })
       .def_readwrite("fused_tail", &ExpRunner::fused_tail_)
+      .def_property("prepass_feat_reuse",  // streaming steps: grad pass from the pre-pass's field outputs, field backward on the cache rows (A/B: False = field_shade_fwd + field_x copy)
+                    [](ExpRunner& r) { return r.renderer_->prepass_feat_reuse_; },
+                    [](ExpRunner& r, bool on) { r.renderer_->prepass_feat_reuse_ = on; })
+      .def_property_readonly("prepass_reuse_steps", [](ExpRunner& r) { return r.renderer_->n_feat_reuse_steps_; })  // steps that took that path
       .def_readwrite("spec_start_without_event", &ExpRunner::spec_start_without_event_)
       .def_readwrite("draws_off_main", &ExpRunner::draws_off_main_)  // ExpRunner::Train's batch draws on the tail stream (A/B: False = main queue)
       .def_readwrite("exact_flag_order", &ExpRunner::exact_flag_order_)  // the step's tail inside the field backward's call (A/B: False = separate launches)

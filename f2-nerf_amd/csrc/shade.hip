@@ -179,22 +179,27 @@ __global__ __launch_bounds__(256) void shade_fwd_kernel(int n, const float* __re
 // pre-activation f0 [M] (compositing), the two networks' h16 inputs (their backward passes recompute everything else) and
 // rgb.  Bit-identical to f2n_field_fwd_cached followed by f2n_shade_fwd (same fragments, same MFMA chains, same roundings).
 // Inputs of the next tile are in flight while the current one goes through its 20 MFMAs.
-__global__ __launch_bounds__(256) void field_shade_fwd_kernel(int n, const int32_t* __restrict__ n_dev, const int32_t* __restrict__ src_rows,
-                                                              const half_t* __restrict__ x_cache, const half_t* __restrict__ field_params,
-                                                              const float* __restrict__ dirs, const float* __restrict__ app_emb,
-                                                              const int32_t* __restrict__ sample_emb_idx,
-                                                              const half_t* __restrict__ color_params, float* __restrict__ out_f0,
-                                                              half_t* __restrict__ save_field_x, half_t* __restrict__ save_shade_x,
-                                                              float* __restrict__ rgb, int n_extra,
-                                                              const half_t* __restrict__ x_extra, float* __restrict__ feat_extra,
-                                                              half_t* __restrict__ save_x_extra) {
+//
+// FROM_FEAT (shade_from_feat_kernel): the field network's outputs of these very rows already exist -- the density pre-pass of
+// the same step evaluated the same network on the same h16 features with the same weights and kept its 16 f16 outputs
+// (field_fwd_kernel's out_feat_h) -- so x_cache / x_extra are THOSE rows ([*,16] h16), lane (c, g) loads outputs 4g..4g+3 as one
+// 8-byte read and enters the code below at `f[r] = (float) oh[r]`: no field weights in LDS, no field forward (14 MFMAs and three
+// dependent layer stages per tile instead of 20 and four), no field-input copy.  The extra rows need no MLP at all: their fp32
+// rows are their cached f16 rows widened.  Same bits as the kernel that evaluates the network itself.
+template <bool FROM_FEAT>
+__device__ __forceinline__ void f2n_field_shade_fwd_body(half8_t* s_wf, half8_t* s_wc, int n, const int32_t* __restrict__ n_dev,
+                                                         const int32_t* __restrict__ src_rows, const half_t* __restrict__ x_cache,
+                                                         const half_t* __restrict__ field_params, const float* __restrict__ dirs,
+                                                         const float* __restrict__ app_emb, const int32_t* __restrict__ sample_emb_idx,
+                                                         const half_t* __restrict__ color_params, float* __restrict__ out_f0,
+                                                         half_t* __restrict__ save_field_x, half_t* __restrict__ save_shade_x,
+                                                         float* __restrict__ rgb, int n_extra, const half_t* __restrict__ x_extra,
+                                                         float* __restrict__ feat_extra, half_t* __restrict__ save_x_extra) {
   F2N_RAISE_PRIO();
   const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
   if (n_dev != nullptr) n = min(n, *n_dev);
   // both networks' weight fragments live in LDS (F2nMlpFwdWLds: 152 -> ~80 registers, twice the resident waves)
-  __shared__ half8_t s_wf[F2nMlpFwdWLds<1>::N_FRAG * 64];
-  __shared__ half8_t s_wc[F2nMlpFwdWLds<2>::N_FRAG * 64];
-  if ((tid >> 6) == 0) F2nMlpFwdWLds<1>::fill(s_wf, field_params, lane);
+  if (!FROM_FEAT && (tid >> 6) == 0) F2nMlpFwdWLds<1>::fill(s_wf, field_params, lane);
   if ((tid >> 6) == 1) F2nMlpFwdWLds<2>::fill(s_wc, color_params, lane);
   __syncthreads();
   int w_off = lane;
@@ -210,6 +215,16 @@ __global__ __launch_bounds__(256) void field_shade_fwd_kernel(int n, const int32
     for (int tile = wave_stride - 1 - wave_global; tile < n_etiles; tile += wave_stride) {
       const int s = tile * 16 + c;
       const bool valid = s < n_extra;
+      if (FROM_FEAT) {
+        if (valid) {
+          const half4_t oh = *(const half4_t*) (x_extra + (size_t) s * F2N_D_OUT + 4 * g);
+          float4_t of;
+#pragma unroll
+          for (int r = 0; r < 4; r++) of[r] = (float) oh[r];
+          *(float4_t*) (feat_extra + (size_t) s * F2N_D_OUT + 4 * g) = of;
+        }
+        continue;
+      }
       const half8_t xf = valid ? f2n_rowfrag(x_extra, F2N_D_IN, s, 0, g) : half8_t{0, 0, 0, 0, 0, 0, 0, 0};
       if (save_x_extra != nullptr && valid) {
         half_t* p = save_x_extra + (size_t) s * F2N_D_IN + 4 * g;
@@ -227,7 +242,8 @@ __global__ __launch_bounds__(256) void field_shade_fwd_kernel(int n, const int32
   }
   const int n_tiles = (n + 15) / 16;
   struct In {
-    half8_t xf;
+    half8_t xf;   // the field network's input row fragment ...
+    half4_t oh;   // ... or (FROM_FEAT) its outputs 4g..4g+3
     float4_t e;
     float d[3];
   };
@@ -245,7 +261,8 @@ __global__ __launch_bounds__(256) void field_shade_fwd_kernel(int n, const int32
   auto fetch = [&](int tile, const Idx& ix) {
     const int s = min(tile * 16 + c, n - 1);
     In r;
-    r.xf = f2n_rowfrag(x_cache, F2N_D_IN, ix.row, 0, g);
+    if (FROM_FEAT) r.oh = *(const half4_t*) (x_cache + (size_t) ix.row * F2N_D_OUT + 4 * g);
+    else r.xf = f2n_rowfrag(x_cache, F2N_D_IN, ix.row, 0, g);
     r.e = emb ? *(const float4_t*) (app_emb + (size_t) ix.img * 16 + 4 * g) : float4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 3; k++) r.d[k] = dirs[3 * (size_t) s + k];
@@ -262,16 +279,21 @@ __global__ __launch_bounds__(256) void field_shade_fwd_kernel(int n, const int32
     __builtin_amdgcn_sched_barrier(0);
     const int s = tile * 16 + c;
     const bool valid = s < n;
-    const half8_t xf = valid ? cur.xf : half8_t{0, 0, 0, 0, 0, 0, 0, 0};
-    if (save_field_x != nullptr && valid) {
-      half_t* p = save_field_x + (size_t) s * F2N_D_IN + 4 * g;
-      *(half4_t*) p = __builtin_shufflevector(xf, xf, 0, 1, 2, 3);
-      *(half4_t*) (p + 16) = __builtin_shufflevector(xf, xf, 4, 5, 6, 7);
-    }
-    const float4_t o = F2nMlpFwdWLds<1>::forward(wf, xf);  // lane (c = sample, g): field outputs 4g..4g+3
     float4_t f;
+    if (FROM_FEAT) {
 #pragma unroll
-    for (int r = 0; r < 4; r++) f[r] = (float) (half_t) o[r];  // f16 output precision (TCNNWP.cpp:143-144), widened (:112)
+      for (int r = 0; r < 4; r++) f[r] = (float) cur.oh[r];  // the pre-pass's f16 outputs, widened
+    } else {
+      const half8_t xf = valid ? cur.xf : half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+      if (save_field_x != nullptr && valid) {
+        half_t* p = save_field_x + (size_t) s * F2N_D_IN + 4 * g;
+        *(half4_t*) p = __builtin_shufflevector(xf, xf, 0, 1, 2, 3);
+        *(half4_t*) (p + 16) = __builtin_shufflevector(xf, xf, 4, 5, 6, 7);
+      }
+      const float4_t o = F2nMlpFwdWLds<1>::forward(wf, xf);  // lane (c = sample, g): field outputs 4g..4g+3
+#pragma unroll
+      for (int r = 0; r < 4; r++) f[r] = (float) (half_t) o[r];  // f16 output precision (TCNNWP.cpp:143-144), widened (:112)
+    }
     if (valid && g == 0 && out_f0 != nullptr) out_f0[s] = f[0];
     if (g == 0) f[0] = 1.f;  // Renderer.cpp:181-182
     if (emb) {
@@ -298,6 +320,33 @@ __global__ __launch_bounds__(256) void field_shade_fwd_kernel(int n, const int32
     if (valid && g < 3) rgb[3 * (size_t) s + g] = col;
     cur = nxt;
   }
+}
+
+__global__ __launch_bounds__(256) void field_shade_fwd_kernel(int n, const int32_t* __restrict__ n_dev, const int32_t* __restrict__ src_rows,
+                                                              const half_t* __restrict__ x_cache, const half_t* __restrict__ field_params,
+                                                              const float* __restrict__ dirs, const float* __restrict__ app_emb,
+                                                              const int32_t* __restrict__ sample_emb_idx,
+                                                              const half_t* __restrict__ color_params, float* __restrict__ out_f0,
+                                                              half_t* __restrict__ save_field_x, half_t* __restrict__ save_shade_x,
+                                                              float* __restrict__ rgb, int n_extra,
+                                                              const half_t* __restrict__ x_extra, float* __restrict__ feat_extra,
+                                                              half_t* __restrict__ save_x_extra) {
+  __shared__ half8_t s_wf[F2nMlpFwdWLds<1>::N_FRAG * 64];
+  __shared__ half8_t s_wc[F2nMlpFwdWLds<2>::N_FRAG * 64];
+  f2n_field_shade_fwd_body<false>(s_wf, s_wc, n, n_dev, src_rows, x_cache, field_params, dirs, app_emb, sample_emb_idx, color_params, out_f0,
+                                  save_field_x, save_shade_x, rgb, n_extra, x_extra, feat_extra, save_x_extra);
+}
+
+// The colour path of the grad pass from the pre-pass's own field outputs (see FROM_FEAT above; f2n_shade_fwd_feat).
+__global__ __launch_bounds__(256) void shade_from_feat_kernel(int n, const int32_t* __restrict__ n_dev, const int32_t* __restrict__ src_rows,
+                                                              const half_t* __restrict__ feat_cache, const float* __restrict__ dirs,
+                                                              const float* __restrict__ app_emb, const int32_t* __restrict__ sample_emb_idx,
+                                                              const half_t* __restrict__ color_params, float* __restrict__ out_f0,
+                                                              half_t* __restrict__ save_shade_x, float* __restrict__ rgb, int n_extra,
+                                                              const half_t* __restrict__ feat_extra_h, float* __restrict__ feat_extra) {
+  __shared__ half8_t s_wc[F2nMlpFwdWLds<2>::N_FRAG * 64];
+  f2n_field_shade_fwd_body<true>(nullptr, s_wc, n, n_dev, src_rows, feat_cache, nullptr, dirs, app_emb, sample_emb_idx, color_params, out_f0,
+                                 nullptr, save_shade_x, rgb, n_extra, feat_extra_h, feat_extra, nullptr);
 }
 
 // Appearance-embedding gradient addends on a 2^-38 grid (order-free integer sums; see shade_bwd_kernel).  |v| is clamped to 2^14, so
@@ -532,6 +581,21 @@ int f2n_field_shade_fwd_extra(void* stream, int n_max, const int32_t* n_dev, con
                      src_rows, (const half_t*) x_cache_h, (const half_t*) field_params_h, dirs, app_emb, sample_emb_idx,
                      (const half_t*) color_params_h, out_f0, (half_t*) save_field_x_h, (half_t*) save_shade_x_h, rgb, n_extra,
                      (const half_t*) x_extra_h, feat_extra, (half_t*) save_x_extra_h);
+  return f2n_launch_status();
+}
+
+int f2n_shade_fwd_feat(void* stream, int n_max, const int32_t* n_dev, const int32_t* src_rows, const void* feat_cache_h, const float* dirs,
+                       const float* app_emb, const int32_t* sample_emb_idx, const void* color_params_h, float* out_f0, void* save_shade_x_h,
+                       float* rgb, int n_extra, const void* feat_extra_h, float* feat_extra) {
+  const int n = n_max;
+  if (n < 0 || n_extra < 0 || (n > 0 && (feat_cache_h == nullptr || rgb == nullptr)) || (app_emb != nullptr && sample_emb_idx == nullptr) ||
+      (n_extra > 0 && (feat_extra_h == nullptr || feat_extra == nullptr)) || ((uintptr_t) feat_cache_h & 7) || ((uintptr_t) feat_extra_h & 7))
+    return F2N_ERR_INVALID_ARG;  // 8-byte loads of the f16 rows
+  if (n == 0 && n_extra == 0) return F2N_OK;
+  const int tiles = (n + 15) / 16 + (n_extra + 15) / 16;
+  hipLaunchKernelGGL(shade_from_feat_kernel, dim3(f2n_shade_grid(tiles, 4)), dim3(256), 0, (hipStream_t) stream, n, n_dev, src_rows,
+                     (const half_t*) feat_cache_h, dirs, app_emb, sample_emb_idx, (const half_t*) color_params_h, out_f0,
+                     (half_t*) save_shade_x_h, rgb, n_extra, (const half_t*) feat_extra_h, feat_extra);
   return f2n_launch_status();
 }
 

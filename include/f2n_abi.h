@@ -769,6 +769,45 @@ int f2n_field_bwd_step_tail(void* stream, void* tail_stream /* or NULL */, int n
                             const void* mlp_params_h, const void* saved_x_h, const float* dfeat, float loss_scale,
                             float* dparams_f32_scaled, void* grad_table_h, int level_entries, const F2nStepTail* tail,
                             int* table_stepped_by_owners /* out, or NULL: 1 when the owners applied the table's Adam */);
+/* ---------------------------------------------------------------------------------------------------
+ * Reuse of the density pre-pass's field outputs in the grad pass (same ABI version: additions only).  Renderer::Render queries the
+ * field twice per step with an unchanged table AND unchanged network weights (Renderer.cpp:115-123 and :152-166; the optimiser
+ * runs at the step's end), so the grad pass's 16 field outputs of a surviving sample are the pre-pass's, bit for bit.
+ *   f2n_field_fwd_ex / f2n_field_fwd_fused_ex / f2n_field_mlp_planes_ex: the three pre-pass routes with one more output,
+ *     out_feat_h [n,16] h16 (may be NULL: exactly the plain entry point) = the network's outputs at their f16 output precision
+ *     (TCNNWP.cpp:143-144), i.e. out_feat_f32 before its widening.
+ *   f2n_shade_fwd_feat: f2n_field_shade_fwd_extra without the field network -- sample i takes row src_rows[i] (NULL = row i) of
+ *     feat_cache_h [*,16] (a pre-pass's out_feat_h), then [1 | feat[1:]] + app_emb | SH4 -> colour MLP -> sigmoid as there;
+ *     out_f0 / save_shade_x_h / rgb as there; the n_extra edge rows (Renderer.cpp:159-166) are feat_extra_h [n_extra,16] widened
+ *     into feat_extra fp32 [n_extra,16].  Nothing is saved for the field backward: see the _rows calls.
+ *   f2n_field_bwd_dyn_rows / f2n_field_bwd_step_tail_rows: f2n_field_bwd_dyn / f2n_field_bwd_step_tail whose saved input is not
+ *     a compact [n_max,32] copy: row s < n_off is row s of x_edge_h [n_off,32] (may be NULL when n_off == 0), row s >= n_off is
+ *     row src_rows[s - n_off] of x_cache_h [*,32] (the pre-pass's save_x_h).  Same results as the compact calls on the gathered rows.
+ * ------------------------------------------------------------------------------------------------- */
+int f2n_field_fwd_ex(void* stream, int n, int n_volumes, const void* table_h, const int32_t* prim_pool,
+                     const int32_t* local_idx, const int32_t* local_size, const float* bias_pool,
+                     const float* level_scale, const float* pts_warped, const int32_t* volume_idx, int vol_stride,
+                     const void* mlp_params_h, float* out_feat_f32, float* out_f0, void* save_x_h, void* out_feat_h);
+int f2n_field_fwd_fused_ex(void* stream, int n, int n_volumes, const void* table_h, const int32_t* prim_pool, const int32_t* local_idx,
+                           const int32_t* local_size, const float* bias_pool, const float* level_scale, const float* pts_warped,
+                           const int32_t* volume_idx, int vol_stride, const void* mlp_params_h, float* out_feat_f32 /*or NULL*/,
+                           float* out_f0 /*or NULL*/, void* save_x_h /*or NULL*/, void* out_feat_h /*or NULL*/);
+int f2n_field_mlp_planes_ex(void* stream, int n, const void* planes_h, const void* mlp_params_h, float* out_feat_f32,
+                            float* out_f0, void* save_x_h, void* out_feat_h);
+int f2n_shade_fwd_feat(void* stream, int n_max, const int32_t* n_dev, const int32_t* src_rows, const void* feat_cache_h,
+                       const float* dirs, const float* app_emb, const int32_t* sample_emb_idx, const void* color_params_h,
+                       float* out_f0, void* save_shade_x_h, float* rgb, int n_extra, const void* feat_extra_h, float* feat_extra);
+int f2n_field_bwd_dyn_rows(void* stream, int n_max, const int32_t* n_dev, int n_off, int n_volumes, const int32_t* prim_pool,
+                           const int32_t* local_idx, const int32_t* local_size, const float* bias_pool, const float* level_scale,
+                           const float* pts_warped, const int32_t* volume_idx, int vol_stride, const void* mlp_params_h,
+                           const void* x_edge_h, const void* x_cache_h, const int32_t* src_rows, const float* dfeat, float loss_scale,
+                           float* dparams_f32_scaled, void* grad_table_h, int level_entries, int defer_reduce);
+int f2n_field_bwd_step_tail_rows(void* stream, void* tail_stream /* or NULL */, int n_max, const int32_t* n_dev, int n_off, int n_volumes,
+                                 const int32_t* prim_pool, const int32_t* local_idx, const int32_t* local_size, const float* bias_pool,
+                                 const float* level_scale, const float* pts_warped, const int32_t* volume_idx, int vol_stride,
+                                 const void* mlp_params_h, const void* x_edge_h, const void* x_cache_h, const int32_t* src_rows,
+                                 const float* dfeat, float loss_scale, float* dparams_f32_scaled, void* grad_table_h, int level_entries,
+                                 const F2nStepTail* tail, int* table_stepped_by_owners /* out, or NULL */);
 /* h16 gradient table produced by f2n_hash_bwd / f2n_field_bwd (true gradient = float(grad_h) * grad_scale,
  * grad_scale = 1/128): fuses the fp16->fp32 cast, the /128 (Hash3DAnchored.cu:232), Adam, the fp32->fp16
  * refresh of the table (Hash3DAnchored.cu:186) and the re-zeroing of the gradient (:222) in one pass. */
