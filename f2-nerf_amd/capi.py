@@ -1098,6 +1098,98 @@ def mesh_raycast(verts, faces, accel, rays_o, rays_d, bounds=None):
     return t, face, bary
 
 
+# ---------------------------------------------------------------- texture atlas of a triangle mesh
+def mesh_atlas(verts, faces, density, max_size=8192, max_log=7):
+    """(uv [F,3,2], size, blocks, density_used): host.mesh_atlas through ctypes (f2n_atlas_classify -> sort and prefix sums ->
+    f2n_atlas_place; include/f2n_abi.h states the layout).  blocks: dict of offsets [B+1] int64, block_log [B], block_faces [B,2],
+    log_s [F], rot [F], slot [F].  While the atlas is wider than max_size the density is halved, at most 32 times; ValueError for a
+    max_size that is no power of two and for a mesh that cannot fit."""
+    import numpy as np
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    dev = verts.device
+    max_size, max_log = int(max_size), int(max_log)
+    density = float(np.float32(density))
+    if max_size < 4 or max_size & (max_size - 1):
+        raise ValueError("mesh_atlas: max_size must be a power of two, at least 4")
+    if not 2 <= max_log <= 13:
+        raise ValueError("mesh_atlas: max_log must lie in [2, 13]")
+    if not (density > 0.0 and density < float("inf")):
+        raise ValueError("mesh_atlas: density must be positive and finite")
+    least = 4
+    while least * least < 16 * ((nf + 1) // 2):
+        least *= 2
+    if least > max_size:
+        raise ValueError("mesh_atlas: the mesh does not fit max_size even at the smallest block size")
+    i64 = dict(dtype=torch.int64, device=dev)
+    m, ncls = max(nf, 1), max_log - 1
+    log_s, rot = torch.empty(nf, dtype=torch.int32, device=dev), torch.empty(nf, dtype=torch.int32, device=dev)
+    for _ in range(33):
+        if not density > 0.0:
+            break
+        _ck(lib().f2n_atlas_classify(_stream(), _i(nv), _i(nf), _p(verts, "f32", True), _p(faces, "i32", nf == 0), _f(density), _i(max_log),
+                                     _p(log_s, "i32", nf == 0), _p(rot, "i32", nf == 0)), "f2n_atlas_classify")
+        keys = torch.sort((max_log - log_s.to(torch.int64)) * m + torch.arange(nf, **i64))[0]
+        order, cls = torch.remainder(keys, m), torch.div(keys, m, rounding_mode="floor")
+        n_c = torch.bincount(cls, minlength=ncls)
+        nb_c = torch.div(n_c + 1, 2, rounding_mode="floor")
+        c0, b0 = n_c.cumsum(0) - n_c, nb_c.cumsum(0) - nb_c
+        q = torch.arange(nf, **i64) - c0[cls]
+        sl = (b0[cls] + torch.div(q, 2, rounding_mode="floor")) * 2 + torch.remainder(q, 2)
+        B = int(nb_c.sum())
+        block_log = (max_log - torch.repeat_interleave(torch.arange(ncls, **i64), nb_c)).to(torch.int32).contiguous()
+        offsets = torch.cat([torch.zeros(1, **i64), torch.bitwise_left_shift(torch.ones(B, **i64), block_log.to(torch.int64) * 2).cumsum(0)])
+        offsets = offsets.contiguous()
+        total, size = int(offsets[B]), 4
+        while size * size < total:
+            size *= 2
+        if size > max_size:
+            density = float(np.float32(density * 0.5))
+            continue
+        slot = torch.zeros(nf, dtype=torch.int32, device=dev)
+        slot[order] = sl.to(torch.int32)
+        block_faces = torch.full((B * 2,), -1, dtype=torch.int32, device=dev)
+        block_faces[sl] = order.to(torch.int32)
+        uv = torch.zeros((nf, 3, 2), dtype=torch.float32, device=dev)
+        _ck(lib().f2n_atlas_place(_stream(), _i(nf), _i(B), _i(size), _p(log_s, "i32", nf == 0), _p(rot, "i32", nf == 0),
+                                  _p(slot, "i32", nf == 0), _p(offsets, "i64"), _p(uv, "f32", nf == 0)), "f2n_atlas_place")
+        blocks = {"offsets": offsets, "block_log": block_log, "block_faces": block_faces.view(B, 2), "log_s": log_s, "rot": rot, "slot": slot}
+        return uv, size, blocks, density
+    raise ValueError("mesh_atlas: the mesh does not fit max_size after 32 halvings of the density")
+
+
+def mesh_atlas_texels(verts, faces, blocks, size, clamp=True):
+    """(tex_face [S,S] int32 (-1: unowned), tex_bary [S,S,3], tex_pos [S,S,3]) of mesh_atlas's blocks (f2n_atlas_texels), in row
+    bands above 4096^2 texels."""
+    nv, nf, S = int(verts.shape[0]), int(faces.shape[0]), int(size)
+    dev = verts.device
+    B = int(blocks["block_log"].numel())
+    if S < 4 or S > 8192 or S & (S - 1):
+        raise ValueError("mesh_atlas_texels: size must be a power of two in [4, 8192]")
+    if blocks["offsets"].numel() != B + 1 or blocks["block_faces"].numel() != 2 * B or blocks["rot"].numel() != nf:
+        raise ValueError("mesh_atlas_texels: blocks do not match (offsets [B+1], block_faces [B,2], rot [F])")
+    tex_face = torch.empty((S, S), dtype=torch.int32, device=dev)
+    tex_bary, tex_pos = torch.empty((S, S, 3), dtype=torch.float32, device=dev), torch.empty((S, S, 3), dtype=torch.float32, device=dev)
+    band = max(16, 4096 * 4096 // S)
+    for y in range(0, S, band):
+        _ck(lib().f2n_atlas_texels(_stream(), _i(nv), _i(nf), _p(verts, "f32", True), _p(faces, "i32", nf == 0), _i(B), _i(S),
+                                   _p(blocks["offsets"], "i64"), _p(blocks["block_log"], "i32", B == 0), _p(blocks["block_faces"], "i32", B == 0),
+                                   _p(blocks["rot"], "i32", nf == 0), _i(1 if clamp else 0), _i(y), _i(min(S, y + band)), _p(tex_face, "i32"),
+                                   _p(tex_bary, "f32"), _p(tex_pos, "f32")), "f2n_atlas_texels")
+    return tex_face, tex_bary, tex_pos
+
+
+def texture_sample(tex, uv):
+    """[N,C]: the bilinear lookup of tex [S,S,C] at uv [N,2] (f2n_texture_sample): texel centres at (i + 0.5) / S, clamped to the edge,
+    zeros for a uv that is not finite."""
+    if tex.dim() != 3 or tex.shape[0] != tex.shape[1] or not 1 <= int(tex.shape[0]) <= 32768 or not 1 <= int(tex.shape[2]) <= 64:
+        raise ValueError("texture_sample: tex must be [S,S,C] with S in [1, 32768] and C in [1, 64]")
+    n = int(uv.shape[0])
+    out = torch.empty((n, int(tex.shape[2])), dtype=torch.float32, device=tex.device)
+    _ck(lib().f2n_texture_sample(_stream(), _i(int(tex.shape[0])), _i(int(tex.shape[2])), _p(tex, "f32"), ctypes.c_int64(n),
+                                 _p(uv, "f32", n == 0), _p(out, "f32", n == 0)), "f2n_texture_sample")
+    return out
+
+
 # ---------------------------------------------------------------- TSDF fusion of depth maps
 def tsdf_integrate(S, W, lo, step, poses, intri, dist_params, depth, conf, trunc):
     """Adds the depth maps depth [V,h,w] (conf [V,h,w] or None: weight 1) seen from poses [V,3,4] / intri [V,3,3] / dist_params [V,4] into

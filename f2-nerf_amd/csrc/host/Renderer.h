@@ -112,6 +112,24 @@ MeshRaycastAccel MeshRaycastBuild(const Tensor& verts, const Tensor& faces, floa
 std::tuple<Tensor, Tensor, Tensor> MeshRaycast(const Tensor& verts, const Tensor& faces, const MeshRaycastAccel* accel, const Tensor& rays_o,
                                                const Tensor& rays_d, const Tensor& bounds);
 
+// Texture atlas of a mesh (f2n_atlas_*; include/f2n_abi.h states the layout): one right-triangle chart per face, two to a power-of-two
+// block, blocks placed by the Morton decode of the prefix sum of their areas.  density = texels per length unit; while the atlas is
+// wider than max_size (a power of two) the density is halved, at most 32 times.  std::invalid_argument for a max_size that is no
+// power of two and for a mesh that cannot fit.
+struct MeshAtlasResult {
+  Tensor uv;                              // [F,3,2] fp32, image convention, per face corner
+  int size = 4;                           // the atlas side
+  float density_used = 0.f;
+  Tensor offsets, block_log, block_faces; // [B+1] int64, [B] int32, [B,2] int32 (lower, upper; -1: empty)
+  Tensor log_s, rot, slot;                // [F] int32 each; slot = 2 block + upper; bit 2 of rot flags a degenerate face
+};
+MeshAtlasResult MeshAtlas(const Tensor& verts, const Tensor& faces, float density, int max_size, int max_log);
+// (tex_face [S,S] int32 (-1: unowned), tex_bary [S,S,3], tex_pos [S,S,3]): the face, weights and position of every texel; clamp: gutter
+// texels replicate the nearest edge instead of extrapolating.  Reads a's size, offsets, block_log, block_faces and rot.
+std::tuple<Tensor, Tensor, Tensor> MeshAtlasTexels(const Tensor& verts, const Tensor& faces, const MeshAtlasResult& a, bool clamp);
+// [N,C]: the bilinear lookup of tex [S,S,C] at uv [N,2] (texel centres at (i + 0.5) / S, clamped to the edge; f2n_texture_sample)
+Tensor TextureSample(const Tensor& tex, const Tensor& uv);
+
 struct MeshAttrs {  // Renderer::ExtractMeshAttrs; normals / colors are undefined unless asked for
   Tensor verts, faces, normals, colors;
   int64_t verts_in = -1, faces_in = -1;  // simplify >= 2: the size of the mesh that went into MeshSimplify

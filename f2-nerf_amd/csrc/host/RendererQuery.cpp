@@ -681,6 +681,96 @@ std::tuple<Tensor, Tensor, Tensor> MeshRaycast(const Tensor& verts, const Tensor
   return {t, face, bary};
 }
 
+MeshAtlasResult MeshAtlas(const Tensor& verts, const Tensor& faces, float density, int max_size, int max_log) {
+  torch::NoGradGuard g;
+  Tensor v = Points3(verts);
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  const int64_t nv = v.size(0), nf = f.size(0);
+  TORCH_CHECK(nf <= INT32_MAX, "mesh too large");
+  if (max_size < 4 || (max_size & (max_size - 1)) != 0) throw std::invalid_argument("mesh_atlas: max_size must be a power of two, at least 4");
+  if (max_log < 2 || max_log > 13) throw std::invalid_argument("mesh_atlas: max_log must lie in [2, 13]");
+  if (!(density > 0.f) || !std::isfinite(density)) throw std::invalid_argument("mesh_atlas: density must be positive and finite");
+  {  // the layout with every block at its minimum of 4 x 4 texels: two faces to a block
+    int64_t least = 4;
+    while (least * least < 16 * ((nf + 1) / 2)) least *= 2;
+    if (least > max_size) throw std::invalid_argument("mesh_atlas: the mesh does not fit max_size even at the smallest block size");
+  }
+  const auto i64 = DevI32().dtype(torch::kInt64);
+  const int64_t m = std::max<int64_t>(nf, 1), ncls = max_log - 1;
+  MeshAtlasResult a;
+  a.log_s = torch::empty({nf}, DevI32());
+  a.rot = torch::empty({nf}, DevI32());
+  for (int round = 0; round <= 32; round++, density *= 0.5f) {
+    if (!(density > 0.f)) break;
+    F2N_TIMED_CALL("atlas_classify", f2n_atlas_classify(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), density, max_log, I32P(a.log_s),
+                                                        I32P(a.rot)));
+    TimedSpan span("atlas_layout");
+    // classes descending, faces ascending within a class; positions 2j and 2j + 1 of a class share its block j
+    Tensor keys = std::get<0>(torch::sort((max_log - a.log_s.to(torch::kInt64)) * m + torch::arange(nf, i64)));
+    Tensor order = torch::remainder(keys, m), cls = torch::floor_divide(keys, m);
+    Tensor n_c = torch::bincount(cls, {}, ncls);
+    Tensor nb_c = torch::floor_divide(n_c + 1, 2);
+    Tensor c0 = n_c.cumsum(0) - n_c, b0 = nb_c.cumsum(0) - nb_c;
+    Tensor q = torch::arange(nf, i64) - c0.index_select(0, cls);
+    Tensor sl = (b0.index_select(0, cls) + torch::floor_divide(q, 2)) * 2 + torch::remainder(q, 2);
+    const int64_t B = nb_c.sum().item<int64_t>();
+    a.block_log = (max_log - torch::repeat_interleave(torch::arange(ncls, i64), nb_c)).to(torch::kInt32).contiguous();
+    Tensor areas = torch::bitwise_left_shift(torch::ones({B}, i64), a.block_log.to(torch::kInt64) * 2);
+    a.offsets = torch::cat({torch::zeros({1}, i64), areas.cumsum(0)}).contiguous();
+    const int64_t total = a.offsets[B].item<int64_t>();
+    int64_t size = 4;
+    while (size * size < total) size *= 2;
+    if (size > max_size) continue;
+    a.slot = torch::zeros({nf}, DevI32());
+    a.slot.index_put_({order}, sl.to(torch::kInt32));
+    Tensor bf = torch::full({B * 2}, -1, DevI32());
+    bf.index_put_({sl}, order.to(torch::kInt32));
+    a.block_faces = bf.view({B, 2});
+    a.size = (int) size;
+    a.density_used = density;
+    a.uv = torch::zeros({nf, 3, 2}, DevF32());
+    F2N_TIMED_CALL("atlas_place", f2n_atlas_place(CurStream(), (int) nf, (int) B, a.size, I32P(a.log_s), I32P(a.rot), I32P(a.slot),
+                                                  a.offsets.data_ptr<int64_t>(), F32P(a.uv)));
+    return a;
+  }
+  throw std::invalid_argument("mesh_atlas: the mesh does not fit max_size after 32 halvings of the density");
+}
+
+std::tuple<Tensor, Tensor, Tensor> MeshAtlasTexels(const Tensor& verts, const Tensor& faces, const MeshAtlasResult& a, bool clamp) {
+  torch::NoGradGuard g;
+  Tensor v = Points3(verts);
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  const int64_t nv = v.size(0), nf = f.size(0), S = a.size;
+  DevArg(a.offsets, torch::kInt64, "offsets");
+  DevArg(a.block_log, torch::kInt32, "block_log");
+  DevArg(a.block_faces, torch::kInt32, "block_faces");
+  DevArg(a.rot, torch::kInt32, "rot");
+  const int64_t B = a.block_log.numel();
+  if (S < 4 || S > 8192 || (S & (S - 1)) != 0) throw std::invalid_argument("mesh_atlas_texels: size must be a power of two in [4, 8192]");
+  if (a.offsets.numel() != B + 1 || a.block_faces.numel() != 2 * B || a.rot.numel() != nf)
+    throw std::invalid_argument("mesh_atlas_texels: blocks do not match (offsets [B+1], block_faces [B,2], rot [F])");
+  Tensor tex_face = torch::empty({S, S}, DevI32()), tex_bary = torch::empty({S, S, 3}, DevF32()), tex_pos = torch::empty({S, S, 3}, DevF32());
+  // above 4096^2 texels in row bands (16 M lanes a launch); the kernel writes the outputs in place, so there is no workspace
+  const int64_t band = std::max<int64_t>(16, (int64_t) 4096 * 4096 / S);
+  for (int64_t y = 0; y < S; y += band)
+    F2N_TIMED_CALL("atlas_texels", f2n_atlas_texels(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), (int) B, (int) S,
+                                                    a.offsets.data_ptr<int64_t>(), B > 0 ? I32P(a.block_log) : nullptr,
+                                                    B > 0 ? I32P(a.block_faces) : nullptr, I32P(a.rot), clamp ? 1 : 0, (int) y,
+                                                    (int) std::min(S, y + band), I32P(tex_face), F32P(tex_bary), F32P(tex_pos)));
+  return {tex_face, tex_bary, tex_pos};
+}
+
+Tensor TextureSample(const Tensor& tex, const Tensor& uv) {
+  torch::NoGradGuard g;
+  Tensor t = tex.to(torch::kCUDA, torch::kFloat32).contiguous();
+  Tensor u = uv.to(torch::kCUDA, torch::kFloat32).contiguous().view({-1, 2});
+  if (t.dim() != 3 || t.size(0) != t.size(1) || t.size(0) < 1 || t.size(0) > 32768 || t.size(2) < 1 || t.size(2) > 64)
+    throw std::invalid_argument("texture_sample: tex must be [S,S,C] with S in [1, 32768] and C in [1, 64]");
+  Tensor out = torch::empty({u.size(0), t.size(2)}, DevF32());
+  F2N_TIMED_CALL("texture_sample", f2n_texture_sample(CurStream(), (int) t.size(0), (int) t.size(2), F32P(t), u.size(0), F32P(u), F32P(out)));
+  return out;
+}
+
 MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level,
                                      int min_component_faces, bool normals, bool colors, const std::string& normal_source, int simplify) {
   torch::NoGradGuard g;

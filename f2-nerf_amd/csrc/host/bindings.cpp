@@ -206,6 +206,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::vector<Tensor>{std::get<0>(r), std::get<1>(r), std::get<2>(r)};
         },
         py::arg("verts"), py::arg("faces"), py::arg("accel"), py::arg("rays_o"), py::arg("rays_d"), py::arg("bounds") = py::none());
+  // the texture atlas of a mesh: (uv [F,3,2], size, blocks, density_used); blocks = dict of the device tensors mesh_atlas_texels needs
+  // (offsets [B+1] int64, block_log, block_faces, log_s, rot, slot).  ValueError: max_size no power of two, or the mesh cannot fit
+  m.def("mesh_atlas",
+        [](const Tensor& verts, const Tensor& faces, float density, int max_size, int max_log) {
+          MeshAtlasResult a = MeshAtlas(verts, faces, density, max_size, max_log);
+          py::dict b;
+          b["offsets"] = a.offsets; b["block_log"] = a.block_log; b["block_faces"] = a.block_faces;
+          b["log_s"] = a.log_s; b["rot"] = a.rot; b["slot"] = a.slot;
+          return py::make_tuple(a.uv, a.size, b, a.density_used);
+        },
+        py::arg("verts"), py::arg("faces"), py::arg("density"), py::arg("max_size") = 8192, py::arg("max_log") = 7);
+  // [tex_face [S,S] int32, tex_bary [S,S,3], tex_pos [S,S,3]] of mesh_atlas's blocks at its size
+  m.def("mesh_atlas_texels",
+        [](const Tensor& verts, const Tensor& faces, const py::dict& blocks, int size, bool clamp) {
+          MeshAtlasResult a;
+          a.size = size;
+          a.offsets = blocks["offsets"].cast<Tensor>(); a.block_log = blocks["block_log"].cast<Tensor>();
+          a.block_faces = blocks["block_faces"].cast<Tensor>(); a.rot = blocks["rot"].cast<Tensor>();
+          auto r = MeshAtlasTexels(verts, faces, a, clamp);
+          return std::vector<Tensor>{std::get<0>(r), std::get<1>(r), std::get<2>(r)};
+        },
+        py::arg("verts"), py::arg("faces"), py::arg("blocks"), py::arg("size"), py::arg("clamp") = true);
+  m.def("texture_sample", [](const Tensor& tex, const Tensor& uv) { return TextureSample(tex, uv); }, py::arg("tex"), py::arg("uv"));
   m.def("dp_set_table_buckets", [](int n) { DataParallel::table_buckets = n; });  // table all-reduce buckets of the next attach (A/B)
   // data-parallel replicas draw stream `rank` of every keyed purpose (KeyedDraws.h; the native attach sets it itself)
   m.def("dp_set_replica", [](int rank) { KeyedUniforms::SetReplica(rank); });

@@ -1619,3 +1619,219 @@ int f2n_mesh_raycast(void* stream, int n_verts, int n_faces, const float* verts,
                        rays_d, bounds, out_t, out_face, out_bary);
   return f2n_launch_status();
 }
+
+// =====================================================================================================================
+// Texture atlas (include/f2n_abi.h, "Texture atlas of a triangle mesh"): one right-triangle chart per face in power-of-two
+// blocks placed by the Morton decode of a prefix sum, the texel-to-surface map and a bilinear lookup.  One lane owns one
+// face / texel / output value: no atomics, so every output is a function of the inputs alone.  The corner rotation is
+// done with selects (sel3): a private array under a runtime index would live in scratch memory.
+// =====================================================================================================================
+namespace {
+
+#define F2N_ATLAS_MAX_LOG 13      // blocks and the atlas itself are at most 8192 texels wide
+#define F2N_ATLAS_DEGENERATE 4    // bit 2 of rot
+
+__device__ __forceinline__ int morton_even_bits(long long m) {  // bits 0, 2, 4, ... of m, compacted (13 of them)
+  int x = 0;
+#pragma unroll
+  for (int k = 0; k < F2N_ATLAS_MAX_LOG; k++) x |= (int) ((m >> (2 * k)) & 1) << k;
+  return x;
+}
+
+__device__ __forceinline__ long long morton_encode(int x, int y) {
+  long long m = 0;
+#pragma unroll
+  for (int k = 0; k < F2N_ATLAS_MAX_LOG; k++) m |= ((long long) ((x >> k) & 1) << (2 * k)) | ((long long) ((y >> k) & 1) << (2 * k + 1));
+  return m;
+}
+
+__global__ void __launch_bounds__(256) atlas_classify_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                            const int32_t* __restrict__ faces, float density, int max_log,
+                                                            int32_t* __restrict__ log_s, int32_t* __restrict__ rot) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  int a, b, c, ls = 2, r = F2N_ATLAS_DEGENERATE;
+  if (face_in_range(faces, f, n_verts, &a, &b, &c)) {
+    const float* pa = verts + (int64_t) a * 3;
+    const float* pb = verts + (int64_t) b * 3;
+    const float* pc = verts + (int64_t) c * 3;
+    if (finite3(pa) && finite3(pb) && finite3(pc)) {
+      const double px = (double) pb[0] - (double) pa[0], py = (double) pb[1] - (double) pa[1], pz = (double) pb[2] - (double) pa[2];
+      const double qx = (double) pc[0] - (double) pa[0], qy = (double) pc[1] - (double) pa[1], qz = (double) pc[2] - (double) pa[2];
+      const double ex = (double) pc[0] - (double) pb[0], ey = (double) pc[1] - (double) pb[1], ez = (double) pc[2] - (double) pb[2];
+      const double l_ab = (px * px + py * py) + pz * pz, l_bc = (ex * ex + ey * ey) + ez * ez, l_ca = (qx * qx + qy * qy) + qz * qz;
+      const double nx = py * qz - pz * qy, ny = pz * qx - px * qz, nz = px * qy - py * qx;
+      const double n2 = (nx * nx + ny * ny) + nz * nz;
+      if (n2 > 0.0) {
+        const double need = fmax(4.0, ceil(sqrt(sqrt(n2)) * (double) density) + 3.0);
+        while (ls < max_log && (double) (1 << ls) < need) ls++;
+        // the corner opposite the longest edge: corner 0 faces BC, corner 1 faces CA, corner 2 faces AB; the first among equals
+        r = 0;
+        double longest = l_bc;
+        if (l_ca > longest) { r = 1; longest = l_ca; }
+        if (l_ab > longest) r = 2;
+      }
+    }
+  }
+  log_s[f] = ls;
+  rot[f] = r;
+}
+
+__global__ void __launch_bounds__(256) atlas_place_kernel(int n_faces, int n_blocks, int size, const int32_t* __restrict__ log_s,
+                                                         const int32_t* __restrict__ rot, const int32_t* __restrict__ slot,
+                                                         const long long* __restrict__ offsets, float* __restrict__ uv) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  const int sl = slot[f], ls = log_s[f];
+  float o[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (only constant indices below: registers)
+  if (sl >= 0 && (sl >> 1) < n_blocks && ls >= 2 && ls <= F2N_ATLAS_MAX_LOG) {
+    const long long off = offsets[sl >> 1];
+    const float x0 = (float) morton_even_bits(off), y0 = (float) morton_even_bits(off >> 1), s = (float) (1 << ls), S = (float) size;
+    const bool up = (sl & 1) != 0;
+    // chart corners 0 (the right angle), 1 (along x), 2 (along y) in texels from the block's origin: every sum below is exact
+    const float c0x = up ? s - 0.5f : 0.5f, c0y = c0x;
+    const float c1x = up ? 2.5f : s - 2.5f, c1y = c0y;
+    const float c2x = c0x, c2y = up ? 2.5f : s - 2.5f;
+    const int r = rot[f] & 3;  // chart corner k is the face's corner (r + k) % 3: the face's corner j is chart corner (j - r) mod 3
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const int k = (j - r + 3) % 3;
+      o[2 * j] = F2N_DIV_RN(x0 + sel3(k, c0x, c1x, c2x), S);
+      o[2 * j + 1] = F2N_DIV_RN(y0 + sel3(k, c0y, c1y, c2y), S);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; k++) uv[f * 6 + k] = o[k];
+}
+
+// One wave owns an 8 x 8 texel tile (a block of four waves a 16 x 16 one): a tile lies inside one block of the atlas unless that
+// block is a 4 x 4 one, so the wave's binary search takes one path and its loads are broadcasts.
+__global__ void __launch_bounds__(256) atlas_texels_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                          const int32_t* __restrict__ faces, int n_blocks, int size,
+                                                          const long long* __restrict__ offsets, const int32_t* __restrict__ block_log,
+                                                          const int32_t* __restrict__ block_faces, const int32_t* __restrict__ rot,
+                                                          int clamp, int row_begin, int row_end, int32_t* __restrict__ tex_face,
+                                                          float* __restrict__ tex_bary, float* __restrict__ tex_pos) {
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int x = (int) blockIdx.x * 16 + (w & 1) * 8 + (l & 7);
+  const int y = row_begin + (int) blockIdx.y * 16 + (w >> 1) * 8 + (l >> 3);
+  if (x >= size || y >= row_end) return;
+  const long long m = morton_encode(x, y);
+  int face = -1;
+  float b0 = 0.f, b1 = 0.f, b2 = 0.f, p0 = 0.f, p1 = 0.f, p2 = 0.f;
+  if (m < offsets[n_blocks]) {
+    int lo = 0, hi = n_blocks;  // the last block whose offset is <= m: offsets[lo] <= m < offsets[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (offsets[mid] <= m) lo = mid; else hi = mid;
+    }
+    const long long off = offsets[lo];
+    const int ls = block_log[lo], s = 1 << ls;
+    const int i = x - morton_even_bits(off), j = y - morton_even_bits(off >> 1);
+    const bool up = i + j > s - 1;
+    const int f = block_faces[lo * 2 + (up ? 1 : 0)];
+    int a, b, c;
+    if (f >= 0 && f < n_faces && (rot[f] & F2N_ATLAS_DEGENERATE) == 0 && i >= 0 && j >= 0 && i < s && j < s &&
+        face_in_range(faces, f, n_verts, &a, &b, &c)) {
+      const float leg = (float) (s - 3);
+      const float u = F2N_DIV_RN((float) (up ? s - 1 - i : i), leg), v = F2N_DIV_RN((float) (up ? s - 1 - j : j), leg);
+      const float w0 = F2N_SUB_RN(F2N_SUB_RN(1.f, u), v);
+      const int r = rot[f] & 3;  // the face's corner j carries the weight of chart corner (j - r) mod 3
+      b0 = sel3((3 - r) % 3, w0, u, v);
+      b1 = sel3((4 - r) % 3, w0, u, v);
+      b2 = sel3((5 - r) % 3, w0, u, v);
+      if (clamp != 0 && (b0 < 0.f || b1 < 0.f || b2 < 0.f)) {
+        b0 = fmaxf(b0, 0.f); b1 = fmaxf(b1, 0.f); b2 = fmaxf(b2, 0.f);
+        const float sum = F2N_ADD_RN(F2N_ADD_RN(b0, b1), b2);
+        b0 = F2N_DIV_RN(b0, sum); b1 = F2N_DIV_RN(b1, sum); b2 = F2N_DIV_RN(b2, sum);
+      }
+      const float* pa = verts + (int64_t) a * 3;
+      const float* pb = verts + (int64_t) b * 3;
+      const float* pc = verts + (int64_t) c * 3;
+      p0 = F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(b0, pa[0]), F2N_MUL_RN(b1, pb[0])), F2N_MUL_RN(b2, pc[0]));
+      p1 = F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(b0, pa[1]), F2N_MUL_RN(b1, pb[1])), F2N_MUL_RN(b2, pc[1]));
+      p2 = F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(b0, pa[2]), F2N_MUL_RN(b1, pb[2])), F2N_MUL_RN(b2, pc[2]));
+      face = f;
+    }
+  }
+  const int64_t at = (int64_t) y * size + x;
+  tex_face[at] = face;
+  tex_bary[at * 3] = b0; tex_bary[at * 3 + 1] = b1; tex_bary[at * 3 + 2] = b2;
+  tex_pos[at * 3] = p0; tex_pos[at * 3 + 1] = p1; tex_pos[at * 3 + 2] = p2;
+}
+
+__global__ void __launch_bounds__(256) texture_sample_kernel(int size, int channels, const float* __restrict__ tex, int64_t n,
+                                                            const float* __restrict__ uv, float* __restrict__ out) {
+  const int64_t at = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (at >= n * channels) return;
+  const int64_t row = at / channels;
+  const int ch = (int) (at - row * channels);
+  const float u = uv[row * 2], v = uv[row * 2 + 1], inf = __builtin_huge_valf();
+  float r = 0.f;
+  if (fabsf(u) < inf && fabsf(v) < inf) {
+    const float top = (float) (size - 1), S = (float) size;
+    const float fx = fminf(fmaxf(F2N_SUB_RN(F2N_MUL_RN(u, S), 0.5f), 0.f), top);
+    const float fy = fminf(fmaxf(F2N_SUB_RN(F2N_MUL_RN(v, S), 0.5f), 0.f), top);
+    const float gx = floorf(fx), gy = floorf(fy);
+    const float ax = F2N_SUB_RN(fx, gx), ay = F2N_SUB_RN(fy, gy), cx = F2N_SUB_RN(1.f, ax), cy = F2N_SUB_RN(1.f, ay);
+    const int x0 = (int) gx, y0 = (int) gy, x1 = min(x0 + 1, size - 1), y1 = min(y0 + 1, size - 1);
+    const float t00 = tex[((int64_t) y0 * size + x0) * channels + ch], t10 = tex[((int64_t) y0 * size + x1) * channels + ch];
+    const float t01 = tex[((int64_t) y1 * size + x0) * channels + ch], t11 = tex[((int64_t) y1 * size + x1) * channels + ch];
+    r = F2N_ADD_RN(F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(t00, F2N_MUL_RN(cx, cy)), F2N_MUL_RN(t10, F2N_MUL_RN(ax, cy))),
+                              F2N_MUL_RN(t01, F2N_MUL_RN(cx, ay))),
+                   F2N_MUL_RN(t11, F2N_MUL_RN(ax, ay)));
+  }
+  out[at] = r;
+}
+
+bool atlas_size_ok(int size) { return size >= 4 && size <= (1 << F2N_ATLAS_MAX_LOG) && (size & (size - 1)) == 0; }
+
+}  // namespace
+
+int f2n_atlas_classify(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, float density, int max_log,
+                       int32_t* log_s, int32_t* rot) {
+  if (n_verts < 0 || n_faces < 0 || !(density > 0.f) || !(density < __builtin_huge_valf()) || max_log < 2 || max_log > F2N_ATLAS_MAX_LOG ||
+      (n_faces > 0 && (faces == nullptr || log_s == nullptr || rot == nullptr || (n_verts > 0 && verts == nullptr))))
+    return F2N_ERR_INVALID_ARG;
+  if (n_faces == 0) return F2N_OK;
+  hipLaunchKernelGGL(atlas_classify_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, (hipStream_t) stream, n_verts, n_faces, verts, faces,
+                     density, max_log, log_s, rot);
+  return f2n_launch_status();
+}
+
+int f2n_atlas_place(void* stream, int n_faces, int n_blocks, int size, const int32_t* log_s, const int32_t* rot, const int32_t* slot,
+                    const int64_t* offsets, float* uv) {
+  if (n_faces < 0 || n_blocks < 0 || !atlas_size_ok(size) ||
+      (n_faces > 0 && (log_s == nullptr || rot == nullptr || slot == nullptr || offsets == nullptr || uv == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n_faces == 0) return F2N_OK;
+  hipLaunchKernelGGL(atlas_place_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, (hipStream_t) stream, n_faces, n_blocks, size, log_s, rot,
+                     slot, (const long long*) offsets, uv);
+  return f2n_launch_status();
+}
+
+int f2n_atlas_texels(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, int n_blocks, int size,
+                     const int64_t* offsets, const int32_t* block_log, const int32_t* block_faces, const int32_t* rot, int clamp,
+                     int row_begin, int row_end, int32_t* tex_face, float* tex_bary, float* tex_pos) {
+  if (n_verts < 0 || n_faces < 0 || n_blocks < 0 || !atlas_size_ok(size) || row_begin < 0 || row_end < row_begin || row_end > size ||
+      offsets == nullptr || tex_face == nullptr || tex_bary == nullptr || tex_pos == nullptr || (clamp != 0 && clamp != 1) ||
+      (n_blocks > 0 && (block_log == nullptr || block_faces == nullptr)) ||
+      (n_faces > 0 && (faces == nullptr || rot == nullptr || (n_verts > 0 && verts == nullptr))))
+    return F2N_ERR_INVALID_ARG;
+  if (row_end == row_begin) return F2N_OK;
+  hipLaunchKernelGGL(atlas_texels_kernel, dim3(f2n_div_up(size, 16), f2n_div_up(row_end - row_begin, 16)), dim3(256), 0, (hipStream_t) stream,
+                     n_verts, n_faces, verts, faces, n_blocks, size, (const long long*) offsets, block_log, block_faces, rot, clamp, row_begin,
+                     row_end, tex_face, tex_bary, tex_pos);
+  return f2n_launch_status();
+}
+
+int f2n_texture_sample(void* stream, int size, int channels, const float* tex, int64_t n, const float* uv, float* out) {
+  if (size < 1 || size > 32768 || channels < 1 || channels > 64 || n < 0 || n > (int64_t) 1 << 40 ||
+      (n > 0 && (tex == nullptr || uv == nullptr || out == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  const int64_t blocks = (n * channels + 255) / 256;
+  if (blocks > 0x7fffffffLL) return F2N_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(texture_sample_kernel, dim3((unsigned) blocks), dim3(256), 0, (hipStream_t) stream, size, channels, tex, n, uv, out);
+  return f2n_launch_status();
+}

@@ -24,6 +24,18 @@ Options (hydra-style overrides, no `mesh` group in the configs):
                    (check_mesh: the field's surface distance per ray against a ray cast at the mesh, host.mesh_raycast) ->
                    <same name>_check.json and one printed line; options check.res_level (4), check.tau (0.5), check.min_opacity (0.5),
                    check.max_views (0: all), with the meaning of their tsdf.* namesakes.  Default false: nothing changes
+  mesh.texture     true: the mesh just written is also exported with a baked texture (runner.bake_texture: one right-triangle chart per
+                   face in a power-of-two atlas, host.mesh_atlas; every owned texel takes the field's colour at its point of the
+                   surface) -> <same name>_tex.obj, _tex.mtl and _tex.png, and one printed line.  It works with either mesh.source and
+                   with or without mesh.simplify, and computes the per-vertex normals whether or not mesh.normals writes them to the
+                   .ply.  Options: texture.texels_per_step (2.0: texels per grid step of mesh.resolution; not measured on a scene),
+                   texture.max_size (8192, a power of two: the density is halved until the atlas fits), texture.max_block_log2 (7),
+                   texture.source (point | ray: the radiance AT the texel's point seen along the inward normal, as mesh.colors, or
+                   the volume-rendered colour of a short ray through it), texture.ray_steps (4.0 grid steps, the TSDF truncation's
+                   default; not measured on a scene).  With mesh.check the check JSON gains texture_psnr and n_texture_rays.
+                   Known limits: no mip-safe padding between blocks (nearest and bilinear filtering are clean, mipmaps bleed); charts
+                   are per face, so filtering is not seam-free across edges beyond the replicated gutter; a chart's anisotropy is
+                   bounded only by putting the longest edge on the diagonal.  Default false: nothing changes
   mesh.source      density | tsdf (default density): the iso-surface of the raw density at mesh.level, or the zero crossing of a
                    truncated signed distance field fused from the training views' rendered depth (fuse_tsdf; mesh.level is not
                    used, normals of source "grid" come from the TSDF) -> <exp>/meshes/<iter>_<res>_tsdf.ply
@@ -327,7 +339,8 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
     if k >= 2:  # (cell = k * step as ONE float32 product: what extract_mesh_attrs uses)
         verts, faces, _ = host.mesh_simplify(verts, faces, float(np.float32(k) * np.float32(t["step"])), t["lo"])
     normals = colors = None
-    if (o["normals"] or o["colors"]) and len(verts) > 0:
+    tex_on, nrm = texture_options(cfg)["texture"], None
+    if (o["normals"] or o["colors"] or tex_on) and len(verts) > 0:
         nrm = host.grid_normals(t["g"], verts, t["lo"], t["step"])  # (g is positive inside, as a density is: the same sign)
         if o["normal_source"] == "field":  # the field's own gradient at the vertex; the grid's where that vanishes
             fn = runner.field_normals(verts)
@@ -346,8 +359,9 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
     write_ply(path, v, faces.cpu().numpy(), normals, colors)
     print("Mesh: %d vertices, %d faces%s from the TSDF of %d views (%d of %d grid points known, truncation %g) -> %s" % (
         len(v), len(faces), _simplified(k, faces_in), t["n_views"], int(t["valid"].sum()), t["valid"].numel(), t["trunc"], path))
+    tex = _run_texture(runner, cfg, scene, verts, faces, nrm, t["step"], path) if tex_on else None
     if check_options(cfg)["check"]:
-        _run_check(runner, cfg, scene, dataset, verts, faces, t["step"], path)
+        _run_check(runner, cfg, scene, dataset, verts, faces, t["step"], path, tex)
     return path
 
 
@@ -362,11 +376,13 @@ def check_options(cfg):
     return o
 
 
-def render_mesh(verts, faces, rays_o, rays_d, bounds=None, accel=None, normals=None, colors=None):
+def render_mesh(verts, faces, rays_o, rays_d, bounds=None, accel=None, normals=None, colors=None, uv=None, texture=None):
     """The mesh seen along rays (host.mesh_raycast; accel None: one is built with the default cell): dict of hit [R] bool, t [R],
     face [R] int32 (-1: none), bary [R,3], points (o + t d), face_normals (the unit geometric normal of the hit face, (B - A) x (C - A)),
     facing (-n.d > 0: the ray meets the face's front) and, for per-vertex normals / colors [V,3], their barycentric blend at the hit
-    (the normal renormalised).  Rows without a hit are zero.  Everything but the ray cast is plain torch."""
+    (the normal renormalised).  With uv [F,3,2] and texture [S,S,C] (host.mesh_atlas, runner.bake_texture) two more: uv [R,2], the
+    blend of the hit face's three corners' uv, and tex_colors [R,C], host.texture_sample there.  Rows without a hit are zero.
+    Everything but the ray cast and the texture lookup is plain torch."""
     import torch
     from . import runtime
     host = runtime.host()
@@ -382,6 +398,8 @@ def render_mesh(verts, faces, rays_o, rays_d, bounds=None, accel=None, normals=N
         for name, attr in (("normals", normals), ("colors", colors)):
             if attr is not None:
                 out[name] = zero3.clone()
+        if uv is not None and texture is not None:
+            out.update(uv=zero3[:, :2].clone(), tex_colors=torch.zeros((R, int(texture.shape[2])), dtype=torch.float32, device=t.device))
         return out
     v = verts.to(torch.float32).reshape(-1, 3)
     corners = faces.reshape(-1, 3).long()[face.clamp_min(0).long()]  # [R,3]
@@ -400,6 +418,11 @@ def render_mesh(verts, faces, rays_o, rays_d, bounds=None, accel=None, normals=N
                 lx = x.norm(dim=1, keepdim=True)
                 x = torch.where(lx > 0, x / lx.clamp_min(1e-38), zero3)
             out[name] = torch.where(hit[:, None], x, zero3)
+    if uv is not None and texture is not None:
+        at = (uv.to(torch.float32).reshape(-1, 3, 2)[face.clamp_min(0).long()] * bary[:, :, None]).sum(1)
+        out["uv"] = torch.where(hit[:, None], at, torch.zeros_like(at)).contiguous()
+        tc = host.texture_sample(texture, out["uv"])
+        out["tex_colors"] = torch.where(hit[:, None], tc, torch.zeros_like(tc))
     return out
 
 
@@ -421,13 +444,16 @@ def compare_depth(t_field, has_field, t_mesh, has_mesh, step):
             "within_1": share(int((e <= 1).sum()), nb), "within_2": share(int((e <= 2).sum()), nb)}
 
 
-def check_mesh(runner, dataset, scene, verts, faces, o):
+def check_mesh(runner, dataset, scene, verts, faces, o, uv=None, texture=None):
     """A mesh (verts, faces in the NORMALISED frame, before to_world) against the field it came from, seen from the training cameras: for
     every checked camera the rays of tsdf_camera_rays at o["res_level"] are rendered (runner.render_geometry: has_field = a surface
     sample with opacity >= o["min_opacity"], t_field = surf_t) and cast at the mesh (render_mesh, the same rays and bounds).  Returns the
     pooled compare_depth statistics in grid steps of o["step"], plus faces_seen (the share of faces that are some checked ray's first
     hit), normal_agreement (the mean |face normal . surface normal| where both have a surface), n_views, n_faces and views (the
-    per-view statistics).  No side effect on training: nothing is drawn, no vote is cast, a pending step is flushed first."""
+    per-view statistics).  With uv and texture (runner.bake_texture) also texture_psnr, -10 log10 of the mean squared difference between
+    the texture seen along the ray (render_mesh's tex_colors) and the field's rendered colour over the n_texture_rays rays where both
+    have a surface (the mean square floored at 1e-10; 0 without such a ray).  No side effect on training: nothing is drawn, no vote is
+    cast, a pending step is flushed first."""
     import torch
     from . import runtime
     host = runtime.host()
@@ -440,11 +466,16 @@ def check_mesh(runner, dataset, scene, verts, faces, o):
     seen = torch.zeros(nf + 1, dtype=torch.bool, device=verts.device)
     pool = {k: [] for k in ("tf", "hf", "tm", "hm", "agree")}
     per_view = []
+    tex, sq_err, n_tex = uv is not None and texture is not None, 0.0, 0
     for idx in views:
         ro, rd, b, _, _ = tsdf_camera_rays(dataset, scene["bounds"], idx, int(o["res_level"]))
         g = runner.render_geometry(ro, rd, b, tau=o["tau"])
         hf = (g["surf_idx"] >= 0) & (g["opacity"] >= o["min_opacity"])
-        m = render_mesh(verts, faces, ro, rd, b, accel=accel)
+        m = render_mesh(verts, faces, ro, rd, b, accel=accel, **(dict(uv=uv, texture=texture) if tex else {}))
+        if tex:
+            both = hf & m["hit"]
+            sq_err += float(((m["tex_colors"][both] - g["colors"][both]).double() ** 2).sum())
+            n_tex += int(both.sum())
         seen[torch.where(m["hit"], m["face"], torch.full_like(m["face"], nf)).long()] = True
         agree = (m["face_normals"] * g["surf_normals"]).sum(1).abs()[hf & m["hit"]]
         stats = compare_depth(g["surf_t"], hf, m["t"], m["hit"], o["step"])
@@ -459,23 +490,167 @@ def check_mesh(runner, dataset, scene, verts, faces, o):
     out.update(faces_seen=float(int(seen[:nf].sum())) / nf if nf else 0.0, normal_agreement=float(agree.double().mean()) if agree.numel() else 0.0,
                n_views=len(views), n_faces=nf, step=float(o["step"]), res_level=int(o["res_level"]), tau=float(o["tau"]),
                min_opacity=float(o["min_opacity"]), views=per_view)
+    if tex:
+        out.update(texture_psnr=float(-10.0 * np.log10(max(sq_err / (3 * n_tex), 1e-10))) if n_tex else 0.0, n_texture_rays=n_tex)
     return out
 
 
-def _run_check(runner, cfg, scene, dataset, verts, faces, step, path):
+def _run_check(runner, cfg, scene, dataset, verts, faces, step, path, tex=None):
     """mesh.check=true: check_mesh of the mesh just written -> <path without .ply>_check.json and one printed line."""
     import json
     if dataset is None:
         raise ValueError("mesh.check=true casts the training cameras' rays at the mesh: it needs the data set")
     o = check_options(cfg)
     o["step"] = float(step)
-    res = check_mesh(runner, dataset, scene, verts, faces, o)
+    res = check_mesh(runner, dataset, scene, verts, faces, o, **(dict(uv=tex["uv"], texture=tex["texture"]) if tex else {}))
     out = path[:-4] + "_check.json"
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1, sort_keys=True)
     print("Check: completeness %.4f, depth error median %.3f / p90 %.3f grid steps, extra %.4f, faces seen %.4f (%d views at 1/%d) -> %s" % (
         res["completeness"], res["median"], res["p90"], res["extra"], res["faces_seen"], res["n_views"], o["res_level"], out))
     return out
+
+
+TEXTURE_SOURCES = ("point", "ray")
+
+
+def texture_options(cfg):
+    """mesh.texture and the texture.* options.  texels_per_step = 2 and ray_steps = 4 (the TSDF truncation's default) are not measured on
+    a scene."""
+    m = cfg.get("mesh") or {}
+    t = cfg.get("texture") or {}
+    src = str(t.get("source", "point")).strip().lower()
+    if src not in TEXTURE_SOURCES:
+        raise ValueError("texture.source must be one of %s, got %r" % (" | ".join(TEXTURE_SOURCES), t.get("source")))
+    o = {"texture": _flag(m.get("texture", False)), "texels_per_step": float(t.get("texels_per_step", 2.0)), "max_size": int(t.get("max_size", 8192)),
+         "max_block_log2": int(t.get("max_block_log2", 7)), "source": src, "ray_steps": float(t.get("ray_steps", 4.0))}
+    if (not 0.0 < o["texels_per_step"] < float("inf") or not 0.0 < o["ray_steps"] < float("inf") or not 2 <= o["max_block_log2"] <= 13 or
+            not 4 <= o["max_size"] <= 8192 or o["max_size"] & (o["max_size"] - 1)):
+        raise ValueError("texture.texels_per_step and texture.ray_steps must be > 0 and finite, texture.max_block_log2 in [2, 13] and "
+                         "texture.max_size a power of two in [4, 8192], got %r" % (o,))
+    return o
+
+
+BAKE_CHUNK = 1 << 20  # texels per radiance query / rays per render of bake_texture
+
+
+def bake_texture(runner, verts, faces, normals, density, max_size=8192, max_log=7, source="point", ray_steps=4.0, step=None):
+    """runner.bake_texture: a texture atlas of the mesh (verts, faces, per-vertex normals [V,3] in the NORMALISED frame; density in texels
+    per length unit) filled from the field.  host.mesh_atlas lays one right-triangle chart per face into an atlas of at most max_size
+    (the density is halved until it fits) and host.mesh_atlas_texels (clamp on) gives every owned texel its point of the surface and
+    its weights; the texel's direction is minus the normalised blend of its corners' normals by those weights (the face's geometric
+    normal where the blend vanishes, (0, 0, -1) where that vanishes too).  source "point": the colour is
+    runner.query_radiance(point, dir)[1], the definition of mesh.colors, so a texel on a vertex carries that vertex's colour;
+    source "ray": the volume-rendered colour of runner.render_geometry along the ray from point - h dir in direction dir over (0, 2 h)
+    with h = ray_steps * step (step: the grid step of the mesh, required) -- it starts h outside the surface and ends h inside it.
+    ray_steps = 4 grid steps is the TSDF truncation's default, not measured on a scene.  Returns dict of uv [F,3,2], size, texture
+    [S,S,3] (0 where no face owns the texel), tex_face [S,S] int32, density_used, texels_used.  No side effect on training: a pending
+    step is flushed first, nothing is drawn, no vote is cast."""
+    import torch
+    from . import runtime
+    host = runtime.host()
+    if source not in TEXTURE_SOURCES:
+        raise ValueError("bake_texture: source must be one of %s, got %r" % (" | ".join(TEXTURE_SOURCES), source))
+    if source == "ray" and not (step is not None and float(step) > 0.0 and float(ray_steps) > 0.0):
+        raise ValueError("bake_texture: source='ray' needs the grid step of the mesh (step > 0) and ray_steps > 0")
+    runner.flush()
+    uv, size, blocks, used = host.mesh_atlas(verts, faces, float(density), int(max_size), int(max_log))
+    tex_face, bary, pos = host.mesh_atlas_texels(verts, faces, blocks, size, True)
+    texture = torch.zeros((size, size, 3), dtype=torch.float32, device=pos.device)
+    own = tex_face.reshape(-1) >= 0
+    at = own.nonzero().reshape(-1)
+    if at.numel():
+        corners = faces.reshape(-1, 3).long()[tex_face.reshape(-1)[at].long()]  # [T,3]
+        w, p = bary.reshape(-1, 3)[at], pos.reshape(-1, 3)[at].contiguous()
+        n = (normals.to(torch.float32).reshape(-1, 3)[corners] * w[:, :, None]).sum(1)
+        P = verts.to(torch.float32).reshape(-1, 3)[corners]
+        gn = torch.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0], dim=1)
+        ln, lg = n.norm(dim=1, keepdim=True), gn.norm(dim=1, keepdim=True)
+        up = torch.tensor([[0.0, 0.0, 1.0]], device=p.device)
+        gn = torch.where((lg > 0) & torch.isfinite(lg), gn / lg.clamp_min(1e-38), up)
+        dirs = (-torch.where((ln > 0) & torch.isfinite(ln), n / ln.clamp_min(1e-38), gn)).contiguous()
+        cols = []
+        for k in range(0, int(at.numel()), BAKE_CHUNK):
+            pk, dk = p[k:k + BAKE_CHUNK].contiguous(), dirs[k:k + BAKE_CHUNK].contiguous()
+            if source == "point":
+                cols.append(runner.query_radiance(pk, dk)[1])
+            else:
+                h = float(np.float32(ray_steps) * np.float32(step))
+                b = torch.tensor([[0.0, 2.0 * h]], dtype=torch.float32, device=p.device).repeat(len(pk), 1).contiguous()
+                cols.append(runner.render_geometry((pk - h * dk).contiguous(), dk, b)["colors"])
+        texture.reshape(-1, 3)[at] = torch.cat(cols)
+    return {"uv": uv, "size": int(size), "texture": texture, "tex_face": tex_face, "density_used": float(used), "texels_used": int(at.numel())}
+
+
+def write_png(path, rgb_uint8):
+    """8-bit RGB PNG of rgb_uint8 [H,W,3] from the standard library alone (zlib, struct): one IDAT, filter 0 on every row."""
+    import struct
+    import zlib
+    a = np.ascontiguousarray(rgb_uint8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("write_png: rgb_uint8 must be a uint8 array [H,W,3]")
+    h, w = int(a.shape[0]), int(a.shape[1])
+    rows = np.zeros((h, 1 + w * 3), np.uint8)
+    rows[:, 1:] = a.reshape(h, w * 3)
+    chunk = lambda kind, data: struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)  # noqa: E731
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+                 chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+    return path
+
+
+def write_obj(path, verts, faces, uv, normals=None, texture_name="texture.png"):
+    """Wavefront OBJ with a material: `v` lines, `vn` lines when normals [V,3] are given, three `vt` per face (uv [F,3,2] in image
+    convention -> vt = (x, 1 - y)), then `f a/ta[/na]` with 1-based indices; <path without .obj>.mtl names texture_name in map_Kd."""
+    v = np.asarray(verts, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    t = np.asarray(uv, np.float32).reshape(-1, 3, 2)
+    if len(t) != len(f) or (normals is not None and np.asarray(normals).reshape(-1, 3).shape[0] != len(v)):
+        raise ValueError("write_obj: uv must be [F,3,2] and normals [V,3]")
+    mtl = path[:-4] + ".mtl" if path.lower().endswith(".obj") else path + ".mtl"
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(mtl, "w") as fh:
+        fh.write("newmtl baked\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s\n" % texture_name)
+    lines = ["mtllib %s" % os.path.basename(mtl)]
+    lines += ["v %.9g %.9g %.9g" % tuple(r) for r in v.tolist()]
+    if normals is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(r) for r in np.asarray(normals, np.float32).reshape(-1, 3).tolist()]
+    t2 = t.reshape(-1, 2)
+    lines += ["vt %.9g %.9g" % (x, y) for x, y in zip(t2[:, 0].tolist(), (np.float32(1.0) - t2[:, 1]).tolist())]
+    lines.append("usemtl baked")
+    for k, (a, b, c) in enumerate(f.tolist()):
+        ta = 3 * k + 1
+        if normals is not None:
+            lines.append("f %d/%d/%d %d/%d/%d %d/%d/%d" % (a + 1, ta, a + 1, b + 1, ta + 1, b + 1, c + 1, ta + 2, c + 1))
+        else:
+            lines.append("f %d/%d %d/%d %d/%d" % (a + 1, ta, b + 1, ta + 1, c + 1, ta + 2))
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    return path
+
+
+def _run_texture(runner, cfg, scene, verts, faces, normals, step, path):
+    """mesh.texture=true: runner.bake_texture of the mesh just written -> <path without .ply>_tex.obj / .mtl / .png and one printed line.
+    Returns bake_texture's dict (mesh.check reads uv and texture from it)."""
+    import torch
+    t = texture_options(cfg)
+    base = path[:-4] + "_tex"
+    density = float(np.float32(t["texels_per_step"]) / np.float32(step))
+    if normals is None:
+        normals = torch.zeros((int(verts.shape[0]), 3), dtype=torch.float32, device=verts.device)
+    r = runner.bake_texture(verts, faces, normals, density, t["max_size"], t["max_block_log2"], t["source"], t["ray_steps"], step)
+    write_png(base + ".png", quantize_colors(r["texture"].cpu().numpy()))
+    write_obj(base + ".obj", to_world(verts.cpu().numpy(), scene["center"], scene["radius"]), faces.cpu().numpy(), r["uv"].cpu().numpy(),
+              normals.cpu().numpy(), os.path.basename(base + ".png"))
+    halved = "" if r["density_used"] == density else " (halved from %g to fit texture.max_size=%d)" % (density, t["max_size"])
+    print("Texture: atlas %d x %d, %d texels used, %g texels per unit%s, source %s -> %s" % (
+        r["size"], r["size"], r["texels_used"], r["density_used"], halved, t["source"], base + ".obj"))
+    return r
 
 
 def _simplified(k, faces_in):
@@ -503,8 +678,15 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
         write_ply(path, v, faces.cpu().numpy(), m["normals"].cpu().numpy() if o["normals"] else None,
                   m["colors"].cpu().numpy() if o["colors"] else None)
     print("Mesh: %d vertices, %d faces%s at level %g -> %s" % (len(v), len(faces), _simplified(k, faces_in), o["level"], path))
-    if check_options(cfg)["check"]:
+    tex = None
+    if texture_options(cfg)["texture"] or check_options(cfg)["check"]:
         from . import runtime
         step = runtime.host().grid_spec([float(x) for x in o["bbox_min"]], [float(x) for x in o["bbox_max"]], int(o["resolution"]))[0]
-        _run_check(runner, cfg, scene, dataset, verts, faces, step, path)
+    if texture_options(cfg)["texture"]:  # the normals are computed for the texture whether or not the .ply carries them
+        m = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"], True, False,
+                                      o["normal_source"], *((k,) if k >= 2 else ()))
+        verts, faces = m["verts"], m["faces"]
+        tex = _run_texture(runner, cfg, scene, verts, faces, m["normals"], step, path)
+    if check_options(cfg)["check"]:
+        _run_check(runner, cfg, scene, dataset, verts, faces, step, path, tex)
     return path

@@ -202,6 +202,7 @@ def main(argv=None):
                 save_png(os.path.join(exp_dir, "images", "%d_%d.png" % (runner.iter_step, idx)), runner.visualize_image(ds, idx))
         elif mode == "extract_mesh":  # no reference counterpart: <exp>/meshes/<iter>_<res>.ply (mesh.py; options mesh.*)
             from . import mesh
+            mesh.texture_options(cfg)  # (mesh.texture / texture.*: a bad value raises before anything is extracted or written)
             # (the TSDF is fused from renders of the training cameras, and mesh.check casts their rays at the mesh: both need them)
             if mesh.options(cfg)["source"] == "tsdf" or mesh.check_options(cfg)["check"]:
                 mesh.extract(runner, cfg, sc, exp_dir, dataset=ds)

@@ -27,6 +27,8 @@ def host():
         _host = importlib.util.module_from_spec(spec)
         sys.modules["f2_nerf_amd._f2n_host"] = _host
         spec.loader.exec_module(_host)
+        from . import mesh  # runner.bake_texture: the kernels are the module's, what joins them to the runner's queries is mesh.py
+        _host.ExpRunner.bake_texture = mesh.bake_texture
     return _host
 
 

@@ -1145,6 +1145,67 @@ int f2n_mesh_raycast(void* stream, int n_verts, int n_faces, const float* verts 
                      const int32_t* cell_faces /*[E]*/, int n_rays, const float* rays_o /*[R,3]*/, const float* rays_d /*[R,3]*/,
                      const float* bounds /*[R,2] or NULL*/, float* out_t /*[R]*/, int32_t* out_face /*[R]*/, float* out_bary /*[R,3]*/);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Texture atlas of a triangle mesh (additive; the ABI version is unchanged): one right-triangle chart per face, two charts to a
+ * square block of 2^k texels a side, blocks placed by the Morton decode of a prefix sum; the texel-to-surface map; a bilinear
+ * lookup.  No reference counterpart.  csrc/octree.hip.  Every operation is ONE rounding of the stated width, never an FMA, and one
+ * lane owns one output: nothing depends on the schedule.  tests/atlas_ref.py restates all of it in numpy.
+ * ------------------------------------------------------------------------------------------------- */
+/* f2n_atlas_classify: no reference counterpart.  Per face (a, b, c) with vertices A, B, C, all in fp64 from the fp32 coordinates:
+ *   p = B - A, q = C - A, e = C - B (per coordinate: (double) x - (double) y);
+ *   |AB|^2 = (p_x p_x + p_y p_y) + p_z p_z, likewise |BC|^2 from e and |CA|^2 from q;
+ *   n = (p_y q_z - p_z q_y, p_z q_x - p_x q_z, p_x q_y - p_y q_x);  n2 = (n_x n_x + n_y n_y) + n_z n_z  (= (2 area)^2);
+ *   l = sqrt(sqrt(n2)) * (double) density  (the leg, in texels, of the right isosceles triangle of the face's area);
+ *   need = max(4, ceil(l) + 3);  log_s = the smallest k in [2, max_log] with 2^k >= need, max_log if there is none.
+ *   rot in {0, 1, 2} = the face's corner opposite its longest edge (corner 0 faces BC, 1 faces CA, 2 faces AB), the first among
+ *   equals in the order 0, 1, 2: r = 0; |CA|^2 > |BC|^2: r = 1; |AB|^2 > that maximum: r = 2.  Chart corner k (0: the right angle,
+ *   1: along x, 2: along y) is the face's corner (rot + k) % 3: a cyclic shift, so the orientation is kept.
+ *   A face with an index outside [0, V), a vertex that is not finite or n2 == 0 is DEGENERATE: log_s = 2, rot = 4 (bit 2 of rot is
+ *   the flag, its rotation is 0).  It keeps a slot in the atlas and gets uv, but owns no texel.  It is never an error.
+ * density must be positive and finite, 2 <= max_log <= 13: F2N_ERR_INVALID_ARG otherwise.
+ *
+ * The caller's plumbing between the calls (sort, prefix sums: host/RendererQuery.cpp MeshAtlas, capi.mesh_atlas):
+ *   order: the faces sorted by the int64 key (max_log - log_s) F + f: classes descending, faces ascending within a class;
+ *   positions 2j and 2j + 1 of a class share its block j, the first as the LOWER chart, the second as the UPPER one (a class with an
+ *   odd count leaves its last upper slot empty); blocks are numbered through the classes in that order;
+ *   slot [F] int32 = 2 block + upper;  block_log [B] int32;  block_faces [B,2] int32 (lower, upper; -1: empty);
+ *   offsets [B + 1] int64 = the exclusive prefix sum of 4^block_log (sizes descend, so every offset is a multiple of its block's area);
+ *   a block's origin (x0, y0) = the Morton decode of its offset (even bits -> x, odd bits -> y);
+ *   size S = the smallest power of two with S^2 >= offsets[B], at least 4 (and at most 8192 = 2^13).
+ * f2n_atlas_place: no reference counterpart.  uv [F,3,2] fp32 in the order of the face's own corners, image convention (x right, y
+ *   down), = (origin + chart corner) / S, in fp32: the sum and the division by a power of two are exact.  With s = 2^log_s the
+ *   chart corners in texels from the origin are  lower: (0.5, 0.5), (s - 2.5, 0.5), (0.5, s - 2.5);  upper: (s - 0.5, s - 0.5),
+ *   (2.5, s - 0.5), (s - 0.5, 2.5): legs of s - 3 texels between texel centres.  The bilinear footprint of the lower chart lies in the
+ *   texels i + j <= s - 2 of the block, that of the upper chart in i + j >= s; the diagonal i + j = s - 1 is a gutter of the lower one.
+ *   A face whose slot is negative or names no block gets zeros.  size must be a power of two in [4, 8192]: F2N_ERR_INVALID_ARG.
+ * f2n_atlas_texels: no reference counterpart.  One lane per texel (x, y) of the rows [row_begin, row_end) (a wave owns an 8 x 8 tile);
+ *   the other rows are not touched.  m = the Morton code of (x, y); no block if m >= offsets[B], else block = the last one with
+ *   offsets[block] <= m (a binary search), s = 2^block_log, i = x - x0, j = y - y0.  Lower chart iff i + j <= s - 1, with
+ *   (u, v) = ((float) i / (float) (s - 3), (float) j / (float) (s - 3)); else upper, from (s - 1 - i, s - 1 - j) likewise.
+ *   Raw weights of the chart corners, fp32: w0 = (1 - u) - v, w1 = u, w2 = v; the face's corner j carries w of chart corner
+ *   (j - rot) mod 3: (b0, b1, b2).  clamp == 1 and some b < 0 (a gutter texel): b_k = max(b_k, 0), sum = (b0 + b1) + b2, b_k = b_k / sum;
+ *   with no negative weight, and for clamp == 0 always, the weights stay raw (gutter texels then extrapolate, so that bilinear
+ *   filtering reproduces a linear function of position everywhere inside a chart).
+ *   tex_face [S,S] int32 = the face, or -1 with zero weights and position where there is no block, an empty slot, a slot whose face
+ *   index is outside [0, F) or a degenerate face;  tex_bary [S,S,3] = (b0, b1, b2), the weights tex_pos was blended with;
+ *   tex_pos [S,S,3]: per coordinate (b0 A + b1 B) + b2 C in fp32 (three products, two sums).
+ *   clamp other than 0 / 1, rows outside [0, S]: F2N_ERR_INVALID_ARG.
+ * f2n_texture_sample: no reference counterpart.  out [N,C] = the bilinear lookup of tex [S,S,C] (row y, column x) at uv [N,2] = (x, y)
+ *   with texel centres at (i + 0.5) / S, clamped to the edge; S in [1, 32768] need not be a power of two, C in [1, 64].  fp32:
+ *   fx = min(max(u S - 0.5, 0), S - 1) (a product, a difference), x0 = floor(fx), x1 = min(x0 + 1, S - 1), ax = fx - x0, cx = 1 - ax;
+ *   likewise fy, y0, y1, ay, cy from v;  out = ((t00 (cx cy) + t10 (ax cy)) + t01 (cx ay)) + t11 (ax ay) with t10 = tex[y0][x1],
+ *   t01 = tex[y1][x0].  A row whose u or v is not finite gives zeros. */
+int f2n_atlas_classify(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/, float density,
+                       int max_log, int32_t* log_s /*[F]*/, int32_t* rot /*[F]*/);
+int f2n_atlas_place(void* stream, int n_faces, int n_blocks, int size, const int32_t* log_s /*[F]*/, const int32_t* rot /*[F]*/,
+                    const int32_t* slot /*[F]*/, const int64_t* offsets /*[B+1]*/, float* uv /*[F,3,2]*/);
+int f2n_atlas_texels(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/, int n_blocks,
+                     int size, const int64_t* offsets /*[B+1]*/, const int32_t* block_log /*[B]*/, const int32_t* block_faces /*[B,2]*/,
+                     const int32_t* rot /*[F]*/, int clamp, int row_begin, int row_end, int32_t* tex_face /*[S,S]*/,
+                     float* tex_bary /*[S,S,3]*/, float* tex_pos /*[S,S,3]*/);
+int f2n_texture_sample(void* stream, int size, int channels, const float* tex /*[S,S,C]*/, int64_t n, const float* uv /*[N,2]*/,
+                       float* out /*[N,C]*/);
+
 #ifdef __cplusplus
 }
 #endif
