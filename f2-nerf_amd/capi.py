@@ -1098,6 +1098,68 @@ def mesh_raycast(verts, faces, accel, rays_o, rays_d, bounds=None):
     return t, face, bary
 
 
+# ---------------------------------------------------------------- mesh-to-mesh distance: closest points and surface samples
+MESH_SAMPLE_PURPOSE = 0x8CB92BA72F3D8DD7  # host/Renderer.h: kMeshSamplePurpose
+
+
+def mesh_closest_point(verts, faces, accel, points, max_dist=float("inf")):
+    """(dist [N] (+inf: none within max_dist), face [N] int32 (-1: none), bary [N,3]): the points' closest point on the mesh
+    (f2n_mesh_closest_point); accel = mesh_raycast_build's tuple, or None for the brute-force mode.  ValueError for a finite point outside
+    the grid walk's domain."""
+    nv, nf, N = int(verts.shape[0]), int(faces.shape[0]), int(points.shape[0])
+    dev = points.device
+    if not float(max_dist) >= 0.0:
+        raise ValueError("mesh_closest_point: max_dist must be >= 0 (inf: no cut-off)")
+    dist = torch.full((N,), float("inf"), dtype=torch.float32, device=dev)
+    face = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    bary = torch.zeros((N, 3), dtype=torch.float32, device=dev)
+    lo_c = dims_c = None
+    cell, cs, cf = 0.0, None, None
+    if accel is not None:
+        lo, cell, dims, cs, cf = accel
+        if cs.numel() != int(dims[0]) * int(dims[1]) * int(dims[2]) + 1:
+            raise ValueError("mesh_closest_point: cell_start does not match dims")
+        far = max(max(abs(float(lo[k])), abs(float(lo[k]) + dims[k] * float(cell))) for k in range(3))
+        if N:
+            far = max(far, float(torch.where(torch.isfinite(points), points.abs(), points.new_zeros(1)).max()))
+        if not far <= RAYCAST_DOMAIN_CELLS * cell:
+            raise ValueError("mesh_closest_point: a point (or the grid) lies more than 2^15 cells from the frame's origin: outside the domain "
+                             "in which the grid walk is exact; use a larger cell or accel=None")
+        lo_c, dims_c = _lo3(lo), (ctypes.c_int32 * 3)(*(int(x) for x in dims))
+    _ck(lib().f2n_mesh_closest_point(_stream(), _i(nv), _i(nf), _p(verts, "f32", nf == 0), _p(faces, "i32", nf == 0), lo_c, _f(cell), dims_c,
+                                     _p(cs, "i32", True), _p(cf if cf is not None and cf.numel() else None, "i32", True), _i(N),
+                                     _p(points, "f32", N == 0), _f(max_dist), _p(dist, "f32", N == 0), _p(face, "i32", N == 0),
+                                     _p(bary, "f32", N == 0)), "f2n_mesh_closest_point")
+    return dist, face, bary
+
+
+def mesh_sample_surface(verts, faces, n, seed=0):
+    """(points [n,3], face [n] int32, bary [n,3]): n area-uniform, stratified samples of the surface (f2n_mesh_face_weights -> max, prefix
+    sum -> f2n_mesh_sample_surface), a pure function of (mesh, n, seed).  ValueError for a mesh without area."""
+    nv, nf, n = int(verts.shape[0]), int(faces.shape[0]), int(n)
+    dev = verts.device
+    if n < 0 or n >= 2 ** 31:
+        raise ValueError("mesh_sample_surface: n must lie in [0, 2^31)")
+    area2 = torch.zeros(nf, dtype=torch.float64, device=dev)
+    weights = torch.zeros(nf, dtype=torch.int64, device=dev)
+    if nf:
+        _ck(lib().f2n_mesh_face_weights(_stream(), _i(nv), _i(nf), _p(verts, "f32", nv == 0), _p(faces, "i32"), _d(0.0),
+                                        ctypes.c_void_p(area2.data_ptr()), ctypes.c_void_p(0)), "f2n_mesh_face_weights")
+    largest = float(area2.max()) if nf else 0.0
+    if not largest > 0.0:
+        raise ValueError("mesh_sample_surface: the mesh has no face with an area")
+    _ck(lib().f2n_mesh_face_weights(_stream(), _i(nv), _i(nf), _p(verts, "f32"), _p(faces, "i32"), _d(largest * 2.0 ** -31), ctypes.c_void_p(0),
+                                    _p(weights, "i64")), "f2n_mesh_face_weights")
+    cum = weights.cumsum(0).contiguous()
+    pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    bary = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    key = (int(seed) ^ MESH_SAMPLE_PURPOSE) & 0xFFFFFFFFFFFFFFFF
+    _ck(lib().f2n_mesh_sample_surface(_stream(), _i(nv), _i(nf), _p(verts, "f32"), _p(faces, "i32"), _p(cum, "i64"), _i(n), ctypes.c_uint64(key),
+                                      _p(pts, "f32", n == 0), _p(face, "i32", n == 0), _p(bary, "f32", n == 0)), "f2n_mesh_sample_surface")
+    return pts, face, bary
+
+
 # ---------------------------------------------------------------- texture atlas of a triangle mesh
 def mesh_atlas(verts, faces, density, max_size=8192, max_log=7):
     """(uv [F,3,2], size, blocks, density_used): host.mesh_atlas through ctypes (f2n_atlas_classify -> sort and prefix sums ->

@@ -112,6 +112,18 @@ MeshRaycastAccel MeshRaycastBuild(const Tensor& verts, const Tensor& faces, floa
 std::tuple<Tensor, Tensor, Tensor> MeshRaycast(const Tensor& verts, const Tensor& faces, const MeshRaycastAccel* accel, const Tensor& rays_o,
                                                const Tensor& rays_d, const Tensor& bounds);
 
+// Mesh-to-mesh distance (f2n_mesh_closest_point, f2n_mesh_face_weights, f2n_mesh_sample_surface; include/f2n_abi.h states both).
+// (dist [N] (+inf: none within max_dist), face [N] int32 (-1: none), bary [N,3]) of the points' closest point on the mesh; accel NULL:
+// the brute-force mode.  The accel is MeshRaycastBuild's, unchanged.  The points are processed in the caller's order (sorting them
+// by grid cell first was measured and bought nothing: DESIGN.md section 3).  std::invalid_argument for a finite point more than 2^15
+// cells from the frame's origin and for a max_dist that is negative or NaN.
+std::tuple<Tensor, Tensor, Tensor> MeshClosestPoint(const Tensor& verts, const Tensor& faces, const MeshRaycastAccel* accel, const Tensor& points,
+                                                    float max_dist);
+// (points [n,3], face [n] int32, bary [n,3]): n area-uniform, stratified samples of the surface, a pure function of (mesh, n, seed).
+// std::invalid_argument for a mesh without area and for n < 0.
+constexpr uint64_t kMeshSamplePurpose = 0x8CB92BA72F3D8DD7ull;  // the key of the samples' Philox draws is seed ^ this (KeyedDraws.h)
+std::tuple<Tensor, Tensor, Tensor> MeshSampleSurface(const Tensor& verts, const Tensor& faces, int64_t n, uint64_t seed);
+
 // Texture atlas of a mesh (f2n_atlas_*; include/f2n_abi.h states the layout): one right-triangle chart per face, two to a power-of-two
 // block, blocks placed by the Morton decode of the prefix sum of their areas.  density = texels per length unit; while the atlas is
 // wider than max_size (a power of two) the density is halved, at most 32 times.  std::invalid_argument for a max_size that is no

@@ -681,6 +681,62 @@ std::tuple<Tensor, Tensor, Tensor> MeshRaycast(const Tensor& verts, const Tensor
   return {t, face, bary};
 }
 
+std::tuple<Tensor, Tensor, Tensor> MeshClosestPoint(const Tensor& verts, const Tensor& faces, const MeshRaycastAccel* accel, const Tensor& points,
+                                                    float max_dist) {
+  torch::NoGradGuard g;
+  Tensor v = Points3(verts), p = Points3(points);
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  const int64_t nv = v.size(0), nf = f.size(0), N = p.size(0);
+  TORCH_CHECK(nf <= INT32_MAX && N <= INT32_MAX, "mesh or point set too large");
+  if (!(max_dist >= 0.f)) throw std::invalid_argument("mesh_closest_point: max_dist must be >= 0 (inf: no cut-off)");
+  const float inf = std::numeric_limits<float>::infinity();
+  Tensor dist = torch::full({N}, inf, DevF32()), face = torch::full({N}, -1, DevI32()), bary = torch::zeros({N, 3}, DevF32());
+  if (accel != nullptr) {
+    TORCH_CHECK(accel->cell_start.defined() && accel->cell_faces.defined(), "mesh_closest_point: the accel has no cell lists");
+    const int64_t nc = (int64_t) accel->dims[0] * accel->dims[1] * accel->dims[2];
+    if (accel->cell_start.numel() != nc + 1) throw std::invalid_argument("mesh_closest_point: cell_start does not match dims");
+    // the walk's domain (include/f2n_abi.h): every coordinate of the box and of the finite points within 2^15 cells of the frame's origin
+    float far = 0.f;
+    for (int k = 0; k < 3; k++)
+      far = std::max(far, std::max(std::fabs(accel->lo[k]), std::fabs(accel->lo[k] + (float) accel->dims[k] * accel->cell)));
+    if (N > 0) far = std::max(far, torch::where(torch::isfinite(p), p.abs(), torch::zeros({1}, DevF32())).max().item<float>());
+    if (!(far <= 32768.f * accel->cell))
+      throw std::invalid_argument("mesh_closest_point: a point (or the grid) lies more than 2^15 cells from the frame's origin: outside the "
+                                  "domain in which the grid walk is exact; use a larger cell or accel=None");
+  }
+  Tensor cs = accel != nullptr ? DevArg(accel->cell_start, torch::kInt32, "cell_start") : Tensor();
+  Tensor cf = accel != nullptr ? DevArg(accel->cell_faces, torch::kInt32, "cell_faces") : Tensor();
+  F2N_TIMED_CALL(accel != nullptr ? "mesh_closest_point" : "mesh_closest_point_brute",
+                 f2n_mesh_closest_point(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), accel != nullptr ? accel->lo : nullptr,
+                                        accel != nullptr ? accel->cell : 0.f, accel != nullptr ? accel->dims : nullptr,
+                                        accel != nullptr ? I32P(cs) : nullptr, accel != nullptr && cf.numel() > 0 ? I32P(cf) : nullptr, (int) N,
+                                        F32P(p), max_dist, F32P(dist), I32P(face), F32P(bary)));
+  return {dist, face, bary};
+}
+
+std::tuple<Tensor, Tensor, Tensor> MeshSampleSurface(const Tensor& verts, const Tensor& faces, int64_t n, uint64_t seed) {
+  torch::NoGradGuard g;
+  Tensor v = Points3(verts);
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  const int64_t nv = v.size(0), nf = f.size(0);
+  TORCH_CHECK(nf <= INT32_MAX, "mesh too large");
+  if (n < 0 || n > INT32_MAX) throw std::invalid_argument("mesh_sample_surface: n must lie in [0, 2^31)");
+  const auto f64 = DevF32().dtype(torch::kFloat64), i64 = DevI32().dtype(torch::kInt64);
+  Tensor area2 = torch::zeros({nf}, f64), weights = torch::zeros({nf}, i64);
+  if (nf > 0)
+    F2N_TIMED_CALL("mesh_face_weights", f2n_mesh_face_weights(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), 0.0, area2.data_ptr<double>(),
+                                                              nullptr));
+  const double largest = nf > 0 ? area2.max().item<double>() : 0.0;
+  if (!(largest > 0.0)) throw std::invalid_argument("mesh_sample_surface: the mesh has no face with an area");
+  F2N_TIMED_CALL("mesh_face_weights", f2n_mesh_face_weights(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), largest * 0x1p-31, nullptr,
+                                                            weights.data_ptr<int64_t>()));
+  Tensor cum = weights.cumsum(0).contiguous();
+  Tensor pts = torch::empty({n, 3}, DevF32()), face = torch::empty({n}, DevI32()), bary = torch::empty({n, 3}, DevF32());
+  F2N_TIMED_CALL("mesh_sample_surface", f2n_mesh_sample_surface(CurStream(), (int) nv, (int) nf, F32P(v), I32P(f), cum.data_ptr<int64_t>(), (int) n,
+                                                                seed ^ kMeshSamplePurpose, F32P(pts), I32P(face), F32P(bary)));
+  return {pts, face, bary};
+}
+
 MeshAtlasResult MeshAtlas(const Tensor& verts, const Tensor& faces, float density, int max_size, int max_log) {
   torch::NoGradGuard g;
   Tensor v = Points3(verts);

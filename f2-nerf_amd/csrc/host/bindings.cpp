@@ -206,6 +206,39 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::vector<Tensor>{std::get<0>(r), std::get<1>(r), std::get<2>(r)};
         },
         py::arg("verts"), py::arg("faces"), py::arg("accel"), py::arg("rays_o"), py::arg("rays_d"), py::arg("bounds") = py::none());
+  // the points' closest point on the mesh: [dist (+inf: none within max_dist), face (-1: none), bary]; accel = mesh_raycast_build's
+  // tuple, or None for the brute-force mode.  ValueError for a finite point outside the walk's domain (more than 2^15 cells from the
+  // frame's origin)
+  m.def("mesh_closest_point",
+        [](const Tensor& verts, const Tensor& faces, const py::object& accel, const Tensor& points, float max_dist) {
+          MeshRaycastAccel a;
+          const bool have = !accel.is_none();
+          if (have) {
+            py::tuple t = accel.cast<py::tuple>();
+            if (t.size() != 5) throw std::invalid_argument("accel must be mesh_raycast_build's (lo, cell, dims, cell_start, cell_faces)");
+            const auto lo = t[0].cast<std::vector<float>>();
+            const auto dims = t[2].cast<std::vector<int>>();
+            if (lo.size() != 3 || dims.size() != 3) throw std::invalid_argument("accel: lo and dims must have three entries");
+            for (int k = 0; k < 3; k++) {
+              a.lo[k] = lo[k];
+              a.dims[k] = dims[k];
+            }
+            a.cell = t[1].cast<float>();
+            a.cell_start = t[3].cast<Tensor>();
+            a.cell_faces = t[4].cast<Tensor>();
+          }
+          auto r = MeshClosestPoint(verts, faces, have ? &a : nullptr, points, max_dist);
+          return std::vector<Tensor>{std::get<0>(r), std::get<1>(r), std::get<2>(r)};
+        },
+        py::arg("verts"), py::arg("faces"), py::arg("accel"), py::arg("points"),
+        py::arg("max_dist") = std::numeric_limits<float>::infinity());
+  // n area-uniform, stratified samples of the mesh's surface, a pure function of (mesh, n, seed): [points, face, bary]
+  m.def("mesh_sample_surface",
+        [](const Tensor& verts, const Tensor& faces, int64_t n, uint64_t seed) {
+          auto r = MeshSampleSurface(verts, faces, n, seed);
+          return std::vector<Tensor>{std::get<0>(r), std::get<1>(r), std::get<2>(r)};
+        },
+        py::arg("verts"), py::arg("faces"), py::arg("n"), py::arg("seed") = 0);
   // the texture atlas of a mesh: (uv [F,3,2], size, blocks, density_used); blocks = dict of the device tensors mesh_atlas_texels needs
   // (offsets [B+1] int64, block_log, block_faces, log_s, rot, slot).  ValueError: max_size no power of two, or the mesh cannot fit
   m.def("mesh_atlas",

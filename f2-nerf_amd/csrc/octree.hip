@@ -1621,6 +1621,312 @@ int f2n_mesh_raycast(void* stream, int n_verts, int n_faces, const float* verts,
 }
 
 // =====================================================================================================================
+// Mesh-to-mesh distance (include/f2n_abi.h, "Closest point on a triangle mesh" and "Area-uniform surface samples"): the
+// fp64 region walk of Ericson 5.1.5 over the ray caster's face grid, and stratified Philox samples of the surface.
+//   brute: every point tests every face; a block stages 256 faces at a time in LDS (the device-side oracle)
+//   grid:  one lane per point walks Chebyshev shells of cells around the point's own cell until the shell's planes are
+//          farther than the face it holds
+// One lane owns one point / face / sample: no atomics.  The region walk keeps its barycentrics in named scalars.
+// =====================================================================================================================
+namespace {
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define F2N_DSQRT_RN(x) __dsqrt_rn(x)
+#else
+#define F2N_DSQRT_RN(x) sqrt(x)
+#endif
+
+struct ClosestHit {
+  double d2, b0, b1, b2;
+  int face;
+};
+
+__device__ __forceinline__ double dot3d(double ax, double ay, double az, double bx, double by, double bz) {
+  return (ax * bx + ay * by) + az * bz;
+}
+
+// the contract for one (point, face) pair: A, B, C are the face's vertices; keeps the nearer face, the lower index among equals
+__device__ __forceinline__ void closest_face(double px, double py, double pz, int face, float a0, float a1, float a2, float b0, float b1,
+                                             float b2, float c0, float c1, float c2, ClosestHit* h) {
+  const double ax = a0, ay = a1, az = a2, bx = b0, by = b1, bz = b2, cx = c0, cy = c1, cz = c2;
+  const double abx = bx - ax, aby = by - ay, abz = bz - az, acx = cx - ax, acy = cy - ay, acz = cz - az;
+  const double d1 = dot3d(abx, aby, abz, px - ax, py - ay, pz - az), d2 = dot3d(acx, acy, acz, px - ax, py - ay, pz - az);
+  const double d3 = dot3d(abx, aby, abz, px - bx, py - by, pz - bz), d4 = dot3d(acx, acy, acz, px - bx, py - by, pz - bz);
+  const double d5 = dot3d(abx, aby, abz, px - cx, py - cy, pz - cz), d6 = dot3d(acx, acy, acz, px - cx, py - cy, pz - cz);
+  double u, v, w;  // the weights of A, B, C
+  if (d1 <= 0.0 && d2 <= 0.0) {
+    u = 1.0; v = 0.0; w = 0.0;  // vertex A
+  } else if (d3 >= 0.0 && d4 <= d3) {
+    u = 0.0; v = 1.0; w = 0.0;  // vertex B
+  } else if (d6 >= 0.0 && d5 <= d6) {
+    u = 0.0; v = 0.0; w = 1.0;  // vertex C
+  } else {
+    const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const double g = d4 - d3, k = d5 - d6;
+    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {  // edge AB
+      v = d1 / (d1 - d3); u = 1.0 - v; w = 0.0;
+    } else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {  // edge AC
+      w = d2 / (d2 - d6); u = 1.0 - w; v = 0.0;
+    } else if (va <= 0.0 && g >= 0.0 && k >= 0.0) {  // edge BC
+      w = g / (g + k); v = 1.0 - w; u = 0.0;
+    } else {  // the interior (and every NaN: no comparison above holds)
+      const double s = (va + vb) + vc;
+      v = vb / s; w = vc / s; u = (1.0 - v) - w;
+    }
+  }
+  const double ex = px - ((u * ax + v * bx) + w * cx), ey = py - ((u * ay + v * by) + w * cy), ez = pz - ((u * az + v * bz) + w * cz);
+  const double dd = (ex * ex + ey * ey) + ez * ez;
+  if (dd < h->d2 || (dd == h->d2 && face < h->face)) {  // (false for a NaN; +inf never wins: no face is held at index -1)
+    h->d2 = dd; h->b0 = u; h->b1 = v; h->b2 = w; h->face = face;
+  }
+}
+
+__device__ __forceinline__ void closest_store(const ClosestHit& h, float max_dist, int64_t i, float* __restrict__ out_dist,
+                                              int32_t* __restrict__ out_face, float* __restrict__ out_bary) {
+  const float dist = (float) F2N_DSQRT_RN(h.d2);
+  const bool hit = h.face >= 0 && !(dist > max_dist);
+  out_dist[i] = hit ? dist : __builtin_huge_valf();
+  out_face[i] = hit ? h.face : -1;
+  out_bary[i * 3] = hit ? (float) h.b0 : 0.f;
+  out_bary[i * 3 + 1] = hit ? (float) h.b1 : 0.f;
+  out_bary[i * 3 + 2] = hit ? (float) h.b2 : 0.f;
+}
+
+// flag_index: a face names a vertex that is not there; flag_box: a finite vertex lies outside the grid box dilated by the guard
+__global__ void __launch_bounds__(256) closest_check_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                            const int32_t* __restrict__ faces, int with_grid, ClusterGrid g,
+                                                            int32_t* flag_index, int32_t* flag_box) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  int a, b, c;
+  if (i < n_faces && !face_in_range(faces, i, n_verts, &a, &b, &c)) *flag_index = 1;  // (benign race: every writer stores 1)
+  if (with_grid && i < n_verts && finite3(verts + i * 3)) {
+    const float guard = ray_guard(g.cell);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const float x = verts[i * 3 + k], hi = F2N_ADD_RN(g.lo[k], F2N_MUL_RN((float) g.dims[k], g.cell));
+      if (!(x >= F2N_SUB_RN(g.lo[k], guard) && x <= F2N_ADD_RN(hi, guard))) *flag_box = 1;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(F2N_RAYCAST_TILE) closest_brute_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                                        const int32_t* __restrict__ faces, int n_points,
+                                                                        const float* __restrict__ points, float max_dist,
+                                                                        float* __restrict__ out_dist, int32_t* __restrict__ out_face,
+                                                                        float* __restrict__ out_bary) {
+  __shared__ float tile[9][F2N_RAYCAST_TILE];
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = i < n_points;
+  const float p0 = points[(live ? i : 0) * 3], p1 = points[(live ? i : 0) * 3 + 1], p2 = points[(live ? i : 0) * 3 + 2];
+  const float inf = __builtin_huge_valf();
+  const bool ok = live && fabsf(p0) < inf && fabsf(p1) < inf && fabsf(p2) < inf;
+  ClosestHit h = {__builtin_huge_val(), 0.0, 0.0, 0.0, -1};
+  for (int base = 0; base < n_faces; base += F2N_RAYCAST_TILE) {
+    const int mine = base + (int) threadIdx.x;
+    int a, b, c;
+    const bool there = mine < n_faces && face_in_range(faces, mine, n_verts, &a, &b, &c);
+    const float nan = __builtin_nanf("");  // (a face that is not there never wins)
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      tile[k][threadIdx.x] = there ? verts[(int64_t) a * 3 + k] : nan;
+      tile[3 + k][threadIdx.x] = there ? verts[(int64_t) b * 3 + k] : nan;
+      tile[6 + k][threadIdx.x] = there ? verts[(int64_t) c * 3 + k] : nan;
+    }
+    __syncthreads();
+    const int n = min(F2N_RAYCAST_TILE, n_faces - base);
+    if (ok)
+      for (int j = 0; j < n; j++)
+        closest_face((double) p0, (double) p1, (double) p2, base + j, tile[0][j], tile[1][j], tile[2][j], tile[3][j], tile[4][j], tile[5][j],
+                     tile[6][j], tile[7][j], tile[8][j], &h);
+    __syncthreads();
+  }
+  if (live) closest_store(h, max_dist, i, out_dist, out_face, out_bary);
+}
+
+// every face of cell c's list against the point
+__device__ __forceinline__ void closest_cell(double px, double py, double pz, int c, int n_verts, int n_faces, const float* __restrict__ verts,
+                                             const int32_t* __restrict__ faces, const int32_t* __restrict__ cell_start,
+                                             const int32_t* __restrict__ cell_faces, ClosestHit* h) {
+  const int e1 = cell_start[c + 1];
+  for (int e = cell_start[c]; e < e1; e++) {
+    const int f = cell_faces[e];
+    int a, b, cc;
+    if (f < 0 || f >= n_faces || !face_in_range(faces, f, n_verts, &a, &b, &cc)) continue;
+    const float* pa = verts + (int64_t) a * 3;
+    const float* pb = verts + (int64_t) b * 3;
+    const float* pc = verts + (int64_t) cc * 3;
+    closest_face(px, py, pz, f, pa[0], pa[1], pa[2], pb[0], pb[1], pb[2], pc[0], pc[1], pc[2], h);
+  }
+}
+
+__global__ void __launch_bounds__(256) closest_grid_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                           const int32_t* __restrict__ faces, ClusterGrid g,
+                                                           const int32_t* __restrict__ cell_start, const int32_t* __restrict__ cell_faces,
+                                                           int n_points, const float* __restrict__ points, float max_dist,
+                                                           float* __restrict__ out_dist, int32_t* __restrict__ out_face,
+                                                           float* __restrict__ out_bary) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_points) return;
+  const float p0 = points[i * 3], p1 = points[i * 3 + 1], p2 = points[i * 3 + 2];
+  const float inf = __builtin_huge_valf();
+  ClosestHit h = {__builtin_huge_val(), 0.0, 0.0, 0.0, -1};
+  if (fabsf(p0) < inf && fabsf(p1) < inf && fabsf(p2) < inf) {
+    const int nx = g.dims[0], ny = g.dims[1], nz = g.dims[2];
+    const int cx = ray_cell(g.lo[0], g.cell, nx, p0), cy = ray_cell(g.lo[1], g.cell, ny, p1), cz = ray_cell(g.lo[2], g.cell, nz, p2);
+    const double px = p0, py = p1, pz = p2;
+    for (int r = 0;; r++) {
+      const int x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1), y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1);
+      const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1);
+      for (int z = z0; z <= z1; z++)
+        for (int y = y0; y <= y1; y++) {
+          const int row = (z * ny + y) * nx;
+          if (z == cz - r || z == cz + r || y == cy - r || y == cy + r) {  // a face of the shell: the whole row
+            for (int x = x0; x <= x1; x++) closest_cell(px, py, pz, row + x, n_verts, n_faces, verts, faces, cell_start, cell_faces, &h);
+          } else {  // (r >= 1 here) the row's two ends, where they are inside the grid
+            if (cx - r >= 0) closest_cell(px, py, pz, row + cx - r, n_verts, n_faces, verts, faces, cell_start, cell_faces, &h);
+            if (cx + r <= nx - 1) closest_cell(px, py, pz, row + cx + r, n_verts, n_faces, verts, faces, cell_start, cell_faces, &h);
+          }
+        }
+      // the nearest open side of the box: no face beyond it is listed inside
+      float lb = inf;
+      bool open = false;
+#define F2N_CLOSEST_SIDE(C, N, LO, P)                                                                          \
+  if (C - r > 0) {                                                                                             \
+    open = true;                                                                                               \
+    lb = fminf(lb, F2N_SUB_RN(P, F2N_ADD_RN(LO, F2N_MUL_RN((float) (C - r), g.cell))));                          \
+  }                                                                                                            \
+  if (C + r < N - 1) {                                                                                         \
+    open = true;                                                                                               \
+    lb = fminf(lb, F2N_SUB_RN(F2N_ADD_RN(LO, F2N_MUL_RN((float) (C + r + 1), g.cell)), P));                      \
+  }
+      F2N_CLOSEST_SIDE(cx, nx, g.lo[0], p0)
+      F2N_CLOSEST_SIDE(cy, ny, g.lo[1], p1)
+      F2N_CLOSEST_SIDE(cz, nz, g.lo[2], p2)
+#undef F2N_CLOSEST_SIDE
+      if (!open) break;  // every cell has been tested
+      if ((h.face >= 0 && (float) F2N_DSQRT_RN(h.d2) < lb) || lb > max_dist) break;
+    }
+  }
+  closest_store(h, max_dist, i, out_dist, out_face, out_bary);
+}
+
+// |(B - A) x (C - A)| in fp64; 0 for a face that names a vertex that is not there or is not finite
+__global__ void __launch_bounds__(256) face_weights_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                           const int32_t* __restrict__ faces, double quantum, double* __restrict__ area2,
+                                                           long long* __restrict__ weights) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  int a, b, c;
+  double area = 0.0;
+  if (face_in_range(faces, f, n_verts, &a, &b, &c)) {
+    const float* pa = verts + (int64_t) a * 3;
+    const float* pb = verts + (int64_t) b * 3;
+    const float* pc = verts + (int64_t) c * 3;
+    if (finite3(pa) && finite3(pb) && finite3(pc)) {
+      const double px = (double) pb[0] - (double) pa[0], py = (double) pb[1] - (double) pa[1], pz = (double) pb[2] - (double) pa[2];
+      const double qx = (double) pc[0] - (double) pa[0], qy = (double) pc[1] - (double) pa[1], qz = (double) pc[2] - (double) pa[2];
+      const double nx = py * qz - pz * qy, ny = pz * qx - px * qz, nz = px * qy - py * qx;
+      area = F2N_DSQRT_RN((nx * nx + ny * ny) + nz * nz);
+    }
+  }
+  if (area2 != nullptr) area2[f] = area;
+  if (weights != nullptr) weights[f] = (long long) floor(area / quantum);
+}
+
+__global__ void __launch_bounds__(256) sample_surface_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                             const int32_t* __restrict__ faces, const long long* __restrict__ cum,
+                                                             int n_samples, uint32_t key_lo, uint32_t key_hi, float* __restrict__ out_points,
+                                                             int32_t* __restrict__ out_face, float* __restrict__ out_bary) {
+  const int64_t j = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_samples) return;
+  uint32_t x[4];
+  f2n_philox4x32((uint32_t) j, 0u, 0u, 0u, key_lo, key_hi, x);
+  const double two32 = 1.0 / 4294967296.0;
+  const long long T = cum[n_faces - 1];
+  const double at = ((double) j + ((double) x[0] + 0.5) * two32) / (double) n_samples * (double) T;
+  long long target = (long long) floor(at);
+  if (target > T - 1) target = T - 1;
+  int lo = 0, hi = n_faces - 1;  // the first face with cum > target (cum[F - 1] = T > target: there is one)
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if (cum[mid] > target) hi = mid; else lo = mid + 1;
+  }
+  const double s = F2N_DSQRT_RN(((double) x[1] + 0.5) * two32), r = ((double) x[2] + 0.5) * two32;
+  const float b0 = (float) (1.0 - s), b1 = (float) (s * (1.0 - r)), b2 = (float) (s * r);
+  int a, b, c;
+  const bool ok = face_in_range(faces, lo, n_verts, &a, &b, &c);  // (a face with a weight is in range: its area is not 0)
+  out_face[j] = lo;
+  out_bary[j * 3] = b0; out_bary[j * 3 + 1] = b1; out_bary[j * 3 + 2] = b2;
+#pragma unroll
+  for (int k = 0; k < 3; k++)
+    out_points[j * 3 + k] = ok ? F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(b0, verts[(int64_t) a * 3 + k]), F2N_MUL_RN(b1, verts[(int64_t) b * 3 + k])),
+                                            F2N_MUL_RN(b2, verts[(int64_t) c * 3 + k]))
+                               : 0.f;
+}
+
+}  // namespace
+
+int f2n_mesh_closest_point(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, const float* lo, float cell,
+                           const int32_t* dims, const int32_t* cell_start, const int32_t* cell_faces, int n_points, const float* points,
+                           float max_dist, float* out_dist, int32_t* out_face, float* out_bary) {
+  ClusterGrid g = {};
+  if (n_verts < 0 || n_faces < 0 || n_points < 0 || !(max_dist >= 0.f) || (cell_start != nullptr && !raycast_grid_ok(lo, cell, dims, &g)) ||
+      (n_faces > 0 && (n_verts == 0 || verts == nullptr || faces == nullptr)) ||
+      (n_points > 0 && (points == nullptr || out_dist == nullptr || out_face == nullptr || out_bary == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (cell_start != nullptr)  // the part of the walk's domain that is host data: the box within 2^15 cells of the origin of the frame
+    for (int k = 0; k < 3; k++)
+      if (!(fmaxf(fabsf(lo[k]), fabsf(lo[k] + (float) dims[k] * cell)) <= F2N_RAYCAST_DOMAIN_CELLS * cell)) return F2N_ERR_UNSUPPORTED;
+  if (n_points == 0) return F2N_OK;
+  hipStream_t st = (hipStream_t) stream;
+  const bool with_grid = cell_start != nullptr && n_faces > 0;
+  if (n_faces > 0) {  // the index check and the vertices' part of the domain, with out_face[0] and out_dist[0] as their flag words
+    int32_t* flag_box = (int32_t*) out_dist;
+    if (hipMemsetAsync(out_face, 0, sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(flag_box, 0, sizeof(int32_t), st) != hipSuccess)
+      return f2n_launch_status();
+    hipLaunchKernelGGL(closest_check_kernel, dim3(f2n_div_up(n_faces > n_verts ? n_faces : n_verts, 256)), dim3(256), 0, st, n_verts, n_faces,
+                       verts, faces, with_grid ? 1 : 0, g, out_face, flag_box);
+    int32_t bad = 0, outside = 0;
+    if (hipMemcpyAsync(&bad, out_face, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&outside, flag_box, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return f2n_launch_status();
+    if (bad != 0) return F2N_ERR_INVALID_ARG;
+    if (outside != 0) return F2N_ERR_UNSUPPORTED;
+  }
+  const dim3 grid(f2n_div_up(n_points, 256)), block(256);
+  if (!with_grid)
+    hipLaunchKernelGGL(closest_brute_kernel, grid, block, 0, st, n_verts, n_faces, verts, faces, n_points, points, max_dist, out_dist, out_face,
+                       out_bary);
+  else  // (cell_faces may be NULL when every list is empty: it is then never read)
+    hipLaunchKernelGGL(closest_grid_kernel, grid, block, 0, st, n_verts, n_faces, verts, faces, g, cell_start, cell_faces, n_points, points,
+                       max_dist, out_dist, out_face, out_bary);
+  return f2n_launch_status();
+}
+
+int f2n_mesh_face_weights(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, double quantum, double* area2,
+                          int64_t* weights) {
+  if (n_verts < 0 || n_faces < 0 || (weights != nullptr && (!(quantum > 0.0) || !(quantum < __builtin_huge_val()))) ||
+      (n_faces > 0 && (faces == nullptr || (n_verts > 0 && verts == nullptr) || (area2 == nullptr && weights == nullptr))))
+    return F2N_ERR_INVALID_ARG;
+  if (n_faces == 0) return F2N_OK;
+  hipLaunchKernelGGL(face_weights_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, (hipStream_t) stream, n_verts, n_faces, verts, faces,
+                     quantum, area2, (long long*) weights);
+  return f2n_launch_status();
+}
+
+int f2n_mesh_sample_surface(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, const int64_t* cum,
+                            int n_samples, uint64_t key, float* out_points, int32_t* out_face, float* out_bary) {
+  if (n_verts < 0 || n_faces < 0 || n_samples < 0 ||
+      (n_samples > 0 && (n_faces == 0 || n_verts == 0 || verts == nullptr || faces == nullptr || cum == nullptr || out_points == nullptr ||
+                         out_face == nullptr || out_bary == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n_samples == 0) return F2N_OK;
+  hipLaunchKernelGGL(sample_surface_kernel, dim3(f2n_div_up(n_samples, 256)), dim3(256), 0, (hipStream_t) stream, n_verts, n_faces, verts,
+                     faces, (const long long*) cum, n_samples, (uint32_t) key, (uint32_t) (key >> 32), out_points, out_face, out_bary);
+  return f2n_launch_status();
+}
+
+// =====================================================================================================================
 // Texture atlas (include/f2n_abi.h, "Texture atlas of a triangle mesh"): one right-triangle chart per face in power-of-two
 // blocks placed by the Morton decode of a prefix sum, the texel-to-surface map and a bilinear lookup.  One lane owns one
 // face / texel / output value: no atomics, so every output is a function of the inputs alone.  The corner rotation is

@@ -36,6 +36,18 @@ Options (hydra-style overrides, no `mesh` group in the configs):
                    Known limits: no mip-safe padding between blocks (nearest and bilinear filtering are clean, mipmaps bleed); charts
                    are per face, so filtering is not seam-free across edges beyond the replicated gutter; a chart's anisotropy is
                    bounded only by putting the longest edge on the diagonal.  Default false: nothing changes
+  mesh.distance    true (needs mesh.simplify=k >= 2): the simplified mesh just written is compared with the unsimplified one (the same
+                   floater filter, extracted once more without the simplification) by mesh_distance: sampled surface-to-surface
+                   distances in both directions (host.mesh_sample_surface, host.mesh_closest_point) -> <same name>_distance.json
+                   (a_to_b: from this mesh to the other, b_to_a: back; chamfer, a sampled hausdorff, precision / recall / F-score per
+                   threshold, all in grid steps) and one printed line.  It works with either mesh.source.  Default false: nothing changes
+  mesh.distance_to  <file.ply>: the mesh just written is compared with that triangle mesh instead (read_ply), both in the data set's
+                   WORLD frame -- another export of the same scene (the TSDF mesh against the density mesh) or a scan a user brings.
+                   It excludes mesh.distance=true (one JSON per mesh).  mesh.distance=true compares in the world frame too, on the
+                   float32 vertices a .ply carries, so mesh.distance_to=<the same run's unsimplified .ply> gives its figures.  Options of both: distance.samples (200 000 per side),
+                   distance.seed (0), distance.thresholds ([0.5, 1, 2] grid steps), distance.max_dist_steps (none: samples farther than
+                   this many grid steps from the other mesh are counted as missed and left out of the statistics).  The sample
+                   count and the thresholds are choices, not measurements
   mesh.source      density | tsdf (default density): the iso-surface of the raw density at mesh.level, or the zero crossing of a
                    truncated signed distance field fused from the training views' rendered depth (fuse_tsdf; mesh.level is not
                    used, normals of source "grid" come from the TSDF) -> <exp>/meshes/<iter>_<res>_tsdf.ply
@@ -331,11 +343,13 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
     host = runtime.host()
     o = options(cfg)
     o.update(tsdf_options(cfg))
+    dist = distance_options(cfg)
     t = fuse_tsdf(runner, dataset, scene, o)
     verts, faces = host.mesh_from_grid_masked(t["g"], t["valid"], t["lo"], t["step"], 0.0)
     if o["min_component_faces"] > 1:
         verts, faces, _ = host.mesh_filter_components(verts, faces, o["min_component_faces"])
     k, faces_in = o["simplify"], len(faces)
+    full_verts, full_faces = verts, faces  # (mesh.distance compares with the mesh before the simplification)
     if k >= 2:  # (cell = k * step as ONE float32 product: what extract_mesh_attrs uses)
         verts, faces, _ = host.mesh_simplify(verts, faces, float(np.float32(k) * np.float32(t["step"])), t["lo"])
     normals = colors = None
@@ -362,6 +376,8 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
     tex = _run_texture(runner, cfg, scene, verts, faces, nrm, t["step"], path) if tex_on else None
     if check_options(cfg)["check"]:
         _run_check(runner, cfg, scene, dataset, verts, faces, t["step"], path, tex)
+    if dist["distance"] or dist["distance_to"] is not None:
+        _distance_in_world(cfg, scene, verts, faces, t["step"], path, (full_verts, full_faces) if dist["distance"] else None)
     return path
 
 
@@ -653,6 +669,200 @@ def _run_texture(runner, cfg, scene, verts, faces, normals, step, path):
     return r
 
 
+def read_ply(path):
+    """(verts [V,3] float32, faces [F,3] int32) of a triangle-mesh PLY: what write_ply writes (further vertex properties are skipped), and
+    ASCII / binary_little_endian files with float x, y, z and a face list `vertex_indices` or `vertex_index` of three entries each.
+    ValueError for anything else: another format, further elements, a face that is no triangle, a truncated file."""
+    scalar = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",
+              "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError("read_ply: %s is not a PLY file" % path)
+    body = data[end + len(b"end_header\n"):]
+    fmt, elements = None, []
+    for ln in data[:end].decode("ascii", "replace").replace("\r", "").split("\n")[1:]:
+        w = ln.split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "format" and len(w) == 3:
+            fmt = w[1]
+        elif w[0] == "element" and len(w) == 3:
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == "property" and elements and len(w) in (3, 5):
+            elements[-1][2].append(w[1:])
+        else:
+            raise ValueError("read_ply: header line %r" % ln)
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError("read_ply: format %r (ascii and binary_little_endian are read)" % fmt)
+    if [e[0] for e in elements] not in (["vertex", "face"], ["vertex"]):
+        raise ValueError("read_ply: elements %r (a vertex element, then a face element)" % [e[0] for e in elements])
+    nv, vprops = elements[0][1], elements[0][2]
+    if any(len(p) != 2 or p[0] not in scalar for p in vprops):
+        raise ValueError("read_ply: a vertex property is a list or of an unknown type")
+    names = [p[1] for p in vprops]
+    if any(names.count(k) != 1 or scalar[vprops[names.index(k)][0]] != "<f4" for k in ("x", "y", "z")):
+        raise ValueError("read_ply: the vertex element needs float x, y and z")
+    nf, fprops = (elements[1][1], elements[1][2]) if len(elements) > 1 else (0, [])
+    if nf or fprops:
+        if (len(fprops) != 1 or len(fprops[0]) != 4 or fprops[0][0] != "list" or fprops[0][3] not in ("vertex_indices", "vertex_index") or
+                scalar.get(fprops[0][1], "<f4")[-2] not in "iu" or scalar.get(fprops[0][2], "<f4")[-2] not in "iu"):
+            raise ValueError("read_ply: the face element must be one integer list vertex_indices / vertex_index")
+    if fmt == "ascii":
+        tok = body.split()
+        need = nv * len(vprops)
+        if len(tok) != need + 4 * nf:
+            raise ValueError("read_ply: %d values for %d vertices and %d triangles (a face that is no triangle?)" % (len(tok), nv, nf))
+        try:
+            vt = np.array(tok[:need], dtype=np.float64).reshape(nv, len(vprops))
+            ft = np.array(tok[need:], dtype=np.int64).reshape(nf, 4)
+        except ValueError:
+            raise ValueError("read_ply: a value of the body is not a number")
+        verts = np.stack([vt[:, names.index(k)] for k in ("x", "y", "z")], 1).astype(np.float32)
+        count, idx = ft[:, 0], ft[:, 1:]
+    else:
+        vdt = np.dtype([(p[1], scalar[p[0]]) for p in vprops])
+        fdt = np.dtype([("n", scalar[fprops[0][1]]), ("idx", scalar[fprops[0][2]], (3,))]) if nf else np.dtype([("n", "u1"), ("idx", "<i4", (3,))])
+        if len(body) != nv * vdt.itemsize + nf * fdt.itemsize:
+            raise ValueError("read_ply: the body holds %d bytes, %d vertices and %d triangles need %d (a face that is no triangle?)" % (
+                len(body), nv, nf, nv * vdt.itemsize + nf * fdt.itemsize))
+        vrec = np.frombuffer(body, vdt, nv)
+        frec = np.frombuffer(body, fdt, nf, nv * vdt.itemsize)
+        verts = np.stack([vrec[k] for k in ("x", "y", "z")], 1).astype(np.float32)
+        count, idx = frec["n"].astype(np.int64), frec["idx"].astype(np.int64)
+    if (count != 3).any():
+        raise ValueError("read_ply: a face that is no triangle")
+    if nf and (idx.min() < 0 or idx.max() >= max(nv, 1) or idx.max() > 2 ** 31 - 1):
+        raise ValueError("read_ply: a face names a vertex that is not there")
+    return np.ascontiguousarray(verts, np.float32).reshape(-1, 3), np.ascontiguousarray(idx, np.int32).reshape(-1, 3)
+
+
+def distance_options(cfg):
+    """mesh.distance, mesh.distance_to and the distance.* options.  200 000 samples per side and thresholds of 0.5, 1 and 2 grid steps are
+    choices, not measurements.  mesh.distance=true needs something to compare with: mesh.simplify >= 2 (the unsimplified mesh); a
+    mesh.distance_to=<file.ply> compares with that file instead, and the two exclude each other (one JSON per mesh)."""
+    m = cfg.get("mesh") or {}
+    d = cfg.get("distance") or {}
+    to = m.get("distance_to", None)
+    to = None if to is None or str(to).strip() == "" else str(to)
+    th = d.get("thresholds", [0.5, 1.0, 2.0])
+    if isinstance(th, str):
+        th = [x for x in th.strip("[]() ").split(",") if x.strip()]
+    elif not isinstance(th, (list, tuple)) and not hasattr(th, "__iter__"):
+        th = [th]
+    md = d.get("max_dist_steps", None)
+    o = {"distance": _flag(m.get("distance", False)), "distance_to": to, "samples": int(d.get("samples", 200000)), "seed": int(d.get("seed", 0)),
+         "thresholds": [float(x) for x in th], "max_dist_steps": None if md is None else float(md)}
+    if (o["samples"] < 1 or o["samples"] >= 2 ** 31 or o["seed"] < 0 or not o["thresholds"] or
+            any(not 0.0 < t < float("inf") for t in o["thresholds"]) or (o["max_dist_steps"] is not None and not o["max_dist_steps"] > 0.0)):
+        raise ValueError("distance.samples must lie in [1, 2^31), distance.seed be >= 0, distance.thresholds a list of positive finite "
+                         "numbers and distance.max_dist_steps > 0, got %r" % (o,))
+    if o["distance"] and o["distance_to"] is not None:
+        raise ValueError("mesh.distance=true (against the unsimplified mesh) and mesh.distance_to=<file> write the same JSON: choose one")
+    if o["distance"] and _simplify(m.get("simplify", 0)) < 2:
+        raise ValueError("mesh.distance=true compares the simplified mesh with the unsimplified one: it needs mesh.simplify >= 2 (or "
+                         "mesh.distance_to=<file.ply> instead)")
+    return o
+
+
+class _HostDistance:
+    """the device primitives of mesh_distance on torch tensors (runtime.host())"""
+    def __init__(self):
+        from . import runtime
+        self.host = runtime.host()
+
+    def _dev(self, verts, faces):
+        import torch
+        v = torch.as_tensor(np.asarray(verts, np.float32) if not torch.is_tensor(verts) else verts).to("cuda", torch.float32).reshape(-1, 3)
+        f = torch.as_tensor(np.asarray(faces, np.int32) if not torch.is_tensor(faces) else faces).to("cuda", torch.int32).reshape(-1, 3)
+        return v.contiguous(), f.contiguous()
+
+    def sample(self, verts, faces, n, seed):
+        return self.host.mesh_sample_surface(*self._dev(verts, faces), int(n), int(seed))[0]
+
+    def distances(self, verts, faces, points, max_dist):
+        v, f = self._dev(verts, faces)
+        accel = self.host.mesh_raycast_build(v, f)
+        return self.host.mesh_closest_point(v, f, accel, points, float(max_dist))[0].cpu().numpy()
+
+
+def _direction(dist, unit, thresholds):
+    """the statistics of one direction from its samples' distances [n] (+inf: missed), in units of `unit`; the quantile q is the element
+    min(m - 1, floor(q m)) of the m ascending distances that are not missed: a sort, no interpolation.  No sample within max_dist: zeros."""
+    d = np.asarray(dist, np.float32).reshape(-1)
+    got = np.isfinite(d)
+    e = np.sort(d[got].astype(np.float64) / float(unit))
+    m = len(e)
+    at = lambda q: float(e[min(m - 1, int(np.floor(q * m)))]) if m else 0.0  # noqa: E731
+    stats = {"n": int(len(d)), "missed": int(len(d) - m), "mean": float(e.mean()) if m else 0.0, "rms": float(np.sqrt((e * e).mean())) if m else 0.0,
+             "median": at(0.5), "p90": at(0.9), "p95": at(0.95), "max": float(e[-1]) if m else 0.0}
+    within = [float((e <= t).sum()) / len(d) if len(d) else 0.0 for t in thresholds]  # (a missed sample is within no threshold)
+    return stats, within
+
+
+def mesh_distance(verts_a, faces_a, verts_b, faces_b, n=200000, seed=0, thresholds=(0.5, 1.0, 2.0), unit=1.0, max_dist=None, backend=None):
+    """The distance between two triangle meshes in the same frame, sampled: n area-uniform, stratified points of each surface
+    (host.mesh_sample_surface, a pure function of (mesh, n, seed)) and the distance of each to the closest point of the OTHER mesh
+    (host.mesh_closest_point over host.mesh_raycast_build's grid).  Returns a dict of
+      a_to_b, b_to_a   n, missed (samples farther than max_dist: counted, left out of the statistics), and over the others mean, rms, median,
+                       p90, p95, max -- a_to_b is measured at the samples of A (how far A strays from B: accuracy when B is the
+                       truth), b_to_a at those of B (what of B is missing in A: completeness)
+      chamfer          the mean of the two means
+      hausdorff        the larger of the two maxima: a SAMPLED estimate, taken at the sample points only and therefore a lower bound of the
+                       true Hausdorff distance, which sits at one point of one surface and which no finite sample is sure to hit
+      thresholds, precision, recall, fscore   per threshold t: the share of A's samples within t of B, of B's within t of A, and their
+                       harmonic mean (0 where both are 0); a missed sample is within no threshold
+      unit, seed, n_faces_a, n_faces_b, max_dist
+    All lengths are divided by `unit` (the launcher passes the grid step, so that they read in grid steps); max_dist (None: no cut-off)
+    is in the meshes' own units.  n = 200 000 per side and thresholds of 0.5, 1 and 2 units are choices, not measurements.  Nothing
+    depends on the schedule: the same call gives the same dict.  backend: an object with sample(verts, faces, n, seed) -> points and
+    distances(verts, faces, points, max_dist) -> numpy [N] (the tests drive the emulated library through it); None: the device."""
+    if not (float(unit) > 0.0 and float(unit) < float("inf")) or int(n) < 1 or (max_dist is not None and not float(max_dist) >= 0.0):
+        raise ValueError("mesh_distance: unit must be positive and finite, n >= 1 and max_dist >= 0")
+    th = [float(t) for t in thresholds]
+    be = backend if backend is not None else _HostDistance()
+    md = float("inf") if max_dist is None else float(max_dist)
+    pa, pb = be.sample(verts_a, faces_a, n, seed), be.sample(verts_b, faces_b, n, seed)
+    ab, p = _direction(be.distances(verts_b, faces_b, pa, md), unit, th)
+    ba, r = _direction(be.distances(verts_a, faces_a, pb, md), unit, th)
+    return {"a_to_b": ab, "b_to_a": ba, "chamfer": 0.5 * (ab["mean"] + ba["mean"]), "hausdorff": max(ab["max"], ba["max"]), "thresholds": th,
+            "precision": p, "recall": r, "fscore": [2.0 * x * y / (x + y) if x + y > 0.0 else 0.0 for x, y in zip(p, r)],
+            "unit": float(unit), "seed": int(seed), "n_faces_a": int(np.shape(faces_a)[0]), "n_faces_b": int(np.shape(faces_b)[0]),
+            "max_dist": None if max_dist is None else float(max_dist)}
+
+
+def _run_distance(cfg, verts, faces, ref_verts, ref_faces, unit, against, path):
+    """mesh_distance(the mesh just written, the other mesh) -> <path without .ply>_distance.json and one printed line, lengths in grid
+    steps (`unit`: the grid step in the frame of the vertices)."""
+    import json
+    d = distance_options(cfg)
+    md = None if d["max_dist_steps"] is None else float(d["max_dist_steps"]) * float(unit)
+    res = mesh_distance(verts, faces, ref_verts, ref_faces, n=d["samples"], seed=d["seed"], thresholds=d["thresholds"], unit=unit, max_dist=md)
+    res["against"] = against
+    out = path[:-4] + "_distance.json"
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1, sort_keys=True)
+    print("Distance: to %s, chamfer %.4f, p95 %.4f / %.4f (this mesh to the other / back), hausdorff %.4f grid steps, F-score %s -> %s" % (
+        against, res["chamfer"], res["a_to_b"]["p95"], res["b_to_a"]["p95"], res["hausdorff"],
+        ", ".join("%.4f at %g" % (f, t) for f, t in zip(res["fscore"], res["thresholds"])), out))
+    return out
+
+
+def _distance_in_world(cfg, scene, verts, faces, step, path, full=None):
+    """mesh.distance / mesh.distance_to: the mesh just written (verts, faces: device tensors in the NORMALISED frame) against the
+    unsimplified one (full = (verts, faces) likewise) or against the file of mesh.distance_to.  Both comparisons are made in the data
+    set's WORLD frame, on the float32 vertices a .ply carries (a grid step there is step * radius): mesh.distance_to=<the same run's
+    unsimplified .ply> therefore reproduces the figures of mesh.distance=true."""
+    d = distance_options(cfg)
+    world = lambda x: to_world(x.cpu().numpy(), scene["center"], scene["radius"])  # noqa: E731
+    if full is not None:
+        rv, rf, against = world(full[0]), full[1].cpu().numpy(), "unsimplified"
+    else:
+        (rv, rf), against = read_ply(d["distance_to"]), d["distance_to"]
+    return _run_distance(cfg, world(verts), faces.cpu().numpy(), rv, rf, float(np.float32(step) * np.float32(scene["radius"])), against, path)
+
+
 def _simplified(k, faces_in):
     return " (simplified from %d faces, mesh.simplify=%d)" % (faces_in, k) if k >= 2 else ""
 
@@ -661,6 +871,7 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
     """Density grid -> iso-surface -> <exp_dir>/meshes/<iter>_<res>.ply, vertices in the data set's world frame (mesh.source=tsdf:
     extract_tsdf, which needs the data set)."""
     o = options(cfg)
+    dist = distance_options(cfg)
     if o["source"] == "tsdf":
         return extract_tsdf(runner, cfg, scene, dataset, exp_dir)
     k, faces_in = o["simplify"], 0
@@ -679,7 +890,7 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
                   m["colors"].cpu().numpy() if o["colors"] else None)
     print("Mesh: %d vertices, %d faces%s at level %g -> %s" % (len(v), len(faces), _simplified(k, faces_in), o["level"], path))
     tex = None
-    if texture_options(cfg)["texture"] or check_options(cfg)["check"]:
+    if texture_options(cfg)["texture"] or check_options(cfg)["check"] or dist["distance"] or dist["distance_to"] is not None:
         from . import runtime
         step = runtime.host().grid_spec([float(x) for x in o["bbox_min"]], [float(x) for x in o["bbox_max"]], int(o["resolution"]))[0]
     if texture_options(cfg)["texture"]:  # the normals are computed for the texture whether or not the .ply carries them
@@ -689,4 +900,10 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
         tex = _run_texture(runner, cfg, scene, verts, faces, m["normals"], step, path)
     if check_options(cfg)["check"]:
         _run_check(runner, cfg, scene, dataset, verts, faces, step, path, tex)
+    if dist["distance"]:  # the same floater filter, extracted once more without the simplification (as the texture path re-extracts)
+        full = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"], False, False,
+                                         o["normal_source"])
+        _distance_in_world(cfg, scene, verts, faces, step, path, (full["verts"], full["faces"]))
+    elif dist["distance_to"] is not None:
+        _distance_in_world(cfg, scene, verts, faces, step, path)
     return path

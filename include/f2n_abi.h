@@ -1146,6 +1146,80 @@ int f2n_mesh_raycast(void* stream, int n_verts, int n_faces, const float* verts 
                      const float* bounds /*[R,2] or NULL*/, float* out_t /*[R]*/, int32_t* out_face /*[R]*/, float* out_bary /*[R,3]*/);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Closest point on a triangle mesh (additive; the ABI version is unchanged): the region walk of Ericson, "Real-Time Collision
+ * Detection" 5.1.5, in fp64 over the ray caster's face grid.  No reference counterpart.  csrc/octree.hip; tests/mesh_distance_ref.py
+ * restates it in numpy.
+ * ------------------------------------------------------------------------------------------------- */
+/* For point p and face (a, b, c) with vertices A, B, C, all converted to fp64, every operation ONE fp64 rounding, never an FMA, a dot
+ * product being (x x' + y y') + z z':
+ *   1. ab = B - A, ac = C - A;  d1 = ab.(p - A), d2 = ac.(p - A);  d3 = ab.(p - B), d4 = ac.(p - B);  d5 = ab.(p - C), d6 = ac.(p - C).
+ *   2. the weights (u, v, w) of (A, B, C) by the FIRST of these tests that holds (a NaN fails every one of them):
+ *        vertex A: d1 <= 0 and d2 <= 0: (1, 0, 0);   vertex B: d3 >= 0 and d4 <= d3: (0, 1, 0);   vertex C: d6 >= 0 and d5 <= d6: (0, 0, 1);
+ *        with vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, g = d4 - d3, k = d5 - d6:
+ *        edge AB: vc <= 0, d1 >= 0, d3 <= 0: v = d1 / (d1 - d3), (1 - v, v, 0);
+ *        edge AC: vb <= 0, d2 >= 0, d6 <= 0: w = d2 / (d2 - d6), (1 - w, 0, w);
+ *        edge BC: va <= 0, g >= 0, k >= 0:   w = g / (g + k), (0, 1 - w, w);
+ *        interior: s = (va + vb) + vc, v = vb / s, w = vc / s, u = (1 - v) - w.
+ *   3. q = (u A + v B) + w C per coordinate;  e = p - q;  d2 = (e_x e_x + e_y e_y) + e_z e_z.
+ *   4. the point's result is its face of the smallest d2, of the lowest index among equal d2; a d2 that is NaN or +inf never wins (a
+ *      face with a vertex that is not finite, a degenerate face whose walk divides 0 by 0; a degenerate face whose walk stays finite
+ *      gives the true distance to one of its points and may win).  out_dist = (float) sqrt(d2) (fp64 sqrt, correctly rounded),
+ *      out_face, out_bary [N,3] = ((float) u, (float) v, (float) w).
+ *   5. nothing wins, out_dist > max_dist, or p has a coordinate that is not finite: face = -1, dist = +inf, bary = 0.
+ * The outputs of a point are a function of that point, max_dist and the face list alone: not of the grid, its cell size, the points'
+ * order or the schedule (no atomics: one lane owns one point).
+ *
+ * cell_start == NULL (lo, cell, dims, cell_faces are then not read) is the BRUTE-FORCE mode: every point tests every face (a block stages
+ * 256 faces at a time in LDS).  Otherwise (lo, cell, dims, cell_start, cell_faces) is the grid of f2n_mesh_raycast_count / _fill above and
+ * one lane per point walks Chebyshev shells around the point's own cell c_k = i_k(p_k): shell r = the cells of the clamped box
+ * [max(c - r, 0), min(c + r, dims - 1)] that are not in box r - 1; every face of their lists is tested by steps 1-4.  After shell r, in
+ * fp32 with one rounding per operation:
+ *     LB = the minimum over the OPEN sides of the box of the distance from p to the side's plane:
+ *       low side of axis k, open iff c_k - r > 0:            p_k - (lo_k + (float) (c_k - r) cell)
+ *       high side of axis k, open iff c_k + r < dims_k - 1:  (lo_k + (float) (c_k + r + 1) cell) - p_k
+ *     no side open: stop (every cell has been tested);  stop iff (a face is held and (float) sqrt(d2) < LB) or LB > max_dist.
+ *   A term is negative for a point outside the grid on that side, which keeps the walk going.
+ *   Domain (DESIGN.md section 3 gives the argument): every finite vertex lies inside the grid box, and M = the largest absolute value
+ *   among the coordinates of lo, lo + dims cell and the points is at most 2^15 cell.  Within it a face that no cell of the box lists lies
+ *   at least guard = cell 2^-4 beyond an open plane, which pays for the roundings of LB and of dist: the walk tests every face that the
+ *   brute-force mode could return, ties included, so the two modes agree bit for bit.  The box part of the domain (F2N_ERR_UNSUPPORTED)
+ *   and the vertices (F2N_ERR_UNSUPPORTED for a finite vertex outside [lo_k - guard, lo_k + dims_k cell + guard]) are checked here; the
+ *   points are device data and are the caller's to check (the host layer does, with one reduction).
+ * max_dist must be >= 0 (+inf: no cut-off), F2N_ERR_INVALID_ARG otherwise.  A face index outside [0, V): F2N_ERR_INVALID_ARG.
+ * out_face[0] and out_dist[0] are the flag words of the two checks before the points are processed; the call READS THEM BACK, so it
+ * synchronises the stream.  n_points == 0: F2N_OK, nothing is touched.  F == 0: every point misses. */
+int f2n_mesh_closest_point(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/,
+                           const float* lo /*host [3]*/, float cell, const int32_t* dims /*host [3]*/,
+                           const int32_t* cell_start /*[ncells+1] or NULL*/, const int32_t* cell_faces /*[E]*/, int n_points,
+                           const float* points /*[N,3]*/, float max_dist, float* out_dist /*[N]*/, int32_t* out_face /*[N]*/,
+                           float* out_bary /*[N,3]*/);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Area-uniform surface samples of a triangle mesh (additive; the ABI version is unchanged): stratified over the faces' areas, drawn
+ * by the keyed Philox4x32-10.  No reference counterpart.  csrc/octree.hip; tests/mesh_distance_ref.py restates it in numpy.
+ * ------------------------------------------------------------------------------------------------- */
+/* f2n_mesh_face_weights: per face, fp64 from the fp32 coordinates, one rounding per operation: p = B - A, q = C - A,
+ *   n = (p_y q_z - p_z q_y, p_z q_x - p_x q_z, p_x q_y - p_y q_x), area2 [F] = sqrt((n_x n_x + n_y n_y) + n_z n_z) (twice the area;
+ *   correctly rounded); 0 for a face with an index outside [0, V) or a vertex that is not finite.  With weights != NULL also
+ *   weights [F] int64 = (int64) floor(area2 / quantum) (quantum > 0 and finite, F2N_ERR_INVALID_ARG otherwise).  Either output may be NULL.
+ * The caller's plumbing: quantum = max_f area2_f 2^-31 (a max is order-free; the largest weight is 2^31), cum [F] int64 = the inclusive
+ *   prefix sum of the weights, T = cum[F - 1] (exact).  T == 0 (no face with an area) is the caller's error to report.
+ * f2n_mesh_sample_surface: sample j of n, one lane each, a pure function of (mesh, n, key, j):
+ *   x = Philox4x32-10 of counter (j, 0, 0, 0) under `key` (low word, high word), key = seed ^ purpose as host/KeyedDraws.h forms keys;
+ *   fp64: target = min((int64) floor(((double) j + (x0 + 0.5) 2^-32) / (double) n * (double) T), T - 1);
+ *   face = the first f with cum[f] > target (a binary search; a face of weight 0 is never drawn);
+ *   fp64: s = sqrt((x1 + 0.5) 2^-32), r = (x2 + 0.5) 2^-32;  bary = ((float) (1 - s), (float) (s (1 - r)), (float) (s r));
+ *   point = (b0 A + b1 B) + b2 C per coordinate in fp32 from the fp32 bary.
+ *   Stratum j holds one target, so the number of samples on face f differs from n w_f / T by less than 2 (up to the fp64 roundings of
+ *   the target, which move it by less than 2^-52 T).  cum must be non-decreasing with cum[F - 1] > 0; n > 0 with F == 0 or V == 0 is
+ *   F2N_ERR_INVALID_ARG.  n == 0: F2N_OK, nothing is touched. */
+int f2n_mesh_face_weights(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/,
+                          double quantum, double* area2 /*[F] or NULL*/, int64_t* weights /*[F] or NULL*/);
+int f2n_mesh_sample_surface(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/,
+                            const int64_t* cum /*[F]*/, int n_samples, uint64_t key, float* out_points /*[n,3]*/, int32_t* out_face /*[n]*/,
+                            float* out_bary /*[n,3]*/);
+
+/* ---------------------------------------------------------------------------------------------------
  * Texture atlas of a triangle mesh (additive; the ABI version is unchanged): one right-triangle chart per face, two charts to a
  * square block of 2^k texels a side, blocks placed by the Morton decode of a prefix sum; the texel-to-surface map; a bilinear
  * lookup.  No reference counterpart.  csrc/octree.hip.  Every operation is ONE rounding of the stated width, never an FMA, and one
