@@ -1252,6 +1252,43 @@ def texture_sample(tex, uv):
     return out
 
 
+# ---------------------------------------------------------------- SSIM
+def ssim_window(filter_size=11, filter_sigma=1.5):
+    """The reference's normalised Gaussian window as a list of filter_size floats (f2n_ssim_window; host only)."""
+    out = (ctypes.c_double * 33)()
+    if lib().f2n_ssim_window(_i(int(filter_size)), _d(float(filter_sigma)), out) != 0:
+        raise ValueError("ssim_window: filter_size in [1, 33], filter_sigma > 0 and finite")
+    return [float(out[k]) for k in range(int(filter_size))]
+
+
+def image_ssim(a, b, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, return_map=False):
+    """(mean, per_channel [C] float64 on the host, map [H-fs+1,W-fs+1,C] float64 on the device or None): the reference's rgb_ssim
+    (scripts/eval.py:29-75) of two float32 [H,W,C] device images (f2n_image_ssim: fp64, fixed tap order, exact integer mean).  A mean is NaN
+    if a value under it is not finite.  Reads the statistics back: it synchronises."""
+    rules = ("image_ssim: a and b must be float32 [H,W,C] of one shape with C in [1, 4], filter_size in [1, 33] and at most min(H, W), "
+             "(H - filter_size + 1) (W - filter_size + 1) <= 2^26, filter_sigma > 0 and finite")
+    fs = int(filter_size)
+    if a.dim() != 3 or a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError(rules)
+    H, W, C = (int(v) for v in a.shape)
+    if not (1 <= C <= 4 and 1 <= fs <= min(H, W, 33) and 0.0 < float(filter_sigma) < float("inf") and (H - fs + 1) * (W - fs + 1) <= 2 ** 26):
+        raise ValueError(rules)
+    w = (ctypes.c_double * 33)(*ssim_window(fs, filter_sigma))
+    c1, c2 = (float(k1) * float(max_val)) ** 2, (float(k2) * float(max_val)) ** 2
+    oh, ow = H - fs + 1, W - fs + 1
+    stats = torch.empty((C, 2), dtype=torch.int64, device=a.device)
+    m = torch.empty((oh, ow, C), dtype=torch.float64, device=a.device) if return_map else None
+    _ck(lib().f2n_image_ssim(_stream(), _i(H), _i(W), _i(C), _p(a, "f32"), _p(b, "f32"), w, _i(fs), _d(c1), _d(c2),
+                             ctypes.c_void_p(m.data_ptr()) if return_map else ctypes.c_void_p(0), ctypes.c_void_p(stats.data_ptr())),
+        "f2n_image_ssim")
+    st = [[int(v) for v in row] for row in stats.cpu().tolist()]
+    n = oh * ow
+    nan = float("nan")
+    per = torch.tensor([float(s) / (2.0 ** 36 * n) if k == n else nan for s, k in st], dtype=torch.float64)
+    mean = float(sum(s for s, _ in st)) / (2.0 ** 36 * (n * C)) if all(k == n for _, k in st) else nan
+    return mean, per, m
+
+
 # ---------------------------------------------------------------- TSDF fusion of depth maps
 def tsdf_integrate(S, W, lo, step, poses, intri, dist_params, depth, conf, trunc):
     """Adds the depth maps depth [V,h,w] (conf [V,h,w] or None: weight 1) seen from poses [V,3,4] / intri [V,3,3] / dist_params [V,4] into

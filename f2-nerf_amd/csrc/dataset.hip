@@ -187,6 +187,127 @@ __global__ void __launch_bounds__(256) tsdf_integrate_kernel(int64_t n, int nx, 
   W[i] = w_sum;
 }
 
+// SSIM of two images (include/f2n_abi.h, f2n_image_ssim; scripts/eval.py:29-75, the mip-NeRF definition): fp64 throughout, one rounding per
+// operation, every sum in a fixed tap order, the mean as an exact integer sum -- so an image's SSIM is a function of the two images
+// alone.  A 256-thread block owns a 16 x 32 tile of outputs (blockIdx.x, row-major) of ONE channel (blockIdx.z) with its fs - 1 halo:
+//   stage:      the (16 + fs - 1) x (32 + fs - 1) pixels of a and b as floats in LDS (pixels beyond the image: 0, they feed only outputs
+//               that do not exist);
+//   vertical:   one item per (output row, input column): the five window sums x, y, xx, yy, xy down the column, taps ascending, in
+//               registers, then to LDS as doubles (adjacent lanes, adjacent columns: no bank conflict);
+//   horizontal: one item per output: the five sums along the row from LDS, the formula, the map, the lane's fixed-point pair;
+//   reduce:     integer sums over the wave (shuffles), over the four waves (LDS), then ONE 64-bit vector atomic per statistic.
+// Dynamic LDS: (16 + fs - 1)(32 + fs - 1) 8 B + 5 x 16 (32 + fs - 1) 8 B: 35.6 KB for fs = 11, 64 KB for fs = 33 (the cross-wave sums
+// reuse the staging area).
+#define F2N_SSIM_TILE_H 16
+#define F2N_SSIM_TILE_W 32
+#define F2N_SSIM_MAX_FS 33
+
+struct SsimWindow {
+  double w[F2N_SSIM_MAX_FS];
+};
+
+// lines 56-73 of the reference for one output; the comparisons are spelled out so that a NaN goes through as numpy's maximum / minimum /
+// sign carry it
+__device__ __forceinline__ double f2n_ssim_value(double m0, double m1, double b00, double b11, double b01, double c1, double c2) {
+  const double mu00 = m0 * m0, mu11 = m1 * m1, mu01 = m0 * m1;
+  double s00 = b00 - mu00, s11 = b11 - mu11, s01 = b01 - mu01;
+  s00 = s00 < 0.0 ? 0.0 : s00;
+  s11 = s11 < 0.0 ? 0.0 : s11;
+  const double t = sqrt(s00 * s11), a = fabs(s01);
+  const double m = t < a ? t : a;
+  s01 = s01 < 0.0 ? -m : m;
+  const double numer = (2.0 * mu01 + c1) * (2.0 * s01 + c2);
+  const double denom = ((mu00 + mu11) + c1) * ((s00 + s11) + c2);
+  return numer / denom;
+}
+
+__global__ void __launch_bounds__(256) image_ssim_kernel(int height, int width, int channels, const float* __restrict__ img_a,
+                                                         const float* __restrict__ img_b, SsimWindow win, int fs, double c1, double c2,
+                                                         double* __restrict__ map, unsigned long long* __restrict__ stats) {
+  extern __shared__ double ssim_lds[];
+  const int tid = threadIdx.x, c = blockIdx.z;
+  const int oh = height - fs + 1, ow = width - fs + 1;
+  const int tiles_x = (ow + F2N_SSIM_TILE_W - 1) / F2N_SSIM_TILE_W;  // (tiles are numbered along blockIdx.x: a grid's y extent is 65535)
+  const int tile_y = blockIdx.x / tiles_x;
+  const int y0 = tile_y * F2N_SSIM_TILE_H, x0 = (blockIdx.x - tile_y * tiles_x) * F2N_SSIM_TILE_W;
+  const int in_rows = F2N_SSIM_TILE_H + fs - 1, in_cols = F2N_SSIM_TILE_W + fs - 1;
+  float* raw_a = (float*) ssim_lds;
+  float* raw_b = raw_a + in_rows * in_cols;
+  double* vert = ssim_lds + in_rows * in_cols;  // [5][TILE_H][in_cols]
+  const int plane = F2N_SSIM_TILE_H * in_cols;
+  for (int i = tid; i < in_rows * in_cols; i += 256) {
+    const int r = i / in_cols, j = i - r * in_cols;
+    const int y = y0 + r, x = x0 + j;
+    float va = 0.f, vb = 0.f;
+    if (y < height && x < width) {
+      const size_t px = ((size_t) y * width + x) * channels + c;
+      va = img_a[px];
+      vb = img_b[px];
+    }
+    raw_a[i] = va;
+    raw_b[i] = vb;
+  }
+  __syncthreads();
+  for (int i = tid; i < plane; i += 256) {
+    const int r = i / in_cols, j = i - r * in_cols;
+    double sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;
+    for (int k = 0; k < fs; k++) {
+      const double w = win.w[k];
+      const double x = (double) raw_a[(r + k) * in_cols + j], y = (double) raw_b[(r + k) * in_cols + j];
+      sx = sx + w * x;
+      sy = sy + w * y;
+      sxx = sxx + w * (x * x);
+      syy = syy + w * (y * y);
+      sxy = sxy + w * (x * y);
+    }
+    vert[i] = sx;
+    vert[plane + i] = sy;
+    vert[2 * plane + i] = sxx;
+    vert[3 * plane + i] = syy;
+    vert[4 * plane + i] = sxy;
+  }
+  __syncthreads();
+  long long sum = 0, cnt = 0;
+  for (int i = tid; i < F2N_SSIM_TILE_H * F2N_SSIM_TILE_W; i += 256) {
+    const int r = i / F2N_SSIM_TILE_W, j = i - r * F2N_SSIM_TILE_W;
+    const int y = y0 + r, x = x0 + j;
+    if (y >= oh || x >= ow) continue;
+    const double* v = vert + r * in_cols + j;
+    double m0 = 0.0, m1 = 0.0, b00 = 0.0, b11 = 0.0, b01 = 0.0;
+    for (int k = 0; k < fs; k++) {
+      const double w = win.w[k];
+      m0 = m0 + w * v[k];
+      m1 = m1 + w * v[plane + k];
+      b00 = b00 + w * v[2 * plane + k];
+      b11 = b11 + w * v[3 * plane + k];
+      b01 = b01 + w * v[4 * plane + k];
+    }
+    const double val = f2n_ssim_value(m0, m1, b00, b11, b01, c1, c2);
+    if (map != nullptr) map[((size_t) y * ow + x) * channels + c] = val;
+    if (fabs(val) < __builtin_huge_val()) {  // (false for a NaN as well)
+      sum += __double2ll_rn(val * 68719476736.0);
+      cnt += 1;
+    }
+  }
+  // integers: any order gives the same sums
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    sum += __shfl_xor(sum, d);
+    cnt += __shfl_xor(cnt, d);
+  }
+  __syncthreads();  // (the staging area is free from here on)
+  long long* part = (long long*) ssim_lds;
+  if ((tid & 63) == 0) {
+    part[2 * (tid >> 6)] = sum;
+    part[2 * (tid >> 6) + 1] = cnt;
+  }
+  __syncthreads();
+  if (tid < 2) {
+    const long long tot = (part[tid] + part[2 + tid]) + (part[4 + tid] + part[6 + tid]);
+    if (tot != 0) atomicAdd(stats + 2 * c + tid, (unsigned long long) tot);
+  }
+}
+
 extern "C" {
 
 int f2n_tsdf_integrate(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int n_views, const float* poses,
@@ -247,6 +368,45 @@ int f2n_gather_pixels(void* stream, int n_rays, int height, int width, const flo
   hipLaunchKernelGGL(gather_pixels_kernel, dim3(f2n_div_up(n_rays, 256)), dim3(256), 0, (hipStream_t) stream, n_rays, height, width,
                      images, cam_bounds, cam_indices, ij, gt_colors, bounds);
   return f2n_launch_status();
+}
+
+int f2n_ssim_window(int filter_size, double sigma, double* out) {
+  if (filter_size < 1 || filter_size > F2N_SSIM_MAX_FS || !(sigma > 0.0) || !(sigma < __builtin_huge_val()) || out == nullptr)
+    return F2N_ERR_INVALID_ARG;
+  const int hw = filter_size / 2;
+  const double shift = (double) (2 * hw - filter_size + 1) / 2.0;
+  double sum = 0.0;
+  for (int i = 0; i < filter_size; i++) {
+    const double u = ((double) (i - hw) + shift) / sigma;
+    out[i] = exp(-0.5 * (u * u));
+    sum = sum + out[i];
+  }
+  for (int i = 0; i < filter_size; i++) out[i] = out[i] / sum;
+  return F2N_OK;
+}
+
+int f2n_image_ssim(void* stream, int height, int width, int channels, const float* a, const float* b, const double* window, int filter_size,
+                   double c1, double c2, double* map_or_null, int64_t* stats) {
+  if (channels < 1 || channels > 4 || filter_size < 1 || filter_size > F2N_SSIM_MAX_FS || height < filter_size || width < filter_size ||
+      a == nullptr || b == nullptr || window == nullptr || stats == nullptr)
+    return F2N_ERR_INVALID_ARG;
+  const int oh = height - filter_size + 1, ow = width - filter_size + 1;
+  if ((int64_t) oh * ow > ((int64_t) 1 << 26)) return F2N_ERR_INVALID_ARG;
+  const unsigned tiles = f2n_div_up(oh, F2N_SSIM_TILE_H) * f2n_div_up(ow, F2N_SSIM_TILE_W);  // (at most 2^26 outputs: below 2^27 tiles)
+  SsimWindow win;
+  for (int k = 0; k < F2N_SSIM_MAX_FS; k++) win.w[k] = k < filter_size ? window[k] : 0.0;
+  const hipError_t e = hipMemsetAsync(stats, 0, sizeof(int64_t) * 2 * channels, (hipStream_t) stream);
+  if (e != hipSuccess) return -(1000 + (int) e);
+  const int in_rows = F2N_SSIM_TILE_H + filter_size - 1, in_cols = F2N_SSIM_TILE_W + filter_size - 1;
+  const size_t lds = sizeof(double) * ((size_t) in_rows * in_cols + 5 * (size_t) F2N_SSIM_TILE_H * in_cols);
+  hipLaunchKernelGGL(image_ssim_kernel, dim3(tiles, 1, channels), dim3(256), lds, (hipStream_t) stream, height,
+                     width, channels, a, b, win, filter_size, c1, c2, map_or_null, (unsigned long long*) stats);
+  return f2n_launch_status();
+}
+
+void f2n_ssim_tile(int* tile_h, int* tile_w) {
+  *tile_h = F2N_SSIM_TILE_H;
+  *tile_w = F2N_SSIM_TILE_W;
 }
 
 }  // extern "C"

@@ -71,6 +71,16 @@ class ExpRunner {
   GeometryResult RenderGeometry(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds, float tau, bool keep_samples);
   float TestImagePSNR(Dataset& dataset, int idx);       // 8-bit quantised prediction, as ExpRunner.cpp:360-369
   std::vector<float> TestImages(Dataset& dataset);      // per-view PSNR of the test set, then the mean
+  // One test view with everything ExpRunner::TestImages of the reference measures or writes (ExpRunner.cpp:353-379), from ONE render:
+  // psnr as TestImagePSNR computes it; ssim = ImageSSIM of the 8-bit quantised prediction against the resident ground truth with the
+  // defaults of scripts/eval.py (what that script gets from the PNGs); pred [H,W,3] (quantised: grey level k as the correctly rounded
+  // fp32 k / 255, what a reader of the PNG gets), disp and oct_disp [H,W,1].
+  struct ImageMetrics {
+    float psnr = 0.f;
+    double ssim = 0.0;
+    Tensor pred, disp, oct_disp;
+  };
+  ImageMetrics TestImageMetrics(Dataset& dataset, int idx);
   Tensor RenderPathFrame(Dataset& dataset, const Tensor& pose, int res_level = 1);
   Tensor VisualizeImage(Dataset& dataset, int idx);     // [H, 4W, 3]: gt | colours | first-hit disparity | disparity (ExpRunner.cpp:301-321)
   void RenderPath(Dataset& dataset, const Tensor& render_poses, const std::function<void(int, const Tensor&)>& sink,

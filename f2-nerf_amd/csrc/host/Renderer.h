@@ -141,6 +141,12 @@ MeshAtlasResult MeshAtlas(const Tensor& verts, const Tensor& faces, float densit
 std::tuple<Tensor, Tensor, Tensor> MeshAtlasTexels(const Tensor& verts, const Tensor& faces, const MeshAtlasResult& a, bool clamp);
 // [N,C]: the bilinear lookup of tex [S,S,C] at uv [N,2] (texel centres at (i + 0.5) / S, clamped to the edge; f2n_texture_sample)
 Tensor TextureSample(const Tensor& tex, const Tensor& uv);
+// SSIM of two float32 [H,W,C] images (the reference's rgb_ssim, scripts/eval.py:29-75; f2n_ssim_window + f2n_image_ssim, include/f2n_abi.h
+// states every rounding): c1 = (k1 max_val)^2, c2 = (k2 max_val)^2 in fp64; mean = sum_c stats[c][0] / (2^36 oh ow C) and per_channel [C]
+// (fp64, on the host) = stats[c][0] / (2^36 oh ow), each NaN if a count of finite values falls short of oh ow (np.mean of the reference's
+// map); map [oh,ow,C] fp64 on the device, undefined unless asked for.  Reads the statistics back: it synchronises the stream.
+std::tuple<double, Tensor, Tensor> ImageSSIM(const Tensor& a, const Tensor& b, double max_val = 1.0, int filter_size = 11, double sigma = 1.5,
+                                             double k1 = 0.01, double k2 = 0.03, bool return_map = false);
 
 struct MeshAttrs {  // Renderer::ExtractMeshAttrs; normals / colors are undefined unless asked for
   Tensor verts, faces, normals, colors;

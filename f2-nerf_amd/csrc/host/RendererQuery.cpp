@@ -827,6 +827,43 @@ Tensor TextureSample(const Tensor& tex, const Tensor& uv) {
   return out;
 }
 
+std::tuple<double, Tensor, Tensor> ImageSSIM(const Tensor& a, const Tensor& b, double max_val, int filter_size, double sigma, double k1, double k2,
+                                             bool return_map) {
+  torch::NoGradGuard g;
+  static const char* rules =
+      "image_ssim: a and b must be float32 [H,W,C] of one shape with C in [1, 4], filter_size in [1, 33] and at most min(H, W), "
+      "(H - filter_size + 1) (W - filter_size + 1) <= 2^26, filter_sigma > 0 and finite";
+  if (a.dim() != 3 || a.sizes() != b.sizes() || a.scalar_type() != torch::kFloat32 || b.scalar_type() != torch::kFloat32)
+    throw std::invalid_argument(rules);
+  const int64_t H = a.size(0), W = a.size(1), C = a.size(2);
+  if (C < 1 || C > 4 || filter_size < 1 || filter_size > 33 || filter_size > std::min(H, W) || !(sigma > 0.0) || !std::isfinite(sigma) ||
+      (H - filter_size + 1) * (W - filter_size + 1) > ((int64_t) 1 << 26))
+    throw std::invalid_argument(rules);
+  Tensor x = a.to(torch::kCUDA).contiguous(), y = b.to(torch::kCUDA).contiguous();
+  double window[33];
+  if (f2n_ssim_window(filter_size, sigma, window) != F2N_OK) throw std::invalid_argument(rules);
+  const double c1 = (k1 * max_val) * (k1 * max_val), c2 = (k2 * max_val) * (k2 * max_val);
+  const int64_t oh = H - filter_size + 1, ow = W - filter_size + 1;
+  Tensor stats = torch::empty({C, 2}, torch::TensorOptions().dtype(torch::kInt64).device(torch::kCUDA));
+  Tensor map;
+  if (return_map) map = torch::empty({oh, ow, C}, torch::TensorOptions().dtype(torch::kFloat64).device(torch::kCUDA));
+  F2N_TIMED_CALL("image_ssim", f2n_image_ssim(CurStream(), (int) H, (int) W, (int) C, F32P(x), F32P(y), window, filter_size, c1, c2,
+                                              return_map ? map.data_ptr<double>() : nullptr, stats.data_ptr<int64_t>()));
+  Tensor st = stats.cpu();
+  const int64_t* s = st.data_ptr<int64_t>();
+  const double n = (double) (oh * ow), nan = std::numeric_limits<double>::quiet_NaN();
+  Tensor per = torch::empty({C}, torch::kFloat64);
+  int64_t total = 0;
+  bool all = true;
+  for (int64_t c = 0; c < C; c++) {
+    const bool full = s[2 * c + 1] == oh * ow;
+    per.data_ptr<double>()[c] = full ? (double) s[2 * c] / (68719476736.0 * n) : nan;
+    total += s[2 * c];
+    all = all && full;
+  }
+  return {all ? (double) total / (68719476736.0 * (n * (double) C)) : nan, per, map};
+}
+
 MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level,
                                      int min_component_faces, bool normals, bool colors, const std::string& normal_source, int simplify) {
   torch::NoGradGuard g;

@@ -262,6 +262,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         },
         py::arg("verts"), py::arg("faces"), py::arg("blocks"), py::arg("size"), py::arg("clamp") = true);
   m.def("texture_sample", [](const Tensor& tex, const Tensor& uv) { return TextureSample(tex, uv); }, py::arg("tex"), py::arg("uv"));
+  m.def("image_ssim",
+        [](const Tensor& a, const Tensor& b, double max_val, int filter_size, double filter_sigma, double k1, double k2, bool return_map) {
+          auto r = ImageSSIM(a, b, max_val, filter_size, filter_sigma, k1, k2, return_map);
+          return py::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r).defined() ? py::cast(std::get<2>(r)) : py::none());
+        },
+        py::arg("a"), py::arg("b"), py::arg("max_val") = 1.0, py::arg("filter_size") = 11, py::arg("filter_sigma") = 1.5, py::arg("k1") = 0.01,
+        py::arg("k2") = 0.03, py::arg("return_map") = false);
   m.def("dp_set_table_buckets", [](int n) { DataParallel::table_buckets = n; });  // table all-reduce buckets of the next attach (A/B)
   // data-parallel replicas draw stream `rank` of every keyed purpose (KeyedDraws.h; the native attach sets it itself)
   m.def("dp_set_replica", [](int rank) { KeyedUniforms::SetReplica(rank); });
@@ -338,6 +345,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("render_rays", &ExpRunner::RenderRays)
       .def("render_whole_image", &ExpRunner::RenderWholeImage)
       .def("test_image_psnr", &ExpRunner::TestImagePSNR)
+      .def("test_image_metrics",
+           [](ExpRunner& r, Dataset& ds, int idx) {
+             auto m = r.TestImageMetrics(ds, idx);
+             py::dict d;
+             d["psnr"] = m.psnr; d["ssim"] = m.ssim; d["pred"] = m.pred; d["disp"] = m.disp; d["oct_disp"] = m.oct_disp;
+             return d;
+           },
+           py::arg("dataset"), py::arg("idx"))
       .def("test_images", &ExpRunner::TestImages)
       .def("visualize_image", &ExpRunner::VisualizeImage)
       .def("render_path_frame", &ExpRunner::RenderPathFrame, py::arg("dataset"), py::arg("pose"), py::arg("res_level") = 1)

@@ -12,7 +12,9 @@
     (split.npy)} -- the reference's layout (Dataset.cpp:16-146); NormalizeScene, bounds relaxation and the 8th-image test split
     are applied as there; images are decoded with PIL and kept resident in HBM.
   * modes (ExpRunner::Execute): train (ExpRunner::Train with checkpoints every save_freq and the final TestImages),
-    test (TestImages of the latest checkpoint), render_path (RenderPath over poses_render.npy), extract_mesh (with is_continue:
+    test (TestImages of the latest checkpoint; with test.ssim=true info.yaml gains `ssim: {view: value}` and `mean_ssim` -- the
+    reference's rgb_ssim of scripts/eval.py on the device, metrics.py -- and with test.write_images=true the reference's
+    test_images/color_<iter>_<idx>.png, depth_... and oct_depth_... are written), render_path (RenderPath over poses_render.npy), extract_mesh (with is_continue:
     <exp>/meshes/<iter>_<res>.ply, the density iso-surface in the data set's world frame, or with mesh.source=tsdf the surface fused from
     the training views' rendered depth; mesh.py), extract_points (with
     is_continue: <exp>/points/<iter>.ply, the training views' surface points with normals and colours; mesh.py).  Image files are written with
@@ -148,16 +150,40 @@ def main(argv=None):
                 os.remove(link)
             os.symlink(os.path.join(d, f), link)
 
+    from . import metrics
+    topt = metrics.launcher_options(cfg)  # (test.ssim / test.write_images: a bad value raises before anything is trained or rendered)
+
     def test_images():  # ExpRunner.cpp:343-383
         if rank != 0:
             return None
-        views = [float(v) for v in runner.test_images(ds)]
+        ssims = {}
+        if not (topt["ssim"] or topt["write_images"]):
+            views = [float(v) for v in runner.test_images(ds)]
+        else:  # one render per view gives the PSNR, the SSIM and the three images the reference writes (ExpRunner.cpp:353-379)
+            from . import mesh
+            views, acc = [], np.float32(0.)
+            for i in sc["test_set"]:
+                m = runner.test_image_metrics(ds, int(i))
+                views.append(float(m["psnr"]))
+                acc = np.float32(acc + np.float32(m["psnr"]))  # (ExpRunner::TestImages' own float sum)
+                ssims[str(int(i))] = float(m["ssim"])
+                if topt["write_images"]:
+                    # Utils::WriteImageTensor truncates (x * 255); pred holds k / 255 in fp32 and its file must hold that k, so it is rounded
+                    for name, img, half in (("color", m["pred"], .5), ("depth", m["disp"].repeat(1, 1, 3), 0.), ("oct_depth", m["oct_disp"].repeat(1, 1, 3), 0.)):
+                        u8 = (img.detach().clamp(0, 1) * 255. + half).to(torch.uint8).cpu().numpy()
+                        mesh.write_png(os.path.join(exp_dir, "test_images", "%s_%d_%03d.png" % (name, runner.iter_step, int(i))), u8)
+            views.append(float(acc / np.float32(len(views))) if views else 0.)
         out = {str(int(i)): p for i, p in zip(sc["test_set"], views[:-1])}
         out["mean_psnr"] = views[-1]
+        if topt["ssim"]:
+            out["ssim"] = ssims
+            out["mean_ssim"] = sum(ssims.values()) / len(ssims) if ssims else 0.
         os.makedirs(os.path.join(exp_dir, "test_images"), exist_ok=True)
         with open(os.path.join(exp_dir, "test_images", "info.yaml"), "w") as f:
             yaml.safe_dump(out, f)
         print("Mean psnr: %s" % views[-1])
+        if topt["ssim"]:
+            print("Mean ssim: %s" % out["mean_ssim"])
         return out
 
     try:

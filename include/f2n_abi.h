@@ -1280,6 +1280,42 @@ int f2n_atlas_texels(void* stream, int n_verts, int n_faces, const float* verts 
 int f2n_texture_sample(void* stream, int size, int channels, const float* tex /*[S,S,C]*/, int64_t n, const float* uv /*[N,2]*/,
                        float* out /*[N,C]*/);
 
+/* ---------------------------------------------------------------------------------------------------
+ * SSIM of two images (additive; the ABI version is unchanged): the reference's rgb_ssim (scripts/eval.py:29-75, the mip-NeRF definition),
+ * "valid" mode, in fp64 with a fixed order of operations and an exact integer sum for the mean.  csrc/dataset.hip; tests/ssim_ref.py
+ * restates it in numpy.
+ * ------------------------------------------------------------------------------------------------- */
+/* f2n_ssim_window (HOST only, no launch; scripts/eval.py:40-45): out [fs] doubles, every operation one fp64 rounding:
+ *   hw = fs / 2 (integer), shift = (2 hw - fs + 1) / 2 (0 for an odd fs, 0.5 for an even one), u_i = ((i - hw) + shift) / sigma,
+ *   e_i = exp(-0.5 (u_i u_i)) (the C library's exp), s = the sum of e_i in ascending i from 0, out_i = e_i / s.
+ *   The window is symmetric: out_i == out_(fs-1-i).  fs in [1, 33] of either parity, sigma > 0 and finite: F2N_ERR_INVALID_ARG otherwise.
+ *   Its own entry point so that every binding passes the same doubles to f2n_image_ssim.
+ * f2n_image_ssim (scripts/eval.py:47-73): a, b [H,W,C] fp32 on the device, window [fs] doubles on the HOST (they travel as kernel
+ *   arguments), stats [C][2] int64 on the device, map [H-fs+1, W-fs+1, C] doubles on the device or NULL.  Per channel, with
+ *   x = (double) a, y = (double) b, everything in fp64, never an FMA:
+ *   1. five planes x, y, x x, y y, x y (a product of two floats is exact in fp64);
+ *   2. each plane z is blurred down the columns first, V[i][j] = B_k z[i + k][j], then along the rows, B(z)[i][j] = B_k V[i][j + k]
+ *      (the order of the reference's two convolve2d calls), where B_k t_k is: acc = 0; for k = 0 .. fs-1 ascending: acc = acc + w[k] t_k,
+ *      each product and each sum rounded once.  The window is symmetric, so this correlation IS the reference's convolution;
+ *   3. mu0 = B(x), mu1 = B(y);  mu00 = mu0 mu0, mu11 = mu1 mu1, mu01 = mu0 mu1;
+ *      s00 = B(x x) - mu00, s11 = B(y y) - mu11, s01 = B(x y) - mu01;  s00 = (s00 < 0 ? 0 : s00), s11 likewise (a NaN stays a NaN);
+ *      t = sqrt(s00 s11) (IEEE), m = (t < |s01| ? t : |s01|), s01 = (s01 < 0 ? -m : m);
+ *      v = ((2 mu01 + c1) (2 s01 + c2)) / (((mu00 + mu11) + c1) ((s00 + s11) + c2)) (IEEE division);
+ *   4. map[i][j][c] = v if map != NULL;
+ *   5. v finite: stats[c][0] += llrint(v 2^36) (round half to even; |v| <= 1 by the clip of step 3), stats[c][1] += 1.  A v that is not
+ *      finite (a NaN or inf pixel under the window) adds to neither and is written to the map as it is.  The sums are exact int64 sums.
+ *   Properties: a == b gives v == 1.0 exactly at every output (numerator and denominator are then the same two factors);  stats and map are
+ *   functions of the two images, the window, c1 and c2 alone: not of the grid, the tile size or the order in which blocks run;  whether
+ *   the map is requested does not change stats.  The caller's mean of channel c is stats[c][0] / (2^36 stats[c][1]).
+ *   The call zeroes stats itself on `stream` before the launch.  C in [1, 4], 1 <= fs <= min(H, W, 33), (H-fs+1)(W-fs+1) <= 2^26:
+ *   F2N_ERR_INVALID_ARG otherwise, as for a NULL a, b, window or stats.
+ * f2n_ssim_tile (HOST only): the kernel's output tile (rows, columns), for tests that want shapes at its edges. */
+int f2n_ssim_window(int filter_size, double sigma, double* out /*host [fs]*/);
+int f2n_image_ssim(void* stream, int height, int width, int channels, const float* a /*[H,W,C]*/, const float* b /*[H,W,C]*/,
+                   const double* window /*host [fs]*/, int filter_size, double c1, double c2, double* map_or_null /*[H-fs+1,W-fs+1,C]*/,
+                   int64_t* stats /*device [C][2]*/);
+void f2n_ssim_tile(int* tile_h /*host*/, int* tile_w /*host*/);
+
 #ifdef __cplusplus
 }
 #endif
