@@ -993,6 +993,92 @@ def mesh_simplify(verts, faces, cell, lo=None, lam=1e-3):
     return ov, of, vert_map
 
 
+# ---------------------------------------------------------------- mesh refinement
+LEVEL_EMPTY, LEVEL_CONVERGED, LEVEL_STEP_CLAMPED, LEVEL_MOVE_CLAMPED = 1, 2, 4, 8  # the status bits of f2n_level_step
+
+
+def _mesh_ring(faces, n_verts):
+    """(ring_start_end, ring, pinned, edge_counts [2] int32 on the device): f2n_mesh_ring_keys -> sort, run lengths (torch ops:
+    plumbing) -> f2n_mesh_ring_fill"""
+    nv, nf = int(n_verts), int(faces.shape[0])
+    if nv < 0:
+        raise ValueError("mesh_ring: n_verts must be >= 0")
+    dev = faces.device
+    ek = uses = torch.empty(0, dtype=torch.int64, device=dev)
+    if nf > 0:
+        keys = torch.empty((nf, 6), dtype=torch.int64, device=dev)
+        _ck(lib().f2n_mesh_ring_keys(_stream(), _i(nv), _i(nf), _p(faces, "i32"), _p(keys, "i64")), "f2n_mesh_ring_keys")
+        keys = torch.sort(keys.view(-1)).values
+        ek, uses = torch.unique_consecutive(keys[keys >= 0], return_counts=True)
+        ek, uses = ek.contiguous(), uses.to(torch.int64).contiguous()
+    ne = int(ek.shape[0])
+    se = torch.empty((nv, 2), dtype=torch.int32, device=dev)
+    ring = torch.empty(ne, dtype=torch.int32, device=dev)
+    pinned = torch.empty(nv, dtype=torch.uint8, device=dev)
+    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    _ck(lib().f2n_mesh_ring_fill(_stream(), _i(nv), _i(ne), _p(ek, "i64", ne == 0), _p(uses, "i64", ne == 0), _p(se, "i32", nv == 0),
+                                 _p(ring, "i32", ne == 0), _p(pinned, "u8", nv == 0), _p(counts, "i32")), "f2n_mesh_ring_fill")
+    return se, ring, pinned, counts
+
+
+def mesh_ring(faces, n_verts):
+    """The vertex one-ring of a mesh: (ring_start_end [V,2], ring [E] (neighbours ascending, each once), pinned [V] uint8 (on a boundary or
+    non-manifold edge, or used by no face), [boundary_edges, nonmanifold_edges])."""
+    se, ring, pinned, counts = _mesh_ring(faces, n_verts)
+    return se, ring, pinned, [int(v) for v in counts.cpu()]
+
+
+def mesh_smooth(verts, faces, passes, lam=0.5, mu=-0.53, max_move=float("inf")):
+    """`passes` Taubin lambda|mu pairs of f2n_mesh_smooth over the one-ring, pinned vertices copied through; then f2n_mesh_move_clamp
+    against the input for a finite max_move."""
+    import math
+    if passes < 0:
+        raise ValueError("mesh_smooth: passes must be >= 0")
+    if not (math.isfinite(lam) and math.isfinite(mu)):
+        raise ValueError("mesh_smooth: lam and mu must be finite")
+    if not max_move > 0:
+        raise ValueError("mesh_smooth: max_move must be > 0 (inf: no clamp)")
+    nv = int(verts.shape[0])
+    a = verts.clone()
+    if nv == 0 or passes == 0:
+        return a
+    se, ring, pinned, _ = _mesh_ring(faces, nv)
+    ne = int(ring.shape[0])
+    b = torch.empty_like(a)
+    for _ in range(passes):
+        for src, dst, factor in ((a, b, lam), (b, a, mu)):
+            _ck(lib().f2n_mesh_smooth(_stream(), _i(nv), _i(ne), _p(src, "f32"), _p(se, "i32"), _p(ring, "i32", ne == 0), _p(pinned, "u8"),
+                                      _d(factor), _p(dst, "f32")), "f2n_mesh_smooth")
+    if math.isfinite(max_move):
+        _ck(lib().f2n_mesh_move_clamp(_stream(), _i(nv), _p(verts, "f32"), _f(max_move), _p(a, "f32")), "f2n_mesh_move_clamp")
+    return a
+
+
+def mesh_face_quality(verts, faces):
+    """[F] float64: 4 sqrt(3) area / (sum of the squared edge lengths) per face (f2n_mesh_face_quality)."""
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    q = torch.empty(nf, dtype=torch.float64, device=faces.device)
+    _ck(lib().f2n_mesh_face_quality(_stream(), _i(nv), _i(nf), _p(verts, "f32", nv == 0), _p(faces, "i32", nf == 0),
+                                    ctypes.c_void_p(q.data_ptr()) if nf else ctypes.c_void_p(0)), "f2n_mesh_face_quality")
+    return q
+
+
+def level_step(first, propose, p0, sigma, grad, h, tol, max_step, max_move, cand, best, h_best, g_best, scale, status, evals):
+    """f2n_level_step on the caller's arrays; cand, best, h_best, g_best, scale, status and evals are updated in place."""
+    n = int(p0.shape[0])
+    for t in (grad, cand, best, g_best):
+        if tuple(t.shape) != (n, 3):
+            raise F2nError("level_step: grad, cand, best and g_best must be [n,3]")
+    for t in (sigma, h, h_best, scale, status, evals):
+        if tuple(t.shape) != (n,):
+            raise F2nError("level_step: sigma, h, h_best, scale, status and evals must be [n]")
+    e = n == 0
+    _ck(lib().f2n_level_step(_stream(), _i(n), _i(1 if first else 0), _i(1 if propose else 0), _p(p0, "f32", e), _p(sigma, "f32", e),
+                             _p(grad, "f32", e), _p(h, "f32", e), _f(tol), _f(max_step), _f(max_move), _p(cand, "f32", e), _p(best, "f32", e),
+                             _p(h_best, "f32", e), _p(g_best, "f32", e), _p(scale, "f32", e), _p(status, "i32", e), _p(evals, "i32", e)),
+        "f2n_level_step")
+
+
 # ---------------------------------------------------------------- ray casting against a triangle mesh
 RAYCAST_MAX_CELLS = 1 << 27
 RAYCAST_DOMAIN_CELLS = 32768.0  # the grid traversal is exact for coordinates up to 2^15 cells (include/f2n_abi.h)

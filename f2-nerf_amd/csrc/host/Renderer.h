@@ -148,9 +148,46 @@ Tensor TextureSample(const Tensor& tex, const Tensor& uv);
 std::tuple<double, Tensor, Tensor> ImageSSIM(const Tensor& a, const Tensor& b, double max_val = 1.0, int filter_size = 11, double sigma = 1.5,
                                              double k1 = 0.01, double k2 = 0.03, bool return_map = false);
 
+// Mesh refinement (f2n_mesh_ring_*, f2n_mesh_smooth, f2n_mesh_move_clamp, f2n_level_step, f2n_mesh_face_quality; include/f2n_abi.h
+// states every rounding).  The one-ring of every vertex as a CSR: start_end [V,2] int32, ring [E] int32 (neighbours ascending, each
+// once), pinned [V] uint8 (on a boundary or non-manifold edge, or used by no face), edge_counts [2] int32 on the device (edges used by
+// one face, by three or more).  The sort of the directed-edge keys is a torch op; reads back one index.
+struct MeshRingResult {
+  Tensor start_end, ring, pinned, edge_counts;
+};
+MeshRingResult MeshRing(const Tensor& faces, int64_t n_verts);
+// `passes` Taubin pairs (a pass with lam, a pass with mu) over the ring, pinned vertices copied through; then, for a finite max_move,
+// the clamp of every vertex to the ball of that radius around its input position.  std::invalid_argument for passes < 0, a lam or mu
+// that is not finite, max_move <= 0 or NaN.
+Tensor MeshSmooth(const Tensor& verts, const Tensor& faces, int passes, double lam, double mu, float max_move);
+Tensor MeshSmoothOnRing(const Tensor& verts, const MeshRingResult& ring, int passes, double lam, double mu, float max_move);
+// [F] float64: 4 sqrt(3) area / (sum of the squared edge lengths); 0 for a degenerate or invalid face, NaN where a coordinate is not finite
+Tensor MeshFaceQuality(const Tensor& verts, const Tensor& faces);
+// f2n_level_step on the caller's device arrays, the state (cand .. evals) in place
+void LevelStep(bool first, bool propose, const Tensor& p0, const Tensor& sigma, const Tensor& grad, const Tensor& h, float tol, float max_step,
+               float max_move, const Tensor& cand, const Tensor& best, const Tensor& h_best, const Tensor& g_best, const Tensor& scale,
+               const Tensor& status, const Tensor& evals);
+
+// Renderer::ProjectToLevel: per point the position, ln(sigma / level) at the start and at the end, the status bits and the number of
+// field evaluations it used
+struct LevelProjection {
+  Tensor points, h_in, h_out, status, evals;
+};
+
+// the refine stage of Renderer::ExtractMeshAttrs; max_*_steps in grid steps (times simplify when simplify >= 2)
+struct MeshRefineOptions {
+  bool on = false;
+  int smooth_passes = 2;
+  double lam = 0.5, mu = -0.53;
+  bool project = true;
+  int iters = 8;
+  float max_step_steps = 0.5f, max_move_steps = 1.0f, tol = 1e-3f;
+};
+
 struct MeshAttrs {  // Renderer::ExtractMeshAttrs; normals / colors are undefined unless asked for
   Tensor verts, faces, normals, colors;
   int64_t verts_in = -1, faces_in = -1;  // simplify >= 2: the size of the mesh that went into MeshSimplify
+  std::vector<std::pair<std::string, double>> refine;  // the refine stage's statistics, in order (empty: the stage was off)
 };
 
 // Renderer::RenderGeometry: RenderForward's result and the geometry buffers of f2n_composite_geometry
@@ -391,7 +428,15 @@ class Renderer : public Pipe {
   // normal_source "field": the normals are FieldNormals at the kept vertices (a vertex whose field normal is the zero vector takes
   // its grid normal) and the colours follow them; "grid" (the default): the density grid's normals
   MeshAttrs ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
-                             bool normals, bool colors, const std::string& normal_source = "grid", int simplify = 0);
+                             bool normals, bool colors, const std::string& normal_source = "grid", int simplify = 0,
+                             const MeshRefineOptions& refine = MeshRefineOptions());
+  // Points moved onto the level set sigma = level by a damped Newton iteration on h = ln(sigma) - ln(level) along grad sigma / sigma:
+  // `iters` rounds of QueryDensityGrad at the candidates (DensityGradChunk, in slabs), a torch log, f2n_level_step.  A step is at most
+  // max_step long and no candidate leaves the ball of radius max_move around its origin (origins undefined: the point's own start).
+  // A point where the field cannot be evaluated (an empty leaf, sigma = 0) keeps its bits.  Inference only; the side-effect contract
+  // of QueryDensity.  std::invalid_argument for level <= 0, iters < 1, max_step <= 0, max_move <= 0, tol < 0.
+  LevelProjection ProjectToLevel(const Tensor& points, float level, int iters, float max_step, float max_move, float tol,
+                                 const Tensor& origins = Tensor());
   // (density [n], grad [n,3]) at world points: the density of QueryDensity, bit for bit, and its analytic gradient with respect to the
   // world position, sigma J^T df0/dw (f2n_field_density_grad / f2n_density_grad_scatter: the hash table's trilinear blend, the
   // density MLP and the leaf's warp differentiated exactly, fp32); zeros where no listed leaf holds the point.  Field shapes

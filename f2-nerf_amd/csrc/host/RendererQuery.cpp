@@ -563,6 +563,97 @@ std::tuple<Tensor, Tensor, Tensor> MeshSimplify(const Tensor& verts, const Tenso
   return {ov, of, vert_map};
 }
 
+MeshRingResult MeshRing(const Tensor& faces, int64_t n_verts) {
+  torch::NoGradGuard g;
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  const int64_t nf = f.size(0);
+  TORCH_CHECK(n_verts >= 0 && n_verts <= INT32_MAX && nf <= INT32_MAX / 6, "mesh too large");
+  const auto i64 = DevI32().dtype(torch::kInt64);
+  Tensor ek = torch::empty({0}, i64), uses = torch::empty({0}, i64);
+  if (nf > 0) {
+    Tensor keys = torch::empty({nf, 6}, i64);
+    F2N_TIMED_CALL("mesh_ring_keys", f2n_mesh_ring_keys(CurStream(), (int) n_verts, (int) nf, I32P(f), keys.data_ptr<int64_t>()));
+    TimedSpan span("mesh_ring_sort");
+    Tensor sorted = std::get<0>(torch::sort(keys.view({-1})));
+    const int64_t first = torch::searchsorted(sorted, torch::zeros({1}, i64)).item<int64_t>();  // the invalid faces' -1 sort first
+    auto u = at::unique_consecutive(sorted.narrow(0, first, sorted.size(0) - first), /*return_inverse=*/false, /*return_counts=*/true);
+    ek = std::get<0>(u).contiguous();
+    uses = std::get<2>(u).to(torch::kInt64).contiguous();
+  }
+  const int64_t ne = ek.size(0);
+  MeshRingResult r;
+  r.start_end = torch::empty({n_verts, 2}, DevI32());
+  r.ring = torch::empty({ne}, DevI32());
+  r.pinned = torch::empty({n_verts}, DevI32().dtype(torch::kUInt8));
+  r.edge_counts = torch::zeros({2}, DevI32());
+  F2N_TIMED_CALL("mesh_ring_fill", f2n_mesh_ring_fill(CurStream(), (int) n_verts, (int) ne, ne > 0 ? ek.data_ptr<int64_t>() : nullptr,
+                                                      ne > 0 ? uses.data_ptr<int64_t>() : nullptr, n_verts > 0 ? I32P(r.start_end) : nullptr,
+                                                      ne > 0 ? I32P(r.ring) : nullptr, n_verts > 0 ? r.pinned.data_ptr<uint8_t>() : nullptr,
+                                                      I32P(r.edge_counts)));
+  return r;
+}
+
+Tensor MeshSmoothOnRing(const Tensor& verts, const MeshRingResult& ring, int passes, double lam, double mu, float max_move) {
+  torch::NoGradGuard g;
+  if (passes < 0) throw std::invalid_argument("mesh_smooth: passes must be >= 0");
+  if (!std::isfinite(lam) || !std::isfinite(mu)) throw std::invalid_argument("mesh_smooth: lam and mu must be finite");
+  if (!(max_move > 0.f)) throw std::invalid_argument("mesh_smooth: max_move must be > 0 (inf: no clamp)");
+  Tensor v = Points3(verts);
+  const int64_t nv = v.size(0), ne = ring.ring.size(0);
+  TORCH_CHECK(ring.start_end.size(0) == nv && ring.pinned.size(0) == nv, "mesh_smooth: the ring does not belong to these vertices");
+  Tensor a = v.clone();
+  if (nv == 0 || passes == 0) return a;
+  Tensor b = torch::empty_like(a);
+  auto pass = [&](const Tensor& src, const Tensor& dst, double factor) {
+    F2N_TIMED_CALL("mesh_smooth", f2n_mesh_smooth(CurStream(), (int) nv, (int) ne, F32P(src), I32P(ring.start_end),
+                                                  ne > 0 ? I32P(ring.ring) : nullptr, ring.pinned.data_ptr<uint8_t>(), factor, F32P(dst)));
+  };
+  for (int p = 0; p < passes; p++) {
+    pass(a, b, lam);
+    pass(b, a, mu);
+  }
+  if (std::isfinite(max_move)) F2N_TIMED_CALL("mesh_move_clamp", f2n_mesh_move_clamp(CurStream(), (int) nv, F32P(v), max_move, F32P(a)));
+  return a;
+}
+
+Tensor MeshSmooth(const Tensor& verts, const Tensor& faces, int passes, double lam, double mu, float max_move) {
+  Tensor v = Points3(verts);
+  return MeshSmoothOnRing(v, MeshRing(faces, v.size(0)), passes, lam, mu, max_move);
+}
+
+Tensor MeshFaceQuality(const Tensor& verts, const Tensor& faces) {
+  torch::NoGradGuard g;
+  Tensor v = Points3(verts);
+  Tensor f = faces.to(torch::kCUDA, torch::kInt32).contiguous().view({-1, 3});
+  const int64_t nv = v.size(0), nf = f.size(0);
+  TORCH_CHECK(nf <= INT32_MAX, "mesh too large");
+  Tensor q = torch::empty({nf}, DevF32().dtype(torch::kFloat64));
+  if (nf > 0)
+    F2N_TIMED_CALL("mesh_face_quality", f2n_mesh_face_quality(CurStream(), (int) nv, (int) nf, nv > 0 ? F32P(v) : nullptr, I32P(f),
+                                                              q.data_ptr<double>()));
+  return q;
+}
+
+void LevelStep(bool first, bool propose, const Tensor& p0, const Tensor& sigma, const Tensor& grad, const Tensor& h, float tol, float max_step,
+               float max_move, const Tensor& cand, const Tensor& best, const Tensor& h_best, const Tensor& g_best, const Tensor& scale,
+               const Tensor& status, const Tensor& evals) {
+  torch::NoGradGuard g;
+  if (!(tol >= 0.f) || !(max_step > 0.f) || !(max_move > 0.f))
+    throw std::invalid_argument("level_step: tol must be >= 0, max_step and max_move > 0");
+  const int64_t n = DevArg(p0, torch::kFloat32, "p0").numel() / 3;
+  TORCH_CHECK(n <= INT32_MAX, "too many points");
+  for (const Tensor* t : {&p0, &grad, &cand, &best, &g_best})
+    TORCH_CHECK(DevArg(*t, torch::kFloat32, "a [n,3] array").dim() == 2 && t->size(0) == n && t->size(1) == 3, "level_step: p0, grad, cand, best and g_best must be [n,3]");
+  for (const Tensor* t : {&sigma, &h, &h_best, &scale})
+    TORCH_CHECK(DevArg(*t, torch::kFloat32, "a [n] array").dim() == 1 && t->size(0) == n, "level_step: sigma, h, h_best and scale must be [n]");
+  for (const Tensor* t : {&status, &evals})
+    TORCH_CHECK(DevArg(*t, torch::kInt32, "status / evals").dim() == 1 && t->size(0) == n, "level_step: status and evals must be [n] int32");
+  if (n == 0) return;
+  F2N_TIMED_CALL("level_step", f2n_level_step(CurStream(), (int) n, first ? 1 : 0, propose ? 1 : 0, F32P(p0), F32P(sigma), F32P(grad), F32P(h), tol,
+                                              max_step, max_move, F32P(cand), F32P(best), F32P(h_best), F32P(g_best), F32P(scale), I32P(status),
+                                              I32P(evals)));
+}
+
 namespace {
 // per coordinate, over its finite values: (min [3], max [3]) on the host; min > max for a coordinate without a finite value
 void FiniteBox(const Tensor& v, float mn[3], float mx[3]) {
@@ -864,8 +955,65 @@ std::tuple<double, Tensor, Tensor> ImageSSIM(const Tensor& a, const Tensor& b, d
   return {all ? (double) total / (68719476736.0 * (n * (double) C)) : nan, per, map};
 }
 
+LevelProjection Renderer::ProjectToLevel(const Tensor& points, float level, int iters, float max_step, float max_move, float tol,
+                                         const Tensor& origins) {
+  torch::NoGradGuard g;
+  TORCH_CHECK(global_data_pool_->mode_ != RunningMode::TRAIN, "ProjectToLevel is an inference path");
+  if (!(level > 0.f) || !std::isfinite(level)) throw std::invalid_argument("project_to_level: level must be positive and finite");
+  if (iters < 1) throw std::invalid_argument("project_to_level: iters must be >= 1 (it counts field evaluations)");
+  if (!(max_step > 0.f) || !(max_move > 0.f) || !(tol >= 0.f))
+    throw std::invalid_argument("project_to_level: max_step and max_move must be > 0, tol >= 0");
+  Tensor start = Points3(points);
+  Tensor p0 = origins.defined() ? Points3(origins) : start;
+  const int64_t n = start.size(0);
+  TORCH_CHECK(p0.size(0) == n, "project_to_level: one origin per point");
+  LevelProjection out;
+  out.points = torch::empty({n, 3}, DevF32());
+  out.h_in = torch::empty({n}, DevF32());
+  out.h_out = torch::empty({n}, DevF32());
+  out.status = torch::empty({n}, DevI32());
+  out.evals = torch::empty({n}, DevI32());
+  const Tensor log_level = torch::log(torch::full({1}, level, DevF32()));
+  for (int64_t i0 = 0; i0 < n; i0 += density_slab_points_) {  // (bounded workspaces, as DensityGradSlabs)
+    const int64_t c = std::min(density_slab_points_, n - i0);
+    Tensor cand = start.narrow(0, i0, c).clone(), origin = p0.narrow(0, i0, c);
+    Tensor best = out.points.narrow(0, i0, c), h_best = out.h_out.narrow(0, i0, c), status = out.status.narrow(0, i0, c);
+    Tensor evals = out.evals.narrow(0, i0, c);
+    Tensor g_best = torch::empty({c, 3}, DevF32()), scale = torch::empty({c}, DevF32());
+    Tensor sigma = torch::empty({c}, DevF32()), grad = torch::empty({c, 3}, DevF32());
+    for (int k = 0; k < iters; k++) {
+      DensityGradChunk(cand, sigma, grad, Tensor());
+      Tensor h = (torch::log(sigma) - log_level).contiguous();
+      if (k == 0) out.h_in.narrow(0, i0, c).copy_(h);
+      LevelStep(k == 0, k + 1 < iters, origin, sigma, grad, h, tol, max_step, max_move, cand, best, h_best, g_best, scale, status, evals);
+    }
+  }
+  return out;
+}
+
+namespace {
+// the values of the sorted 1-d tensor at the given fractions of its length ("lower": index floor(q (n - 1))); NaN for an empty tensor
+std::vector<double> SortedAt(const Tensor& x, const std::vector<double>& qs) {
+  std::vector<double> out;
+  const int64_t n = x.numel();
+  Tensor s = n > 0 ? std::get<0>(torch::sort(x.to(torch::kFloat64).view({-1}))) : x;
+  std::vector<int64_t> at;
+  for (double q : qs) at.push_back(n > 0 ? (int64_t) std::floor(q * (double) (n - 1)) : 0);
+  Tensor picked = n > 0 ? s.index_select(0, torch::tensor(at, torch::kInt64).to(s.device())).cpu() : Tensor();
+  for (size_t k = 0; k < qs.size(); k++) out.push_back(n > 0 ? picked.data_ptr<double>()[k] : std::numeric_limits<double>::quiet_NaN());
+  return out;
+}
+
+Tensor FaceNormalsF64(const Tensor& verts, const Tensor& faces) {
+  Tensor v = verts.to(torch::kFloat64), f = faces.to(torch::kInt64);
+  Tensor a = v.index_select(0, f.select(1, 0)), b = v.index_select(0, f.select(1, 1)), c = v.index_select(0, f.select(1, 2));
+  return torch::cross(b - a, c - a, 1);
+}
+}  // namespace
+
 MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level,
-                                     int min_component_faces, bool normals, bool colors, const std::string& normal_source, int simplify) {
+                                     int min_component_faces, bool normals, bool colors, const std::string& normal_source, int simplify,
+                                     const MeshRefineOptions& refine) {
   torch::NoGradGuard g;
   const bool from_field = normal_source == "field";
   TORCH_CHECK(from_field || normal_source == "grid", "normal_source must be \"grid\" or \"field\", got \"", normal_source, "\"");
@@ -884,6 +1032,54 @@ MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::ve
     auto simple = MeshSimplify(out.verts, out.faces, (float) simplify * s.step, s.lo, 1e-3);
     out.verts = std::get<0>(simple);
     out.faces = std::get<1>(simple);
+  }
+  if (refine.on) {  // smooth, then project onto the level set; the attributes below are computed at the refined vertices
+    const float unit = simplify >= 2 ? (float) simplify * s.step : s.step;
+    const float max_step = refine.max_step_steps * unit, max_move = refine.max_move_steps * unit;
+    if (!(max_step > 0.f) || !(max_move > 0.f)) throw std::invalid_argument("refine: max_step_steps and max_move_steps must be > 0");
+    if (refine.smooth_passes < 0) throw std::invalid_argument("refine: smooth_passes must be >= 0");
+    auto& st = out.refine;
+    const Tensor v0 = out.verts;
+    const int64_t nv = v0.size(0);
+    MeshRingResult ring = MeshRing(out.faces, nv);
+    Tensor q0 = MeshFaceQuality(v0, out.faces);
+    Tensor v = refine.smooth_passes > 0 ? MeshSmoothOnRing(v0, ring, refine.smooth_passes, refine.lam, refine.mu, max_move) : v0;
+    st.emplace_back("smooth_passes", refine.smooth_passes);
+    st.emplace_back("project", refine.project ? 1 : 0);
+    st.emplace_back("max_step", max_step);
+    st.emplace_back("max_move", max_move);
+    st.emplace_back("points", (double) nv);
+    if (refine.project) {
+      LevelProjection pr = ProjectToLevel(v, level, refine.iters, max_step, max_move, refine.tol, v0);
+      v = pr.points;
+      Tensor live = (pr.status.bitwise_and(F2N_LEVEL_EMPTY) == 0);
+      const char* names[4] = {"empty", "converged", "step_clamped", "move_clamped"};
+      const int bits[4] = {F2N_LEVEL_EMPTY, F2N_LEVEL_CONVERGED, F2N_LEVEL_STEP_CLAMPED, F2N_LEVEL_MOVE_CLAMPED};
+      for (int k = 0; k < 4; k++) st.emplace_back(names[k], (double) (pr.status.bitwise_and(bits[k]) != 0).sum().item<int64_t>());
+      st.emplace_back("evals", (double) pr.evals.sum(torch::kInt64).item<int64_t>());
+      const auto before = SortedAt(pr.h_in.masked_select(live).abs(), {0.5, 0.9});
+      const auto after = SortedAt(pr.h_out.masked_select(live).abs(), {0.5, 0.9});
+      st.emplace_back("h_median_before", before[0]);
+      st.emplace_back("h_p90_before", before[1]);
+      st.emplace_back("h_median_after", after[0]);
+      st.emplace_back("h_p90_after", after[1]);
+    }
+    const auto moved = SortedAt((v.to(torch::kFloat64) - v0.to(torch::kFloat64)).norm(2, 1) / (double) s.step, {0.5, 0.9, 1.0});
+    st.emplace_back("moved_median", moved[0]);
+    st.emplace_back("moved_p90", moved[1]);
+    st.emplace_back("moved_max", moved[2]);
+    const auto qb = SortedAt(q0, {0.5, 0.05}), qa = SortedAt(MeshFaceQuality(v, out.faces), {0.5, 0.05});
+    st.emplace_back("quality_median_before", qb[0]);
+    st.emplace_back("quality_p05_before", qb[1]);
+    st.emplace_back("quality_median_after", qa[0]);
+    st.emplace_back("quality_p05_after", qa[1]);
+    const int64_t flipped =
+        out.faces.size(0) > 0 ? ((FaceNormalsF64(v0, out.faces) * FaceNormalsF64(v, out.faces)).sum(1) < 0).sum().item<int64_t>() : 0;
+    st.emplace_back("flipped_faces", (double) flipped);
+    Tensor ec = ring.edge_counts.cpu();
+    st.emplace_back("boundary_edges", (double) ec.data_ptr<int32_t>()[0]);
+    st.emplace_back("nonmanifold_edges", (double) ec.data_ptr<int32_t>()[1]);
+    out.verts = v.contiguous();
   }
   if (!normals && !colors) return out;
   Tensor nrm = GridNormals(grid, out.verts, s.lo, s.step);

@@ -17,6 +17,16 @@ Hash3DAnchored* FieldOf(ExpRunner& r) { return static_cast<Hash3DAnchored*>(r.re
 SHShader* ShaderOf(ExpRunner& r) { return static_cast<SHShader*>(r.renderer_->shader_.get()); }
 PersSampler* SamplerOf(ExpRunner& r) { return static_cast<PersSampler*>(r.renderer_->pts_sampler_.get()); }
 
+// the runner in validation mode for the length of an inference call (as ExpRunner::RenderGeometry), put back on every exit path
+struct InferenceMode {
+  GlobalDataPool* gdp;
+  RunningMode prev;
+  InferenceMode(ExpRunner& r, bool on) : gdp(r.global_data_pool_.get()), prev(gdp->mode_) {
+    if (on) gdp->mode_ = RunningMode::VALIDATE;
+  }
+  ~InferenceMode() { gdp->mode_ = prev; }
+};
+
 py::dict StatsToDict(const TrainStats& s) {
   py::dict d;
   d["loss"] = s.loss;
@@ -169,6 +179,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::vector<Tensor>{std::get<0>(t), std::get<1>(t), std::get<2>(t)};
         },
         py::arg("verts"), py::arg("faces"), py::arg("cell"), py::arg("lo") = py::none(), py::arg("lam") = 1e-3);
+  // Mesh refinement on any mesh (f2n_mesh_ring_*, f2n_mesh_smooth, f2n_mesh_face_quality, f2n_level_step; include/f2n_abi.h).
+  // the vertex one-ring: (ring_start_end [V,2], ring [E] neighbours ascending, pinned [V] uint8, [boundary_edges, nonmanifold_edges])
+  m.def("mesh_ring",
+        [](const Tensor& faces, int64_t n_verts) {
+          if (n_verts < 0) throw std::invalid_argument("mesh_ring: n_verts must be >= 0");
+          MeshRingResult r = MeshRing(faces, n_verts);
+          Tensor ec = r.edge_counts.cpu();
+          return py::make_tuple(r.start_end, r.ring, r.pinned, std::vector<int64_t>{ec.data_ptr<int32_t>()[0], ec.data_ptr<int32_t>()[1]});
+        },
+        py::arg("faces"), py::arg("n_verts"));
+  // `passes` Taubin lambda|mu pairs (mu = lam: plain Laplacian pairs), boundary and non-manifold vertices pinned; max_move: the clamp
+  // of every vertex to a ball around its input position.  ValueError for passes < 0, lam / mu not finite, max_move <= 0
+  m.def("mesh_smooth",
+        [](const Tensor& verts, const Tensor& faces, int passes, double lam, double mu, float max_move) {
+          return MeshSmooth(verts, faces, passes, lam, mu, max_move);
+        },
+        py::arg("verts"), py::arg("faces"), py::arg("passes"), py::arg("lam") = 0.5, py::arg("mu") = -0.53,
+        py::arg("max_move") = std::numeric_limits<float>::infinity());
+  // [F] float64: 1 for an equilateral face, towards 0 for a sliver, 0 for a degenerate or invalid face, NaN for a coordinate not finite
+  m.def("mesh_face_quality", [](const Tensor& verts, const Tensor& faces) { return MeshFaceQuality(verts, faces); }, py::arg("verts"),
+        py::arg("faces"));
+  // the raw per-iteration update of the level-set projection on the caller's device arrays; cand .. evals are updated in place
+  m.def("level_step",
+        [](bool first, bool propose, const Tensor& p0, const Tensor& sigma, const Tensor& grad, const Tensor& h, float tol, float max_step,
+           float max_move, const Tensor& cand, const Tensor& best, const Tensor& h_best, const Tensor& g_best, const Tensor& scale,
+           const Tensor& status, const Tensor& evals) {
+          LevelStep(first, propose, p0, sigma, grad, h, tol, max_step, max_move, cand, best, h_best, g_best, scale, status, evals);
+        },
+        py::arg("first"), py::arg("propose"), py::arg("p0"), py::arg("sigma"), py::arg("grad"), py::arg("h"), py::arg("tol"),
+        py::arg("max_step"), py::arg("max_move"), py::arg("cand"), py::arg("best"), py::arg("h_best"), py::arg("g_best"), py::arg("scale"),
+        py::arg("status"), py::arg("evals"));
   // the acceleration grid of mesh_raycast over a mesh: (lo [3], cell, dims [3], cell_start, cell_faces); cell None: the documented
   // default (Renderer.h: MeshRaycastDefaultCell), lo None: the vertices' bounding-box minimum.  ValueError for a grid that is too fine
   m.def("mesh_raycast_build",
@@ -483,12 +524,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("world"), py::arg("dirs"))
       .def("extract_mesh_attrs",  // extract_mesh + floater removal, normals from the density grid, colours along the inward normal
            [](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
-              bool normals, bool colors, const std::string& normal_source, int simplify) {
+              bool normals, bool colors, const std::string& normal_source, int simplify, const py::object& refine) {
+             MeshRefineOptions ro;
+             if (!refine.is_none()) {  // a dict of the stage's options; an unknown key is an error
+               ro.on = true;
+               for (auto item : refine.cast<py::dict>()) {
+                 const std::string key = item.first.cast<std::string>();
+                 if (key == "smooth_passes") ro.smooth_passes = item.second.cast<int>();
+                 else if (key == "lam") ro.lam = item.second.cast<double>();
+                 else if (key == "mu") ro.mu = item.second.cast<double>();
+                 else if (key == "project") ro.project = item.second.cast<bool>();
+                 else if (key == "iters") ro.iters = item.second.cast<int>();
+                 else if (key == "max_step_steps") ro.max_step_steps = item.second.cast<float>();
+                 else if (key == "max_move_steps") ro.max_move_steps = item.second.cast<float>();
+                 else if (key == "tol") ro.tol = item.second.cast<float>();
+                 else throw std::invalid_argument("extract_mesh_attrs: unknown refine option \"" + key + "\"");
+               }
+             }
              MeshAttrs a;
              {
                py::gil_scoped_release no_gil;
                r.FinishPending();
-               a = r.renderer_->ExtractMeshAttrs(lo, hi, res, level, min_component_faces, normals, colors, normal_source, simplify);
+               InferenceMode mode(r, ro.on);  // (the projection refuses to run in training mode; without the stage nothing changes)
+               a = r.renderer_->ExtractMeshAttrs(lo, hi, res, level, min_component_faces, normals, colors, normal_source, simplify, ro);
              }
              py::dict d;
              d["verts"] = a.verts;
@@ -499,11 +557,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                d["verts_in"] = a.verts_in;
                d["faces_in"] = a.faces_in;
              }
+             if (ro.on) {  // the stage's statistics: counts as ints, everything else as floats
+               py::dict s;
+               for (const auto& kv : a.refine) {
+                 const bool real = kv.first.rfind("h_", 0) == 0 || kv.first.rfind("moved_", 0) == 0 || kv.first.rfind("quality_", 0) == 0 ||
+                                   kv.first.rfind("max_", 0) == 0;
+                 if (real) s[py::str(kv.first)] = kv.second;
+                 else s[py::str(kv.first)] = (int64_t) kv.second;
+               }
+               d["refine"] = s;
+             }
              return d;
            },
            py::arg("lo"), py::arg("hi"), py::arg("res"), py::arg("level"), py::arg("min_component_faces") = 0, py::arg("normals") = true,
            py::arg("colors") = true, py::arg("normal_source") = "grid",  // "field": normals (and colours) from the field's own gradient
-           py::arg("simplify") = 0)  // k >= 2: mesh_simplify on clusters of k^3 grid cells before the attributes are computed
+           py::arg("simplify") = 0,  // k >= 2: mesh_simplify on clusters of k^3 grid cells before the attributes are computed
+           // a dict (smooth_passes, lam, mu, project, iters, max_step_steps, max_move_steps, tol; {} = the defaults): Taubin smoothing and
+           // the projection onto the level set after the simplification, before the attributes; the result gains a "refine" dict
+           py::arg("refine") = py::none())
+      .def("project_to_level",  // points [n,3] moved onto sigma = level: a dict of points, h_in, h_out (ln(sigma / level)), status, evals
+           [](ExpRunner& r, const Tensor& points, float level, int iters, float max_step, float max_move, float tol,
+              const c10::optional<Tensor>& origins) {
+             LevelProjection p;
+             {
+               py::gil_scoped_release no_gil;
+               r.FinishPending();
+               InferenceMode mode(r, true);
+               p = r.renderer_->ProjectToLevel(points, level, iters, max_step, max_move, tol, origins.has_value() ? *origins : Tensor());
+             }
+             py::dict d;
+             d["points"] = p.points; d["h_in"] = p.h_in; d["h_out"] = p.h_out; d["status"] = p.status; d["evals"] = p.evals;
+             return d;
+           },
+           py::arg("points"), py::arg("level"), py::arg("iters") = 8, py::arg("max_step") = std::numeric_limits<float>::infinity(),
+           py::arg("max_move") = std::numeric_limits<float>::infinity(), py::arg("tol") = 1e-3f,
+           py::arg("origins") = py::none())  // [n,3]: the centres of the max_move balls (None: the points themselves)
       .def("query_density_grad",  // world [n,3] -> [density [n] (= query_density), grad [n,3] = its analytic world-space gradient]
            [](ExpRunner& r, const Tensor& world) {
              py::gil_scoped_release no_gil;

@@ -2141,3 +2141,283 @@ int f2n_texture_sample(void* stream, int size, int channels, const float* tex, i
   hipLaunchKernelGGL(texture_sample_kernel, dim3((unsigned) blocks), dim3(256), 0, (hipStream_t) stream, size, channels, tex, n, uv, out);
   return f2n_launch_status();
 }
+
+// =====================================================================================================================
+// Mesh refinement (include/f2n_abi.h, "Mesh refinement"): the vertex one-ring as a CSR built from sorted directed-edge
+// keys (the sort is the caller's), the Taubin smoothing pass, the trust-region clamp, the per-iteration update of the
+// projection onto a level set of ln(sigma), and the face quality.  One lane owns one face / vertex / point; the only
+// atomics are the two integer edge counts.  No transcendental function: + - * / sqrt, one rounding each.
+// =====================================================================================================================
+namespace {
+
+__global__ void __launch_bounds__(256) ring_keys_kernel(int n_verts, int n_faces, const int32_t* __restrict__ faces,
+                                                       long long* __restrict__ keys) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  int a, b, c;
+  const bool ok = face_in_range(faces, f, n_verts, &a, &b, &c) && a != b && b != c && a != c;
+  const long long V = n_verts;
+  long long* k = keys + f * 6;
+  k[0] = ok ? a * V + b : -1;
+  k[1] = ok ? b * V + a : -1;
+  k[2] = ok ? b * V + c : -1;
+  k[3] = ok ? c * V + b : -1;
+  k[4] = ok ? c * V + a : -1;
+  k[5] = ok ? a * V + c : -1;
+}
+
+// the first index in [0, n) whose key is >= want
+__device__ __forceinline__ int ring_lower_bound(const long long* __restrict__ keys, int n, long long want) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if (keys[mid] < want) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ void __launch_bounds__(256) ring_fill_kernel(int n_verts, int n_edges, const long long* __restrict__ edge_keys,
+                                                       const long long* __restrict__ edge_uses, int32_t* __restrict__ start_end,
+                                                       int32_t* __restrict__ ring, uint8_t* __restrict__ pinned, int32_t* edge_counts) {
+  const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_verts) return;
+  const long long V = n_verts;
+  const int s = ring_lower_bound(edge_keys, n_edges, v * V), e = ring_lower_bound(edge_keys, n_edges, (v + 1) * V);
+  start_end[v * 2] = s;
+  start_end[v * 2 + 1] = e;
+  bool pin = s == e;
+  int boundary = 0, nonmanifold = 0;
+  for (int j = s; j < e; j++) {
+    const int w = (int) (edge_keys[j] - v * V);
+    const long long uses = edge_uses[j];
+    ring[j] = w;
+    pin = pin || uses != 2;
+    if (w > v) {  // (an undirected edge is counted at its lower end)
+      boundary += uses == 1 ? 1 : 0;
+      nonmanifold += uses >= 3 ? 1 : 0;
+    }
+  }
+  pinned[v] = pin ? 1 : 0;
+  if (boundary != 0) atomicAdd(edge_counts, boundary);
+  if (nonmanifold != 0) atomicAdd(edge_counts + 1, nonmanifold);
+}
+
+__global__ void __launch_bounds__(256) mesh_smooth_kernel(int n_verts, int n_ring, const float* __restrict__ verts,
+                                                         const int32_t* __restrict__ start_end, const int32_t* __restrict__ ring,
+                                                         const uint8_t* __restrict__ pinned, double factor, float* __restrict__ out) {
+  const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_verts) return;
+  const float* p = verts + v * 3;
+  const int s = start_end[v * 2], e = start_end[v * 2 + 1];
+  bool move = pinned[v] == 0 && s >= 0 && s < e && e <= n_ring && finite3(p);
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  for (int j = s; move && j < e; j++) {
+    const int w = ring[j];
+    if (w < 0 || w >= n_verts || !finite3(verts + (int64_t) w * 3)) {
+      move = false;
+      break;
+    }
+    const float* q = verts + (int64_t) w * 3;
+    sx = sx + (double) q[0];
+    sy = sy + (double) q[1];
+    sz = sz + (double) q[2];
+  }
+  if (!move) {
+    out[v * 3] = p[0]; out[v * 3 + 1] = p[1]; out[v * 3 + 2] = p[2];
+    return;
+  }
+  const double cnt = (double) (e - s);
+  const double mx = sx / cnt, my = sy / cnt, mz = sz / cnt;
+  const double px = p[0], py = p[1], pz = p[2];
+  const double dx = mx - px, dy = my - py, dz = mz - pz;
+  const double tx = factor * dx, ty = factor * dy, tz = factor * dz;
+  out[v * 3] = (float) (px + tx);
+  out[v * 3 + 1] = (float) (py + ty);
+  out[v * 3 + 2] = (float) (pz + tz);
+}
+
+// x [3] pulled back into the ball of radius r around p0 [3] (fp32): true if it moved
+__device__ __forceinline__ bool move_clamp3(const float* p0, float r, float* x) {
+  const float ux = F2N_SUB_RN(x[0], p0[0]), uy = F2N_SUB_RN(x[1], p0[1]), uz = F2N_SUB_RN(x[2], p0[2]);
+  const float l = sqrtf(F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(ux, ux), F2N_MUL_RN(uy, uy)), F2N_MUL_RN(uz, uz)));
+  if (!(l > r)) return false;  // (a NaN length leaves the point alone)
+  float k = F2N_DIV_RN(r, l);
+  for (int round = 0; round < F2N_MOVE_CLAMP_ROUNDS; round++) {
+    x[0] = F2N_ADD_RN(p0[0], F2N_MUL_RN(ux, k));
+    x[1] = F2N_ADD_RN(p0[1], F2N_MUL_RN(uy, k));
+    x[2] = F2N_ADD_RN(p0[2], F2N_MUL_RN(uz, k));
+    // the three sums round to the coordinates' own grid, which can leave the point just outside: measured again, pulled in again
+    const float wx = F2N_SUB_RN(x[0], p0[0]), wy = F2N_SUB_RN(x[1], p0[1]), wz = F2N_SUB_RN(x[2], p0[2]);
+    const float lw = sqrtf(F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(wx, wx), F2N_MUL_RN(wy, wy)), F2N_MUL_RN(wz, wz)));
+    if (!(lw > r)) break;
+    k = F2N_MUL_RN(F2N_MUL_RN(k, F2N_DIV_RN(r, lw)), 0x1.fffffp-1f);
+  }
+  return true;
+}
+
+__global__ void __launch_bounds__(256) move_clamp_kernel(int n, const float* __restrict__ p0, float max_move, float* __restrict__ pts) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float x[3] = {pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]};
+  if (move_clamp3(p0 + i * 3, max_move, x)) {
+    pts[i * 3] = x[0]; pts[i * 3 + 1] = x[1]; pts[i * 3 + 2] = x[2];
+  }
+}
+
+__device__ __forceinline__ bool finite1(float x) { return fabsf(x) < __builtin_huge_valf(); }
+
+__global__ void __launch_bounds__(256) level_step_kernel(int n, int first, int propose, const float* __restrict__ p0,
+                                                        const float* __restrict__ sigma, const float* __restrict__ grad,
+                                                        const float* __restrict__ h, float tol, float max_step, float max_move,
+                                                        float* __restrict__ cand, float* __restrict__ best, float* __restrict__ h_best,
+                                                        float* __restrict__ g_best, float* __restrict__ scale, int32_t* __restrict__ status,
+                                                        int32_t* __restrict__ evals) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int st = first ? 0 : status[i];
+  if (st & (F2N_LEVEL_EMPTY | F2N_LEVEL_CONVERGED)) {  // a finished point proposes its own position
+    cand[i * 3] = best[i * 3]; cand[i * 3 + 1] = best[i * 3 + 1]; cand[i * 3 + 2] = best[i * 3 + 2];
+    return;
+  }
+  const float c[3] = {cand[i * 3], cand[i * 3 + 1], cand[i * 3 + 2]};
+  const float s = sigma[i], hc = h[i];
+  const float g[3] = {F2N_DIV_RN(grad[i * 3], s), F2N_DIV_RN(grad[i * 3 + 1], s), F2N_DIV_RN(grad[i * 3 + 2], s)};
+  const float q = F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(g[0], g[0]), F2N_MUL_RN(g[1], g[1])), F2N_MUL_RN(g[2], g[2]));
+  const bool evaluable = s > 0.f && finite1(s) && finite1(hc) && finite3(g) && q != 0.f;
+  float b[3], gb[3], hb, a;
+  if (first) {
+    evals[i] = 1;
+    b[0] = c[0]; b[1] = c[1]; b[2] = c[2];
+    hb = hc;
+    a = 1.f;
+    gb[0] = evaluable ? g[0] : 0.f; gb[1] = evaluable ? g[1] : 0.f; gb[2] = evaluable ? g[2] : 0.f;
+    if (!evaluable) st = F2N_LEVEL_EMPTY;
+  } else {
+    evals[i] = evals[i] + 1;
+    hb = h_best[i];
+    a = scale[i];
+    const bool accept = evaluable && fabsf(hc) <= fabsf(hb);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      b[k] = accept ? c[k] : best[i * 3 + k];
+      gb[k] = accept ? g[k] : g_best[i * 3 + k];
+    }
+    if (accept) hb = hc; else a = F2N_MUL_RN(a, 0.5f);
+  }
+  if (!(st & F2N_LEVEL_EMPTY) && fabsf(hb) <= tol) st |= F2N_LEVEL_CONVERGED;
+  float next[3] = {b[0], b[1], b[2]};
+  if (propose && !(st & (F2N_LEVEL_EMPTY | F2N_LEVEL_CONVERGED))) {
+    const float qb = F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(gb[0], gb[0]), F2N_MUL_RN(gb[1], gb[1])), F2N_MUL_RN(gb[2], gb[2]));
+    const float t = -F2N_DIV_RN(F2N_MUL_RN(a, hb), qb);
+    float d[3] = {F2N_MUL_RN(t, gb[0]), F2N_MUL_RN(t, gb[1]), F2N_MUL_RN(t, gb[2])};
+    const float l = sqrtf(F2N_ADD_RN(F2N_ADD_RN(F2N_MUL_RN(d[0], d[0]), F2N_MUL_RN(d[1], d[1])), F2N_MUL_RN(d[2], d[2])));
+    if (l > max_step) {
+      const float k = F2N_DIV_RN(max_step, l);
+      d[0] = F2N_MUL_RN(d[0], k); d[1] = F2N_MUL_RN(d[1], k); d[2] = F2N_MUL_RN(d[2], k);
+      st |= F2N_LEVEL_STEP_CLAMPED;
+    }
+    next[0] = F2N_ADD_RN(b[0], d[0]); next[1] = F2N_ADD_RN(b[1], d[1]); next[2] = F2N_ADD_RN(b[2], d[2]);
+    if (move_clamp3(p0 + i * 3, max_move, next)) st |= F2N_LEVEL_MOVE_CLAMPED;
+    if (!finite3(next)) { next[0] = b[0]; next[1] = b[1]; next[2] = b[2]; }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    cand[i * 3 + k] = next[k];
+    best[i * 3 + k] = b[k];
+    g_best[i * 3 + k] = gb[k];
+  }
+  h_best[i] = hb;
+  scale[i] = a;
+  status[i] = st;
+}
+
+__global__ void __launch_bounds__(256) face_quality_kernel(int n_verts, int n_faces, const float* __restrict__ verts,
+                                                          const int32_t* __restrict__ faces, double* __restrict__ out) {
+  const int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_faces) return;
+  int a, b, c;
+  double q = 0.0;
+  if (face_in_range(faces, f, n_verts, &a, &b, &c) && a != b && b != c && a != c) {
+    const float* pa = verts + (int64_t) a * 3;
+    const float* pb = verts + (int64_t) b * 3;
+    const float* pc = verts + (int64_t) c * 3;
+    if (finite3(pa) && finite3(pb) && finite3(pc)) {
+      const double px = (double) pb[0] - (double) pa[0], py = (double) pb[1] - (double) pa[1], pz = (double) pb[2] - (double) pa[2];
+      const double qx = (double) pc[0] - (double) pa[0], qy = (double) pc[1] - (double) pa[1], qz = (double) pc[2] - (double) pa[2];
+      const double rx = (double) pc[0] - (double) pb[0], ry = (double) pc[1] - (double) pb[1], rz = (double) pc[2] - (double) pb[2];
+      const double nx = py * qz - pz * qy, ny = pz * qx - px * qz, nz = px * qy - py * qx;
+      const double area2 = F2N_DSQRT_RN((nx * nx + ny * ny) + nz * nz);
+      const double l1 = (px * px + py * py) + pz * pz, l2 = (qx * qx + qy * qy) + qz * qz, l3 = (rx * rx + ry * ry) + rz * rz;
+      const double L = (l1 + l2) + l3;
+      q = L > 0.0 ? (F2N_FACE_QUALITY_K * area2) / L : 0.0;
+    } else {
+      q = __builtin_nan("");
+    }
+  }
+  out[f] = q;
+}
+
+}  // namespace
+
+int f2n_mesh_ring_keys(void* stream, int n_verts, int n_faces, const int32_t* faces, int64_t* keys) {
+  if (n_verts < 0 || n_faces < 0 || n_faces > 0x7fffffff / 6 || (n_faces > 0 && (faces == nullptr || keys == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n_faces == 0) return F2N_OK;
+  hipLaunchKernelGGL(ring_keys_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, (hipStream_t) stream, n_verts, n_faces, faces,
+                     (long long*) keys);
+  return f2n_launch_status();
+}
+
+int f2n_mesh_ring_fill(void* stream, int n_verts, int n_edges, const int64_t* edge_keys, const int64_t* edge_uses, int32_t* ring_start_end,
+                       int32_t* ring, uint8_t* pinned, int32_t* edge_counts) {
+  if (n_verts < 0 || n_edges < 0 || edge_counts == nullptr || (n_verts > 0 && (ring_start_end == nullptr || pinned == nullptr)) ||
+      (n_edges > 0 && (n_verts == 0 || edge_keys == nullptr || edge_uses == nullptr || ring == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t) stream;
+  if (hipMemsetAsync(edge_counts, 0, 2 * sizeof(int32_t), st) != hipSuccess) return f2n_launch_status();
+  if (n_verts == 0) return F2N_OK;
+  hipLaunchKernelGGL(ring_fill_kernel, dim3(f2n_div_up(n_verts, 256)), dim3(256), 0, st, n_verts, n_edges, (const long long*) edge_keys,
+                     (const long long*) edge_uses, ring_start_end, ring, pinned, edge_counts);
+  return f2n_launch_status();
+}
+
+int f2n_mesh_smooth(void* stream, int n_verts, int n_ring, const float* verts, const int32_t* ring_start_end, const int32_t* ring,
+                    const uint8_t* pinned, double factor, float* out_verts) {
+  if (n_verts < 0 || n_ring < 0 || !(fabs(factor) < __builtin_huge_val()) ||
+      (n_verts > 0 && (verts == nullptr || ring_start_end == nullptr || pinned == nullptr || out_verts == nullptr || out_verts == verts)) ||
+      (n_ring > 0 && ring == nullptr))
+    return F2N_ERR_INVALID_ARG;
+  if (n_verts == 0) return F2N_OK;
+  hipLaunchKernelGGL(mesh_smooth_kernel, dim3(f2n_div_up(n_verts, 256)), dim3(256), 0, (hipStream_t) stream, n_verts, n_ring, verts,
+                     ring_start_end, ring, pinned, factor, out_verts);
+  return f2n_launch_status();
+}
+
+int f2n_mesh_move_clamp(void* stream, int n, const float* p0, float max_move, float* pts) {
+  if (n < 0 || !(max_move > 0.f) || (n > 0 && (p0 == nullptr || pts == nullptr))) return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  hipLaunchKernelGGL(move_clamp_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, p0, max_move, pts);
+  return f2n_launch_status();
+}
+
+int f2n_level_step(void* stream, int n, int first, int propose, const float* p0, const float* sigma, const float* grad, const float* h,
+                   float tol, float max_step, float max_move, float* cand, float* best, float* h_best, float* g_best, float* scale,
+                   int32_t* status, int32_t* evals) {
+  if (n < 0 || !(tol >= 0.f) || !(max_step > 0.f) || !(max_move > 0.f) ||
+      (n > 0 && (p0 == nullptr || sigma == nullptr || grad == nullptr || h == nullptr || cand == nullptr || best == nullptr ||
+                 h_best == nullptr || g_best == nullptr || scale == nullptr || status == nullptr || evals == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  hipLaunchKernelGGL(level_step_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, first ? 1 : 0, propose ? 1 : 0, p0,
+                     sigma, grad, h, tol, max_step, max_move, cand, best, h_best, g_best, scale, status, evals);
+  return f2n_launch_status();
+}
+
+int f2n_mesh_face_quality(void* stream, int n_verts, int n_faces, const float* verts, const int32_t* faces, double* quality) {
+  if (n_verts < 0 || n_faces < 0 || (n_faces > 0 && (faces == nullptr || quality == nullptr || (n_verts > 0 && verts == nullptr))))
+    return F2N_ERR_INVALID_ARG;
+  if (n_faces == 0) return F2N_OK;
+  hipLaunchKernelGGL(face_quality_kernel, dim3(f2n_div_up(n_faces, 256)), dim3(256), 0, (hipStream_t) stream, n_verts, n_faces, verts, faces,
+                     quality);
+  return f2n_launch_status();
+}

@@ -48,6 +48,22 @@ Options (hydra-style overrides, no `mesh` group in the configs):
                    distance.seed (0), distance.thresholds ([0.5, 1, 2] grid steps), distance.max_dist_steps (none: samples farther than
                    this many grid steps from the other mesh are counted as missed and left out of the statistics).  The sample
                    count and the thresholds are choices, not measurements
+  mesh.refine      true: after the mesh is written as ever, a refined copy is made by the refine stage (after the floater removal and the
+                   simplification, before normals, colours, texture, check and distance, which then all see the refined vertices):
+                   refine.smooth_passes Taubin lambda|mu pairs over the vertex one-ring (host.mesh_smooth; default 2, a choice;
+                   refine.lam 0.5 and refine.mu -0.53: Taubin's pass band 1/lam + 1/mu ~ 0.1, a literature value), then every vertex
+                   is moved onto the level set by a damped Newton iteration on ln(sigma) - ln(level) along the field's analytic
+                   gradient (runner.project_to_level; refine.project, default true; refine.iters 8 field evaluations; refine.tol 1e-3
+                   in ln(sigma), a 0.1 % density error: a choice; refine.max_step_steps 0.5: a choice; refine.max_move_steps 1.0 grid
+                   steps from where the mesher put the vertex: the surface crosses the very edge the vertex sits on, at most sqrt(3)
+                   steps long -- a geometric argument, not a measurement; both are multiplied by mesh.simplify when that is >= 2)
+                   -> <same name>_r.ply, <same name>_r_refine.json (status counts, |ln(sigma/level)| before and after, the distance
+                   moved in grid steps, face quality before and after, flipped_faces, boundary_edges, nonmanifold_edges) and one
+                   printed line.  mesh.source=tsdf: the smoothing applies, the projection does not (the TSDF surface is no density
+                   level set: refine.project=true is an error there, unset means off).  Known limits: vertices on a boundary or
+                   non-manifold edge are pinned by the smoothing, so an open rim keeps its shape; nothing prevents
+                   self-intersection (flipped_faces only counts faces whose normal turned over); the projection follows ln(sigma),
+                   so a vertex in an empty leaf stays where it is.  Default false: nothing changes
   mesh.source      density | tsdf (default density): the iso-surface of the raw density at mesh.level, or the zero crossing of a
                    truncated signed distance field fused from the training views' rendered depth (fuse_tsdf; mesh.level is not
                    used, normals of source "grid" come from the TSDF) -> <exp>/meshes/<iter>_<res>_tsdf.ply
@@ -90,7 +106,64 @@ def options(cfg):
     return {"resolution": int(m.get("resolution", 256)), "level": float(m.get("level", DEFAULT_LEVEL)), "bbox_min": lo,
             "bbox_max": hi, "normals": _flag(m.get("normals", False)), "colors": _flag(m.get("colors", False)),
             "min_component_faces": int(m.get("min_component_faces", 0)), "normal_source": _normal_source(m.get("normal_source", "grid")),
-            "source": _source(m.get("source", "density")), "simplify": _simplify(m.get("simplify", 0))}
+            "source": _source(m.get("source", "density")), "simplify": _simplify(m.get("simplify", 0)),
+            "refine": refine_options(cfg, _source(m.get("source", "density")))}
+
+
+def refine_options(cfg, source="density"):
+    """mesh.refine and the refine.* options: None when the stage is off, else the dict runner.extract_mesh_attrs(..., refine=) takes.
+    Every default is a choice or a literature value, none is measured on a scene (the module's docstring says which)."""
+    import math
+    m = cfg.get("mesh") or {}
+    r = cfg.get("refine") or {}
+    if not _flag(m.get("refine", False)):
+        return None
+
+    def whole(name, default):
+        v = r.get(name, default)
+        if v is None or isinstance(v, bool) or (isinstance(v, float) and v != int(v)):
+            raise ValueError("refine.%s must be an integer, got %r" % (name, v))
+        return int(v)  # (ValueError for a string that is not an integer)
+    project = r.get("project", None)
+    if project is not None and _flag(project) and source == "tsdf":
+        raise ValueError("refine.project=true with mesh.source=tsdf: the TSDF surface is no level set of the density (the smoothing applies; "
+                         "leave refine.project unset)")
+    o = {"smooth_passes": whole("smooth_passes", 2), "lam": float(r.get("lam", 0.5)), "mu": float(r.get("mu", -0.53)),
+         "project": source != "tsdf" if project is None else _flag(project), "iters": whole("iters", 8),
+         "max_step_steps": float(r.get("max_step_steps", 0.5)), "max_move_steps": float(r.get("max_move_steps", 1.0)),
+         "tol": float(r.get("tol", 1e-3))}
+    if (o["smooth_passes"] < 0 or o["iters"] < 1 or not math.isfinite(o["lam"]) or not math.isfinite(o["mu"]) or not o["max_step_steps"] > 0.0 or
+            not o["max_move_steps"] > 0.0 or not 0.0 <= o["tol"] < float("inf")):
+        raise ValueError("refine.smooth_passes must be >= 0, refine.iters >= 1, refine.lam and refine.mu finite, refine.max_step_steps and "
+                         "refine.max_move_steps > 0, refine.tol >= 0 and finite, got %r" % (o,))
+    return o
+
+
+def _lower(x, q):
+    """the element floor(q (n - 1)) of the n ascending values (as the runner's refine statistics): a sort, no interpolation"""
+    e = np.sort(np.asarray(x, np.float64).reshape(-1))
+    return float(e[int(np.floor(q * (len(e) - 1)))]) if len(e) else float("nan")
+
+
+def _write_refined(path, scene, verts, faces, normals, colors, stats):
+    """<path without .ply>_r.ply, <the same>_r_refine.json and the Refine: line; returns the refined file's path"""
+    import json
+    rpath = path[:-4] + "_r.ply"
+    v = to_world(verts.cpu().numpy(), scene["center"], scene["radius"])
+    write_ply(rpath, v, faces.cpu().numpy(), normals, colors)
+    out = rpath[:-4] + "_refine.json"
+    with open(out, "w") as fh:
+        json.dump(stats, fh, indent=1, sort_keys=True)
+    g = lambda key: stats.get(key, float("nan"))  # noqa: E731
+    n = lambda key: int(stats.get(key, 0))  # noqa: E731
+    proj = ("|ln(sigma/level)| median %.4g -> %.4g, p90 %.4g -> %.4g, %d converged, %d empty" % (
+        g("h_median_before"), g("h_median_after"), g("h_p90_before"), g("h_p90_after"), n("converged"), n("empty"))) if "h_median_before" in stats \
+        else "no projection"
+    print("Refine: %d vertices, %d smoothing pairs, %s; moved %.3f / %.3f / %.3f grid steps (median / p90 / max), face quality p05 %.3f -> %.3f, "
+          "median %.3f -> %.3f, %d flipped faces, %d boundary and %d non-manifold edges -> %s, %s" % (
+              len(v), n("smooth_passes"), proj, g("moved_median"), g("moved_p90"), g("moved_max"), g("quality_p05_before"), g("quality_p05_after"),
+              g("quality_median_before"), g("quality_median_after"), n("flipped_faces"), n("boundary_edges"), n("nonmanifold_edges"), rpath, out))
+    return rpath
 
 
 def _simplify(v):
@@ -352,27 +425,51 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
     full_verts, full_faces = verts, faces  # (mesh.distance compares with the mesh before the simplification)
     if k >= 2:  # (cell = k * step as ONE float32 product: what extract_mesh_attrs uses)
         verts, faces, _ = host.mesh_simplify(verts, faces, float(np.float32(k) * np.float32(t["step"])), t["lo"])
-    normals = colors = None
-    tex_on, nrm = texture_options(cfg)["texture"], None
-    if (o["normals"] or o["colors"] or tex_on) and len(verts) > 0:
-        nrm = host.grid_normals(t["g"], verts, t["lo"], t["step"])  # (g is positive inside, as a density is: the same sign)
-        if o["normal_source"] == "field":  # the field's own gradient at the vertex; the grid's where that vanishes
-            fn = runner.field_normals(verts)
-            nrm = torch.where((fn == 0).all(1, keepdim=True), nrm, fn).contiguous()
-        if o["normals"]:
-            normals = nrm.cpu().numpy()
-        if o["colors"]:  # the radiance AT the vertex seen along the inward normal, as in the density export
-            flat = (nrm == 0).all(1, keepdim=True)
-            dirs = torch.where(flat, torch.tensor([[0.0, 0.0, -1.0]], device=nrm.device), -nrm).contiguous()
-            colors = runner.query_radiance(verts, dirs)[1].cpu().numpy()
-    elif o["normals"] or o["colors"]:
-        normals = np.zeros((0, 3), np.float32) if o["normals"] else None
-        colors = np.zeros((0, 3), np.float32) if o["colors"] else None
+    tex_on = texture_options(cfg)["texture"]
+
+    def attributes(verts):
+        normals = colors = nrm = None
+        if (o["normals"] or o["colors"] or tex_on) and len(verts) > 0:
+            nrm = host.grid_normals(t["g"], verts, t["lo"], t["step"])  # (g is positive inside, as a density is: the same sign)
+            if o["normal_source"] == "field":  # the field's own gradient at the vertex; the grid's where that vanishes
+                fn = runner.field_normals(verts)
+                nrm = torch.where((fn == 0).all(1, keepdim=True), nrm, fn).contiguous()
+            if o["normals"]:
+                normals = nrm.cpu().numpy()
+            if o["colors"]:  # the radiance AT the vertex seen along the inward normal, as in the density export
+                flat = (nrm == 0).all(1, keepdim=True)
+                dirs = torch.where(flat, torch.tensor([[0.0, 0.0, -1.0]], device=nrm.device), -nrm).contiguous()
+                colors = runner.query_radiance(verts, dirs)[1].cpu().numpy()
+        elif o["normals"] or o["colors"]:
+            normals = np.zeros((0, 3), np.float32) if o["normals"] else None
+            colors = np.zeros((0, 3), np.float32) if o["colors"] else None
+        return nrm, normals, colors
+
+    nrm, normals, colors = attributes(verts)
     path = os.path.join(exp_dir, "meshes", "%d_%d_tsdf%s.ply" % (runner.iter_step, o["resolution"], "_s%d" % k if k >= 2 else ""))
     v = to_world(verts.cpu().numpy(), scene["center"], scene["radius"])
     write_ply(path, v, faces.cpu().numpy(), normals, colors)
     print("Mesh: %d vertices, %d faces%s from the TSDF of %d views (%d of %d grid points known, truncation %g) -> %s" % (
         len(v), len(faces), _simplified(k, faces_in), t["n_views"], int(t["valid"].sum()), t["valid"].numel(), t["trunc"], path))
+    if o["refine"] is not None:  # the smoothing alone: the TSDF surface is no level set of the density
+        rf = o["refine"]
+        max_move = float(np.float32(rf["max_move_steps"]) * np.float32(t["step"]) * np.float32(k if k >= 2 else 1))
+        v0, q0 = verts, host.mesh_face_quality(verts, faces).cpu().numpy()
+        if rf["smooth_passes"] > 0:
+            verts = host.mesh_smooth(verts, faces, rf["smooth_passes"], rf["lam"], rf["mu"], max_move)
+        q1 = host.mesh_face_quality(verts, faces).cpu().numpy()
+        moved = (verts.double() - v0.double()).norm(dim=1).cpu().numpy() / float(t["step"])
+        fl = faces.long()
+        nb = torch.cross(v0.double()[fl[:, 1]] - v0.double()[fl[:, 0]], v0.double()[fl[:, 2]] - v0.double()[fl[:, 0]], dim=1)
+        na = torch.cross(verts.double()[fl[:, 1]] - verts.double()[fl[:, 0]], verts.double()[fl[:, 2]] - verts.double()[fl[:, 0]], dim=1)
+        edges = host.mesh_ring(faces, len(verts))[3]
+        stats = {"smooth_passes": rf["smooth_passes"], "project": 0, "max_move": max_move, "points": len(verts),
+                 "moved_median": _lower(moved, 0.5), "moved_p90": _lower(moved, 0.9), "moved_max": _lower(moved, 1.0),
+                 "quality_median_before": _lower(q0, 0.5), "quality_p05_before": _lower(q0, 0.05), "quality_median_after": _lower(q1, 0.5),
+                 "quality_p05_after": _lower(q1, 0.05), "flipped_faces": int(((nb * na).sum(1) < 0).sum()), "boundary_edges": int(edges[0]),
+                 "nonmanifold_edges": int(edges[1])}
+        nrm, normals, colors = attributes(verts)
+        path = _write_refined(path, scene, verts, faces, normals, colors, stats)
     tex = _run_texture(runner, cfg, scene, verts, faces, nrm, t["step"], path) if tex_on else None
     if check_options(cfg)["check"]:
         _run_check(runner, cfg, scene, dataset, verts, faces, t["step"], path, tex)
@@ -889,20 +986,27 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
         write_ply(path, v, faces.cpu().numpy(), m["normals"].cpu().numpy() if o["normals"] else None,
                   m["colors"].cpu().numpy() if o["colors"] else None)
     print("Mesh: %d vertices, %d faces%s at level %g -> %s" % (len(v), len(faces), _simplified(k, faces_in), o["level"], path))
+    refine = {} if o["refine"] is None else {"refine": o["refine"]}  # (what every later extract_mesh_attrs call passes on)
+    if refine:  # the unrefined file stands as it is; everything below works on the refined mesh
+        m = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"], o["normals"],
+                                      o["colors"], o["normal_source"], k if k >= 2 else 0, **refine)
+        verts, faces = m["verts"], m["faces"]
+        path = _write_refined(path, scene, verts, faces, m["normals"].cpu().numpy() if o["normals"] else None,
+                              m["colors"].cpu().numpy() if o["colors"] else None, dict(m["refine"]))
     tex = None
     if texture_options(cfg)["texture"] or check_options(cfg)["check"] or dist["distance"] or dist["distance_to"] is not None:
         from . import runtime
         step = runtime.host().grid_spec([float(x) for x in o["bbox_min"]], [float(x) for x in o["bbox_max"]], int(o["resolution"]))[0]
     if texture_options(cfg)["texture"]:  # the normals are computed for the texture whether or not the .ply carries them
         m = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"], True, False,
-                                      o["normal_source"], *((k,) if k >= 2 else ()))
+                                      o["normal_source"], *((k,) if k >= 2 or refine else ()), **refine)
         verts, faces = m["verts"], m["faces"]
         tex = _run_texture(runner, cfg, scene, verts, faces, m["normals"], step, path)
     if check_options(cfg)["check"]:
         _run_check(runner, cfg, scene, dataset, verts, faces, step, path, tex)
     if dist["distance"]:  # the same floater filter, extracted once more without the simplification (as the texture path re-extracts)
         full = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"], False, False,
-                                         o["normal_source"])
+                                         o["normal_source"], **({"simplify": 0, **refine} if refine else {}))
         _distance_in_world(cfg, scene, verts, faces, step, path, (full["verts"], full["faces"]))
     elif dist["distance_to"] is not None:
         _distance_in_world(cfg, scene, verts, faces, step, path)

@@ -1316,6 +1316,82 @@ int f2n_image_ssim(void* stream, int height, int width, int channels, const floa
                    int64_t* stats /*device [C][2]*/);
 void f2n_ssim_tile(int* tile_h /*host*/, int* tile_w /*host*/);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Mesh refinement (additive; the ABI version is unchanged): the vertex one-ring, Taubin smoothing, the projection of points onto a
+ * level set of ln(sigma), face quality.  No reference counterpart.  csrc/octree.hip.  Every fp32 and every fp64 operation below is ONE
+ * rounding, never an FMA; the kernels use + - * / sqrt only.  Every call returns F2N_ERR_INVALID_ARG for a negative size or a NULL
+ * pointer it needs, and F2N_OK without touching anything when it has no element to work on.
+ * ------------------------------------------------------------------------------------------------- */
+/* The one-ring of every vertex as a CSR.  A face is VALID if its three indices lie in [0, V) and are pairwise distinct; any other face
+ * contributes nothing.
+ * f2n_mesh_ring_keys: keys [F,6] int64.  A valid face (a, b, c) writes the directed edges a V + b, b V + a, b V + c, c V + b, c V + a,
+ *   a V + c (int64 products) in this order, any other face six times -1.  F <= (2^31 - 1) / 6.
+ * The caller sorts all keys ascending, drops the -1s and run-length encodes the rest (plumbing, not a kernel here): edge_keys [E] int64
+ *   = the distinct keys ascending, edge_uses [E] int64 = how often each occurs = the number of valid faces on the undirected edge
+ *   (a face holds an edge once, in both directions).  A sort makes the result independent of the order of the faces.
+ * f2n_mesh_ring_fill: one thread per vertex v.  ring_start_end [V,2] int32 = the range of edge_keys within [v V, (v + 1) V) (two binary
+ *   searches); ring [E] int32: ring[j] = edge_keys[j] - v V for j in that range -- the neighbours of v ascending, each once;
+ *   pinned [V] uint8 = 1 if the range is empty (no valid face uses v) or any edge of the range has edge_uses != 2 (v lies on a boundary
+ *   or non-manifold edge), else 0;  edge_counts [2] int32 on the DEVICE, zeroed by the call on `stream`: [0] = the undirected edges
+ *   with edge_uses == 1, [1] = those with edge_uses >= 3, each counted at its lower end (integer atomics: order-free).
+ * f2n_mesh_smooth: one pass, one thread per vertex, out_verts [V,3] != verts.  A vertex is COPIED THROUGH bit for bit if it is pinned,
+ *   its range is empty (or not within [0, n_ring]), one of its own coordinates is not finite, or a ring entry is outside [0, V) or
+ *   names a vertex with a coordinate that is not finite.  Otherwise per component, in fp64:  s = 0;  for j in ring order: s = s + (double) x_j;
+ *   m = s / (double) count;  d = m - (double) p;  t = factor * d;  out = (float) ((double) p + t).  factor is a finite double.
+ *   A Taubin lambda|mu pair is this call twice (lambda, then mu) between two buffers.
+ * f2n_mesh_move_clamp: the trust region, in place on pts [n,3] against p0 [n,3], fp32:  u_k = x_k - p0_k;
+ *   l = sqrt((u_x u_x + u_y u_y) + u_z u_z);  if l > max_move:  k = max_move / l;  x_k = p0_k + u_k * k.  Otherwise (a NaN l included) the
+ *   point keeps its bits.  The sums p0_k + u_k k round to the coordinates' own grid, which can leave x just outside the ball, so the
+ *   result is measured again and pulled in, at most F2N_MOVE_CLAMP_ROUNDS times in all:  w_k = x_k - p0_k;  lw = sqrt((w_x w_x + w_y w_y)
+ *   + w_z w_z);  lw > max_move:  k = (k * (max_move / lw)) * (1 - 2^-21);  x_k = p0_k + u_k * k again.  A round that ends with
+ *   lw <= max_move ends the loop: then |x - p0| <= max_move as fp32 measures it (within max_move (1 + 2^-22) exactly).  Where an ulp of
+ *   the coordinates is coarser than about max_move 2^-17 the rounds can run out with x one rounding outside.  max_move > 0 (+inf allowed). */
+#define F2N_MOVE_CLAMP_ROUNDS 16
+int f2n_mesh_ring_keys(void* stream, int n_verts, int n_faces, const int32_t* faces /*[F,3]*/, int64_t* keys /*[F,6]*/);
+int f2n_mesh_ring_fill(void* stream, int n_verts, int n_edges, const int64_t* edge_keys /*[E]*/, const int64_t* edge_uses /*[E]*/,
+                       int32_t* ring_start_end /*[V,2]*/, int32_t* ring /*[E]*/, uint8_t* pinned /*[V]*/, int32_t* edge_counts /*device [2]*/);
+int f2n_mesh_smooth(void* stream, int n_verts, int n_ring, const float* verts /*[V,3]*/, const int32_t* ring_start_end /*[V,2]*/,
+                    const int32_t* ring /*[E]*/, const uint8_t* pinned /*[V]*/, double factor, float* out_verts /*[V,3]*/);
+int f2n_mesh_move_clamp(void* stream, int n, const float* p0 /*[n,3]*/, float max_move, float* pts /*[n,3], in place*/);
+
+/* f2n_level_step: the per-iteration update of a damped Newton projection onto { h = 0 }, h(p) = ln sigma(p) - ln level, along
+ * grad h = grad sigma / sigma.  The caller evaluates the field; the kernel never takes a logarithm and keeps no state of its own.
+ * Per point i (one thread): p0 [n,3] the start;  cand [n,3] IN: the candidate c the caller just evaluated, OUT: the next one;
+ * sigma [n], grad [n,3], h [n]: the field at c and h_c = log(sigma_c) - log(level) as the caller formed it;  state, in/out:
+ * best [n,3] = b, h_best [n], g_best [n,3], scale [n] = a, status [n] int32 (bits below), evals [n] int32.  All fp32:
+ *   0. not first and status has EMPTY or CONVERGED:  cand = b;  nothing else changes.
+ *   1. g_k = grad_k / sigma (IEEE);  q = (g_x g_x + g_y g_y) + g_z g_z;  EVALUABLE = sigma > 0 and sigma, h_c, g_x, g_y, g_z finite
+ *      and q != 0.
+ *   2. first:  evals = 1;  b = c;  h_best = h_c;  a = 1;  status = 0;  g_best = g if EVALUABLE, else g_best = 0 and status = EMPTY
+ *      (the point never moves: b = c = where the caller started it).
+ *      not first:  evals = evals + 1;  ACCEPT = EVALUABLE and |h_c| <= |h_best|;  ACCEPT: b = c, h_best = h_c, g_best = g;
+ *      otherwise a = a * 0.5.
+ *   3. not EMPTY and |h_best| <= tol:  status |= CONVERGED.
+ *   4. EMPTY, CONVERGED or propose == 0:  cand = b.  Otherwise  q_b = (g_best_x^2 + g_best_y^2) + g_best_z^2;  t = -((a * h_best) / q_b);
+ *      d_k = t * g_best_k;  l = sqrt((d_x d_x + d_y d_y) + d_z d_z);  if l > max_step:  k = max_step / l, d_k = d_k * k,
+ *      status |= STEP_CLAMPED;  c'_k = b_k + d_k;  then the trust region of f2n_mesh_move_clamp on c' against p0 with max_move, which sets
+ *      MOVE_CLAMPED when it acts;  a c' with a coordinate that is not finite is replaced by b;  cand = c'.
+ * So b is always a position at which the caller evaluated the field, and |h_best| never grows.  The clamp bits are sticky: they say
+ * that a candidate of this point was clamped, not that the accepted one was.  tol >= 0, max_step > 0, max_move > 0 (+inf allowed). */
+#define F2N_LEVEL_EMPTY 1
+#define F2N_LEVEL_CONVERGED 2
+#define F2N_LEVEL_STEP_CLAMPED 4
+#define F2N_LEVEL_MOVE_CLAMPED 8
+int f2n_level_step(void* stream, int n, int first, int propose, const float* p0 /*[n,3]*/, const float* sigma /*[n]*/,
+                   const float* grad /*[n,3]*/, const float* h /*[n]*/, float tol, float max_step, float max_move, float* cand /*[n,3]*/,
+                   float* best /*[n,3]*/, float* h_best /*[n]*/, float* g_best /*[n,3]*/, float* scale /*[n]*/, int32_t* status /*[n]*/,
+                   int32_t* evals /*[n]*/);
+
+/* f2n_mesh_face_quality: quality [F] fp64 per face, from the fp32 coordinates in fp64:  p = B - A, q = C - A, r = C - B;
+ *   n = (p_y q_z - p_z q_y, p_z q_x - p_x q_z, p_x q_y - p_y q_x);  area2 = sqrt((n_x n_x + n_y n_y) + n_z n_z);
+ *   l1 = (p_x p_x + p_y p_y) + p_z p_z, l2 and l3 likewise of q and r;  L = (l1 + l2) + l3;
+ *   quality = L > 0 ? (K * area2) / L : 0, K = F2N_FACE_QUALITY_K = the double nearest 2 sqrt(3)  -- that is 4 sqrt(3) A / (sum of the
+ *   squared edge lengths): 1 for an equilateral face, towards 0 for a sliver.  0 for a face that is not VALID (above); NaN for a valid
+ *   face with a coordinate that is not finite. */
+#define F2N_FACE_QUALITY_K 3.4641016151377544
+int f2n_mesh_face_quality(void* stream, int n_verts, int n_faces, const float* verts /*[V,3]*/, const int32_t* faces /*[F,3]*/,
+                          double* quality /*[F]*/);
+
 #ifdef __cplusplus
 }
 #endif
