@@ -681,6 +681,20 @@ def field_bwd_dyn_rows(n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, loc
                                      _i(int(defer_reduce))), "f2n_field_bwd_dyn_rows")
 
 
+def field_bwd_dyn_planes(n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped, volume_idx,
+                         vol_stride, mlp_params_h, x_edge_h, x_edge_planes_h, x_planes_h, plane_rows, src_rows, dfeat, loss_scale,
+                         dparams_scaled, grad_table_h, level_entries, defer_reduce):
+    """f2n_field_bwd_dyn_planes: field_bwd_dyn_rows on the gather's f16 planes [8][plane_rows][4] -- x_planes_h is a contiguous view
+    that starts at the survivors' first row of plane 0; the edge rows from x_edge_h [n_off,32] or, when x_edge_planes_h (a view that
+    starts at the edge samples' first row of plane 0) is given, from the planes."""
+    _ck(lib().f2n_field_bwd_dyn_planes(_stream(), _i(n_max), _p(n_dev, "i32", True), _i(n_off), _i(n_volumes), _p(prim_pool, "i32"),
+                                       _p(local_idx, "i32"), _p(local_size, "i32"), _p(bias_pool, "f32"), _p(level_scale, "f32"),
+                                       _p(pts_warped, "f32"), _p(volume_idx, "i32"), _i(vol_stride), _p(mlp_params_h, "h16"),
+                                       _p(x_edge_h, "h16", True), _p(x_edge_planes_h, "h16", True), _p(x_planes_h, "h16"), _i(plane_rows),
+                                       _p(src_rows, "i32"), _p(dfeat, "f32"), _f(loss_scale), _p(dparams_scaled, "f32"),
+                                       _p(grad_table_h, "h16"), _i(level_entries), _i(int(defer_reduce))), "f2n_field_bwd_dyn_planes")
+
+
 class _StepTail(ctypes.Structure):
     _fields_ = [("n_flags_a", ctypes.c_int), ("flags_grad_a", ctypes.c_void_p), ("n_flags_b", ctypes.c_int), ("flags_grad_b", ctypes.c_void_p),
                 ("flags", ctypes.c_void_p), ("flags_mirror", ctypes.c_void_p), ("n_groups", ctypes.c_int), ("groups", ctypes.c_void_p),
@@ -693,11 +707,12 @@ class _StepTail(ctypes.Structure):
 def field_bwd_step_tail(n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped, volume_idx,
                         vol_stride, mlp_params_h, saved_x_h, dfeat, loss_scale, dparams_scaled, grad_table_h, level_entries, flags_a,
                         flags_b, flags, groups, table, step, lr, beta1, beta2, eps, tail_stream=None, flags_mirror=None, leave_table_to_caller=False,
-                        after_reduce=None, x_cache_h=None, src_rows=None):
+                        after_reduce=None, x_cache_h=None, src_rows=None, plane_rows=0, x_edge_planes_h=None):
     """f2n_field_bwd_step_tail: the field backward + the rest of the training step (deferred reductions, finiteness flags, Adam of
     `groups` (as adam_fused) and of `table` = {param, exp_avg, exp_avg_sq, param_h, grad_scale, n}) re-ordered around the scatter.
     Returns 1 when the scatter's owners stepped the table.  x_cache_h / src_rows given: f2n_field_bwd_step_tail_rows, with
-    saved_x_h as its x_edge_h (rows < n_off; None when n_off == 0) -- see field_bwd_dyn_rows."""
+    saved_x_h as its x_edge_h (rows < n_off; None when n_off == 0) -- see field_bwd_dyn_rows.  plane_rows > 0:
+    f2n_field_bwd_step_tail_planes, x_cache_h as its x_planes_h -- see field_bwd_dyn_planes."""
     arr = (_AdamGroup * max(len(groups), 1))()
     for a, g in zip(arr, groups):
         a.param = _p(g["param"], "f32").value
@@ -726,6 +741,15 @@ def field_bwd_step_tail(n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, lo
         t.after_reduce = ctypes.cast(cb, ctypes.c_void_p).value
     by_owners = ctypes.c_int(0)
     ts = ctypes.c_void_p(tail_stream.cuda_stream) if tail_stream is not None else ctypes.c_void_p(0)
+    if plane_rows > 0:
+        _ck(lib().f2n_field_bwd_step_tail_planes(_stream(), ts, _i(n_max), _p(n_dev, "i32", True), _i(n_off), _i(n_volumes), _p(prim_pool, "i32"),
+                                                 _p(local_idx, "i32"), _p(local_size, "i32"), _p(bias_pool, "f32"), _p(level_scale, "f32"),
+                                                 _p(pts_warped, "f32"), _p(volume_idx, "i32"), _i(vol_stride), _p(mlp_params_h, "h16"),
+                                                 _p(saved_x_h, "h16", True), _p(x_edge_planes_h, "h16", True), _p(x_cache_h, "h16"),
+                                                 _i(plane_rows), _p(src_rows, "i32"), _p(dfeat, "f32"), _f(loss_scale),
+                                                 _p(dparams_scaled, "f32"), _p(grad_table_h, "h16"), _i(level_entries), ctypes.byref(t),
+                                                 ctypes.byref(by_owners)), "f2n_field_bwd_step_tail_planes")
+        return by_owners.value
     if x_cache_h is not None:
         _ck(lib().f2n_field_bwd_step_tail_rows(_stream(), ts, _i(n_max), _p(n_dev, "i32", True), _i(n_off), _i(n_volumes), _p(prim_pool, "i32"),
                                                _p(local_idx, "i32"), _p(local_size, "i32"), _p(bias_pool, "f32"), _p(level_scale, "f32"),

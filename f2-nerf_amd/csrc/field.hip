@@ -1231,6 +1231,51 @@ __global__ __launch_bounds__(F2N_FWD_THREADS) void field_fwd_kernel(
   }
 }
 
+// The planes-fed MLP of the large-batch pre-pass (f2n_field_mlp_planes_ex) with its own loop: field_fwd_kernel<1, false, true>'s
+// fragments, chain, roundings and stores, but tile t + 1's two 8-byte plane loads are issued before tile t's MFMAs (as
+// f2n_field_shade_fwd_body, shade_bwd_kernel and f2n_field_bwd_body do); the last round re-reads its own tile.
+__global__ __launch_bounds__(F2N_FWD_THREADS) void field_mlp_planes_kernel(int n, const half_t* __restrict__ params,
+                                                                           const half_t* __restrict__ x_planes,
+                                                                           float* __restrict__ out_feat_f32, half_t* __restrict__ out_feat_h,
+                                                                           float* __restrict__ out_f0, half_t* __restrict__ save_x) {
+  F2N_RAISE_PRIO();
+  const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
+  F2nMlpFwdW<1> w;
+  w.load(params, c, g);
+  const int n_tiles = (n + 15) / 16;
+  const int wave_global = blockIdx.x * (F2N_FWD_THREADS / 64) + (tid >> 6);
+  const int wave_stride = gridDim.x * (F2N_FWD_THREADS / 64);
+  auto fetch = [&](int tile) {
+    const int s = tile * 16 + c;
+    const int sc = s < n ? s : n - 1;
+    return f2n_cat(*(const half4_t*) (x_planes + ((size_t) g * n + sc) * 4), *(const half4_t*) (x_planes + ((size_t) (4 + g) * n + sc) * 4));
+  };
+  if (wave_global >= n_tiles) return;
+  half8_t cur = fetch(wave_global);
+  for (int tile = wave_global; tile < n_tiles; tile += wave_stride) {
+    const half8_t nxt = fetch(tile + wave_stride < n_tiles ? tile + wave_stride : tile);
+    __builtin_amdgcn_sched_barrier(0);  // keep the loads up here; their s_waitcnt lands at the bottom of the round
+    const int s = tile * 16 + c;
+    const bool valid = s < n;
+    const half8_t xf = valid ? cur : half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+    if (save_x != nullptr && valid) f2n_store_xfrag_h(save_x, s, g, xf);
+    const float4_t o = w.forward(xf);  // lane (c = sample, g): outputs 4g..4g+3
+    if (valid) {
+      half4_t oh;
+      float4_t of;
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        oh[r] = (half_t) o[r];  // output precision is f16 (TCNNWP.cpp:143-144)
+        of[r] = (float) oh[r];
+      }
+      if (out_feat_f32 != nullptr) *(float4_t*) (out_feat_f32 + (size_t) s * F2N_D_OUT + 4 * g) = of;
+      if (out_feat_h != nullptr) *(half4_t*) (out_feat_h + (size_t) s * F2N_D_OUT + 4 * g) = oh;
+      if (out_f0 != nullptr && g == 0) out_f0[s] = of[0];
+    }
+    cur = nxt;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Backward: MLP backward (recompute + both orientations, mlp_dev.h) chained into the hash scatter.
 // One wave handles 16-sample tiles; the weight gradients contract a tile's 16 samples with K = 16 MFMAs
@@ -1249,7 +1294,13 @@ union F2nBwdSmem {
 // f16 planes + non-zero mask for the owner-binned scatter.  BPC = resident blocks per CU the register budget is cut for.
 // ROWS: the saved input is not a compact copy but the pre-pass feature cache read through a row index (f2n_field_bwd_dyn_rows):
 // row s >= n_off is x_cache row src_rows[s - n_off], row s < n_off (the edge samples in front) is x_h row s.
-template <int NH, int HASH, bool ROWS>
+// SRC (F2N_X_*): COMPACT = x_h / x_f32 rows; ROWS as above; PLANES = the cache is the gather's own f16 planes [8][plane_rows][4]
+// (f2n_field_bwd_dyn_planes): row s >= n_off is f2n_cat(plane g, plane 4 + g) at row src_rows[s - n_off] -- field_fwd_kernel's own
+// expression --, an edge row is x_h row s or, when x_edge_planes is given, the same planes form at row s of x_edge_planes.
+#define F2N_X_COMPACT 0
+#define F2N_X_ROWS 1
+#define F2N_X_PLANES 2
+template <int NH, int HASH, int SRC>
 __device__ __forceinline__ void f2n_field_bwd_body(
     int n, F2nHashArgs h, const int32_t* __restrict__ local_idx, const int32_t* __restrict__ local_size,
     const float* __restrict__ level_scale, const float* __restrict__ pts, int pts_are_warped,
@@ -1257,8 +1308,9 @@ __device__ __forceinline__ void f2n_field_bwd_body(
     const half_t* __restrict__ x_h, const float* __restrict__ x_f32, const float* __restrict__ dy, float loss_scale,
     float* __restrict__ dparams, float* __restrict__ dx_f32, half_t* __restrict__ grad_table, half_t* __restrict__ dx_planes,
     uint16_t* __restrict__ nz_mask, const int32_t* __restrict__ n_dev, int n_off, const half_t* __restrict__ x_cache,
-    const int32_t* __restrict__ src_rows) {
+    const int32_t* __restrict__ src_rows, const half_t* __restrict__ x_edge_planes, int plane_rows) {
   F2N_RAISE_PRIO();
+  constexpr bool ROWS = SRC != F2N_X_COMPACT;  // the saved input is read through the row index
   const int n_alloc = n;  // plane stride / mask words: the allocated row count
   if (n_dev != nullptr) n = min(n, *n_dev + n_off);  // the row count is still on the device (f2n_field_bwd_dyn)
   __shared__ F2nBwdSmem<NH> sm;
@@ -1289,7 +1341,13 @@ __device__ __forceinline__ void f2n_field_bwd_body(
   auto fetch = [&](int tile, int row, In& o) {
     const int s = tile * 16 + c;
     const int sc = s < n ? s : n - 1;
-    if (ROWS) o.xf = f2n_rowfrag(row >= 0 ? x_cache + (size_t) row * F2N_D_IN : x_h + (size_t) sc * F2N_D_IN, F2N_D_IN, 0, 0, g);
+    if (SRC == F2N_X_PLANES) {  // one address and one distance between the lane's two 8-byte pieces, whichever array holds the row
+      const bool in_planes = row >= 0 || x_edge_planes != nullptr;
+      const half_t* p = row >= 0                   ? x_cache + ((size_t) g * plane_rows + row) * 4
+                        : x_edge_planes != nullptr ? x_edge_planes + ((size_t) g * plane_rows + sc) * 4
+                                                   : x_h + (size_t) sc * F2N_D_IN + 4 * g;
+      o.xf = f2n_cat(*(const half4_t*) p, *(const half4_t*) (p + (in_planes ? (size_t) 16 * plane_rows : (size_t) 16)));
+    } else if (ROWS) o.xf = f2n_rowfrag(row >= 0 ? x_cache + (size_t) row * F2N_D_IN : x_h + (size_t) sc * F2N_D_IN, F2N_D_IN, 0, 0, g);
     else o.xf = (x_h != nullptr) ? f2n_load_xfrag_h(x_h, sc, g, true) : f2n_load_xfrag_f32(x_f32, sc, g, true);
     o.d4 = *(const float4_t*) (dy + (size_t) sc * F2N_D_OUT + 4 * g);
   };
@@ -1369,9 +1427,9 @@ __global__ __launch_bounds__(F2N_BWD_THREADS, BPC) void field_bwd_kernel(
     const half_t* __restrict__ x_h, const float* __restrict__ x_f32, const float* __restrict__ dy, float loss_scale,
     float* __restrict__ dparams, float* __restrict__ dx_f32, half_t* __restrict__ grad_table, half_t* __restrict__ dx_planes,
     uint16_t* __restrict__ nz_mask, const int32_t* __restrict__ n_dev, int n_off) {
-  f2n_field_bwd_body<NH, HASH, false>(n, h, local_idx, local_size, level_scale, pts, pts_are_warped, volume_idx, vol_stride, params, x_h,
-                                      x_f32, dy, loss_scale, dparams, dx_f32, grad_table, dx_planes, nz_mask, n_dev, n_off, nullptr,
-                                      nullptr);
+  f2n_field_bwd_body<NH, HASH, F2N_X_COMPACT>(n, h, local_idx, local_size, level_scale, pts, pts_are_warped, volume_idx, vol_stride, params,
+                                              x_h, x_f32, dy, loss_scale, dparams, dx_f32, grad_table, dx_planes, nz_mask, n_dev, n_off,
+                                              nullptr, nullptr, nullptr, 0);
 }
 
 // The streaming step's field backward on the pre-pass cache itself (no compact copy of the survivors' rows exists).
@@ -1383,9 +1441,25 @@ __global__ __launch_bounds__(F2N_BWD_THREADS, BPC) void field_bwd_rows_kernel(
     const half_t* __restrict__ x_edge, const half_t* __restrict__ x_cache, const int32_t* __restrict__ src_rows,
     const float* __restrict__ dy, float loss_scale, float* __restrict__ dparams, half_t* __restrict__ grad_table,
     half_t* __restrict__ dx_planes, uint16_t* __restrict__ nz_mask, const int32_t* __restrict__ n_dev, int n_off) {
-  f2n_field_bwd_body<1, HASH, true>(n, h, local_idx, local_size, level_scale, pts, pts_are_warped, volume_idx, vol_stride, params, x_edge,
-                                    nullptr, dy, loss_scale, dparams, nullptr, grad_table, dx_planes, nz_mask, n_dev, n_off, x_cache,
-                                    src_rows);
+  f2n_field_bwd_body<1, HASH, F2N_X_ROWS>(n, h, local_idx, local_size, level_scale, pts, pts_are_warped, volume_idx, vol_stride, params,
+                                          x_edge, nullptr, dy, loss_scale, dparams, nullptr, grad_table, dx_planes, nz_mask, n_dev, n_off,
+                                          x_cache, src_rows, nullptr, 0);
+}
+
+// The same on the gather's planes (the pre-pass of a streaming step keeps them instead of a row-major copy): x_planes is already
+// offset to the survivors' first row, x_edge_planes (optional) to the edge samples' first row; plane_rows is the planes' row count.
+template <int HASH, int BPC>
+__global__ __launch_bounds__(F2N_BWD_THREADS, BPC) void field_bwd_planes_kernel(
+    int n, F2nHashArgs h, const int32_t* __restrict__ local_idx, const int32_t* __restrict__ local_size,
+    const float* __restrict__ level_scale, const float* __restrict__ pts, int pts_are_warped,
+    const int32_t* __restrict__ volume_idx, int vol_stride, const half_t* __restrict__ params,
+    const half_t* __restrict__ x_edge, const half_t* __restrict__ x_edge_planes, const half_t* __restrict__ x_planes, int plane_rows,
+    const int32_t* __restrict__ src_rows, const float* __restrict__ dy, float loss_scale, float* __restrict__ dparams,
+    half_t* __restrict__ grad_table, half_t* __restrict__ dx_planes, uint16_t* __restrict__ nz_mask, const int32_t* __restrict__ n_dev,
+    int n_off) {
+  f2n_field_bwd_body<1, HASH, F2N_X_PLANES>(n, h, local_idx, local_size, level_scale, pts, pts_are_warped, volume_idx, vol_stride, params,
+                                            x_edge, nullptr, dy, loss_scale, dparams, nullptr, grad_table, dx_planes, nz_mask, n_dev, n_off,
+                                            x_planes, src_rows, x_edge_planes, plane_rows);
 }
 
 // Stand-alone hash scatter (seam-level f2n_hash_bwd): grad_in is h16 [n,32].
@@ -2061,11 +2135,8 @@ int f2n_field_mlp_planes_ex(void* stream, int n, const void* planes_h, const voi
                             void* save_x_h, void* out_feat_h) {
   if (n < 0 || (n > 0 && planes_h == nullptr)) return F2N_ERR_INVALID_ARG;
   if (n == 0) return F2N_OK;
-  F2nHashArgs h = {nullptr, nullptr, nullptr, 1};
-  hipLaunchKernelGGL((field_fwd_kernel<1, false, true>), dim3(f2n_wave_grid((n + 15) / 16, 4)), dim3(F2N_FWD_THREADS), 0,
-                     (hipStream_t) stream, n, h, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1, nullptr,
-                     (const half_t*) mlp_params_h, out_feat_f32, (half_t*) out_feat_h, out_f0, (half_t*) save_x_h, (const half_t*) planes_h,
-                     nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(field_mlp_planes_kernel, dim3(f2n_wave_grid((n + 15) / 16, 4)), dim3(F2N_FWD_THREADS), 0, (hipStream_t) stream, n,
+                     (const half_t*) mlp_params_h, (const half_t*) planes_h, out_feat_f32, (half_t*) out_feat_h, out_f0, (half_t*) save_x_h);
   return f2n_launch_status();
 }
 
@@ -2136,13 +2207,18 @@ static int f2n_field_bwd_impl(void* stream, void* tail_stream, int n_max, const 
                               const void* mlp_params_h, const void* saved_x_h, const float* dfeat, float loss_scale,
                               float* dparams_f32_scaled, void* grad_table_h, int level_entries, int defer_reduce,
                               const F2nStepTail* tail, int* table_stepped, const void* x_cache_h = nullptr,
-                              const int32_t* src_rows = nullptr) {
+                              const int32_t* src_rows = nullptr, const void* x_edge_planes_h = nullptr, int plane_rows = 0) {
   const int n = n_max;
   if (table_stepped != nullptr) *table_stepped = 0;
   if (n < 0 || n_volumes <= 0 || vol_stride < 1 || !(loss_scale > 0.f) || level_entries < 0 || ((uintptr_t) mlp_params_h & 15))
     return F2N_ERR_INVALID_ARG;
   // (the row-indexed input of the _rows entry points: edge rows [0, n_off) from saved_x_h, the rest through src_rows)
-  if (x_cache_h != nullptr && (src_rows == nullptr || n_off < 0 || n_off > n || (n_off > 0 && saved_x_h == nullptr))) return F2N_ERR_INVALID_ARG;
+  // (plane_rows > 0, the _planes entry points: x_cache_h is planes [8][plane_rows][4]; the edge rows from saved_x_h or x_edge_planes_h)
+  if (x_cache_h != nullptr && (src_rows == nullptr || n_off < 0 || n_off > n || (n_off > 0 && saved_x_h == nullptr && x_edge_planes_h == nullptr)))
+    return F2N_ERR_INVALID_ARG;
+  if (plane_rows < 0 || (plane_rows > 0 && (x_cache_h == nullptr || ((uintptr_t) x_cache_h & 7) || ((uintptr_t) x_edge_planes_h & 7))) ||
+      (plane_rows == 0 && x_edge_planes_h != nullptr))
+    return F2N_ERR_INVALID_ARG;
   if (tail != nullptr && (tail->flags == nullptr || tail->n_groups < 0 || tail->n_groups > 4 || tail->step < 1 || tail->n_table < 0 ||
                           (tail->n_table > 0 && (tail->table_param == nullptr || tail->table_exp_avg == nullptr ||
                                                  tail->table_exp_avg_sq == nullptr || tail->table_param_h == nullptr))))
@@ -2174,13 +2250,22 @@ static int f2n_field_bwd_impl(void* stream, void* tail_stream, int n_max, const 
                      local_idx, local_size, level_scale, pts_warped, 1, volume_idx, vol_stride, (const half_t*) mlp_params_h,  \
                      (const half_t*) saved_x_h, (const half_t*) x_cache_h, src_rows, dfeat, loss_scale, partials,             \
                      (half_t*) grad_table_h, dx_planes, nz_mask, n_dev, n_off)
-    if (x_cache_h != nullptr) {
+#define F2N_LAUNCH_FIELD_BWD_PLANES(HASH, BPC)                                                                                  \
+  hipLaunchKernelGGL((field_bwd_planes_kernel<HASH, BPC>), dim3(blocks), dim3(F2N_BWD_THREADS), 0, (hipStream_t) stream, n, h,  \
+                     local_idx, local_size, level_scale, pts_warped, 1, volume_idx, vol_stride, (const half_t*) mlp_params_h,   \
+                     (const half_t*) saved_x_h, (const half_t*) x_edge_planes_h, (const half_t*) x_cache_h, plane_rows, src_rows, \
+                     dfeat, loss_scale, partials, (half_t*) grad_table_h, dx_planes, nz_mask, n_dev, n_off)
+    if (plane_rows > 0) {
+      if (!bins) F2N_LAUNCH_FIELD_BWD_PLANES(1, 2);
+      else F2N_LAUNCH_FIELD_BWD_PLANES(2, 3);
+    } else if (x_cache_h != nullptr) {
       if (!bins) F2N_LAUNCH_FIELD_BWD_ROWS(1, 2);
       else F2N_LAUNCH_FIELD_BWD_ROWS(2, 3);
     } else if (!bins) F2N_LAUNCH_FIELD_BWD(1, 2);
     else F2N_LAUNCH_FIELD_BWD(2, 3);
 #undef F2N_LAUNCH_FIELD_BWD
 #undef F2N_LAUNCH_FIELD_BWD_ROWS
+#undef F2N_LAUNCH_FIELD_BWD_PLANES
     rc = f2n_launch_status();
     if (rc != F2N_OK) return rc;
     if (tail == nullptr && !defer_reduce) {
@@ -2297,6 +2382,30 @@ int f2n_field_bwd_step_tail_rows(void* stream, void* tail_stream, int n_max, con
   return f2n_field_bwd_impl(stream, tail_stream, n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_size, bias_pool, level_scale,
                             pts_warped, volume_idx, vol_stride, mlp_params_h, x_edge_h, dfeat, loss_scale, dparams_f32_scaled, grad_table_h,
                             level_entries, 1, tail, table_stepped_by_owners, x_cache_h, src_rows);
+}
+
+int f2n_field_bwd_dyn_planes(void* stream, int n_max, const int32_t* n_dev, int n_off, int n_volumes, const int32_t* prim_pool,
+                             const int32_t* local_idx, const int32_t* local_size, const float* bias_pool, const float* level_scale,
+                             const float* pts_warped, const int32_t* volume_idx, int vol_stride, const void* mlp_params_h,
+                             const void* x_edge_h, const void* x_edge_planes_h, const void* x_planes_h, int plane_rows,
+                             const int32_t* src_rows, const float* dfeat, float loss_scale, float* dparams_f32_scaled, void* grad_table_h,
+                             int level_entries, int defer_reduce) {
+  if (x_planes_h == nullptr || plane_rows < 1) return F2N_ERR_INVALID_ARG;
+  return f2n_field_bwd_impl(stream, nullptr, n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_size, bias_pool, level_scale, pts_warped,
+                            volume_idx, vol_stride, mlp_params_h, x_edge_h, dfeat, loss_scale, dparams_f32_scaled, grad_table_h, level_entries,
+                            defer_reduce, nullptr, nullptr, x_planes_h, src_rows, x_edge_planes_h, plane_rows);
+}
+
+int f2n_field_bwd_step_tail_planes(void* stream, void* tail_stream, int n_max, const int32_t* n_dev, int n_off, int n_volumes,
+                                   const int32_t* prim_pool, const int32_t* local_idx, const int32_t* local_size, const float* bias_pool,
+                                   const float* level_scale, const float* pts_warped, const int32_t* volume_idx, int vol_stride,
+                                   const void* mlp_params_h, const void* x_edge_h, const void* x_edge_planes_h, const void* x_planes_h,
+                                   int plane_rows, const int32_t* src_rows, const float* dfeat, float loss_scale, float* dparams_f32_scaled,
+                                   void* grad_table_h, int level_entries, const F2nStepTail* tail, int* table_stepped_by_owners) {
+  if (tail == nullptr || x_planes_h == nullptr || plane_rows < 1) return F2N_ERR_INVALID_ARG;
+  return f2n_field_bwd_impl(stream, tail_stream, n_max, n_dev, n_off, n_volumes, prim_pool, local_idx, local_size, bias_pool, level_scale,
+                            pts_warped, volume_idx, vol_stride, mlp_params_h, x_edge_h, dfeat, loss_scale, dparams_f32_scaled, grad_table_h,
+                            level_entries, 1, tail, table_stepped_by_owners, x_planes_h, src_rows, x_edge_planes_h, plane_rows);
 }
 
 }  // extern "C"

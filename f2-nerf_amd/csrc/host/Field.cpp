@@ -303,7 +303,8 @@ Tensor Hash3DAnchored::AnchoredQueryReuse(const Tensor& points, const Tensor& an
   return mlp_out_dim_ == F2N_MLP_OUT_PAD ? feat : feat.index({Slc(), Slc(0, mlp_out_dim_)}).contiguous();
 }
 
-Tensor Hash3DAnchored::QueryDensityPreAct(const Tensor& points, const Tensor& anchors, bool keep_features, bool keep_outputs) {
+Tensor Hash3DAnchored::QueryDensityPreAct(const Tensor& points, const Tensor& anchors, bool keep_features, bool keep_outputs,
+                                          bool keep_planes) {
   torch::NoGradGuard g;
   Tensor pts = points.contiguous();
   CheckDev(pts, torch::kFloat32, "points");
@@ -314,7 +315,7 @@ Tensor Hash3DAnchored::QueryDensityPreAct(const Tensor& points, const Tensor& an
     return mlp_->Query(HashEncode(pts, anchors)).select(1, 0).contiguous();
   }
   Tensor f0 = torch::empty({n}, DevF32());
-  prepass_x_ = keep_features ? torch::empty({n, N_LEVELS * N_CHANNELS}, DevF16()) : Tensor();
+  prepass_planes_ = Tensor();
   // (only a streaming train step asks for the outputs: every other caller allocates and stores nothing more than before)
   prepass_feat_h_ = keep_features && keep_outputs ? torch::empty({n, F2N_MLP_OUT_PAD}, DevF16()) : Tensor();
   void* feat_h = prepass_feat_h_.defined() ? VoidP(prepass_feat_h_) : nullptr;
@@ -326,6 +327,9 @@ Tensor Hash3DAnchored::QueryDensityPreAct(const Tensor& points, const Tensor& an
 #else
   constexpr bool force_fused = false;  // (measured to lose at every training size: profiles/r04_fused_gather_ab.txt)
 #endif
+  // the gather's planes serve as the feature cache where they exist: the row-major copy is then neither allocated nor written
+  const bool planes_cache = keep_planes && keep_features && keep_outputs && !force_fused && n >= 32768;
+  prepass_x_ = keep_features && !planes_cache ? torch::empty({n, N_LEVELS * N_CHANNELS}, DevF16()) : Tensor();
   if (force_fused) {
     F2N_TIMED_CALL("field_prepass_fused", f2n_field_fwd_fused_ex(CurStream(), n, n_volumes_, VoidP(feat_pool_h_), I32P(prim_pool_),
                            I32P(feat_local_idx_), I32P(feat_local_size_), F32P(bias_pool_), F32P(level_scale_), F32P(pts), I32P(av.t),
@@ -362,7 +366,8 @@ Tensor Hash3DAnchored::QueryDensityPreAct(const Tensor& points, const Tensor& an
                              I32P(av.t), av.stride, VoidP(planes), balance_gather_ ? step01 : 0.f, level_scale_host_.data()));
     }
     F2N_TIMED_CALL("field_mlp_prepass", f2n_field_mlp_planes_ex(CurStream(), n, VoidP(planes), VoidP(mlp_->params_h_), nullptr, F32P(f0),
-                           keep_features ? VoidP(prepass_x_) : nullptr, feat_h));
+                           prepass_x_.defined() ? VoidP(prepass_x_) : nullptr, feat_h));
+    if (planes_cache) prepass_planes_ = planes;
   } else {
     F2N_TIMED_CALL("field_prepass", f2n_field_fwd_ex(CurStream(), n, n_volumes_, VoidP(feat_pool_h_), I32P(prim_pool_), I32P(feat_local_idx_),
                            I32P(feat_local_size_), F32P(bias_pool_), F32P(level_scale_), F32P(pts), I32P(av.t), av.stride,

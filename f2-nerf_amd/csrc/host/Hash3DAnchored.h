@@ -18,8 +18,12 @@ class Hash3DAnchored : public Field {
   // keep_features: also keep the gathered h16 hash features [n,32] of every point for AnchoredQueryReuse
   // keep_outputs (with keep_features): also keep the network's 16 f16 outputs [n,16] of every point (prepass_feat_h_) -- a
   // streaming train step's grad pass starts its colour path from them instead of evaluating the network again
-  Tensor QueryDensityPreAct(const Tensor& points, const Tensor& anchors, bool keep_features = false, bool keep_outputs = false);
-  void DropPrepassCache() { prepass_x_ = Tensor(); prepass_feat_h_ = Tensor(); }
+  // keep_planes (with keep_outputs; a streaming train step alone passes it): on the large-batch route the gathered features stay in
+  // the form the gather wrote them, f16 planes [8][n][4] (prepass_planes_), and no row-major copy is written -- prepass_x_ is then
+  // undefined; every other route keeps prepass_x_ as before
+  Tensor QueryDensityPreAct(const Tensor& points, const Tensor& anchors, bool keep_features = false, bool keep_outputs = false,
+                            bool keep_planes = false);
+  void DropPrepassCache() { prepass_x_ = Tensor(); prepass_feat_h_ = Tensor(); prepass_planes_ = Tensor(); }
   // AnchoredQuery whose first n_reuse points are points src_rows[i] of the preceding QueryDensityPreAct (same table,
   // same coordinates): their 128 gathers are not repeated.  Bit-identical to AnchoredQuery(points, anchors).
   Tensor AnchoredQueryReuse(const Tensor& points, const Tensor& anchors, const Tensor& src_rows, int n_reuse);
@@ -58,6 +62,7 @@ class Hash3DAnchored : public Field {
   bool grad_clean_ = false;  // grad_h_ is known to be all zero
   Tensor prepass_x_;       // h16 [n,32] features of the last QueryDensityPreAct(keep_features = true), or undefined
   Tensor prepass_feat_h_;  // h16 [n,16] field outputs of the same rows (keep_outputs), or undefined; lives and dies with prepass_x_
+  Tensor prepass_planes_;  // h16 [8,n,4] the same features as the gather's planes (keep_planes) IN PLACE of prepass_x_, or undefined
   std::unique_ptr<FusedMLP> mlp_;
   int n_volumes_;
   std::vector<float> level_scale_host_;  // the 16 level scales again, for the gather's cost model (host side)

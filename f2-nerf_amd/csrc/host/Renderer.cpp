@@ -390,7 +390,8 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
         DigestTap(TAP_DT_PRE, sample_result_.dt);
         DigestTap(TAP_ANCHORS_PRE, sample_result_.anchors.select(1, 0));
       }
-      f0_full = field->QueryDensityPreAct(pts_full, anchors_full, /*keep_features=*/true, /*keep_outputs=*/keep_prepass_outputs_);
+      f0_full = field->QueryDensityPreAct(pts_full, anchors_full, /*keep_features=*/true, /*keep_outputs=*/keep_prepass_outputs_,
+                                          /*keep_planes=*/keep_prepass_outputs_ && prepass_planes_cache_);
       f0p = F32P(f0_full) + front;
       if (digest_taps_ && train) DigestTap(TAP_EDGE, pts_full.narrow(0, 0, front));
       fr.edge_cache_row = 0;
@@ -403,7 +404,8 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
         DigestTap(TAP_DT_PRE, sample_result_.dt);
         DigestTap(TAP_ANCHORS_PRE, sample_result_.anchors.select(1, 0));
       }
-      f0_full = field->QueryDensityPreAct(sample_result_.pts, sample_result_.anchors, /*keep_features=*/true, /*keep_outputs=*/keep_prepass_outputs_);
+      f0_full = field->QueryDensityPreAct(sample_result_.pts, sample_result_.anchors, /*keep_features=*/true, /*keep_outputs=*/keep_prepass_outputs_,
+                                          /*keep_planes=*/keep_prepass_outputs_ && prepass_planes_cache_);
       f0p = F32P(f0_full);
     }
     if (digest_taps_ && train) {

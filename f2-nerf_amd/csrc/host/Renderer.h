@@ -398,6 +398,10 @@ class Renderer : public Pipe {
   // pre-pass feature cache through the survivors' row index instead of a copy (ExpRunner.prepass_feat_reuse; false = the
   // field_shade_fwd / compact field_x path, bit-identical results).  Host-side and data-independent.
   bool prepass_feat_reuse_ = true;
+  // With reuse, a large-batch pre-pass keeps its hash features as the gather's own planes (Hash3DAnchored::prepass_planes_) and
+  // writes no row-major copy; the field backward reads the planes (f2n_field_bwd_*_planes).  ExpRunner.prepass_planes_cache;
+  // false = the row cache and the _rows calls, bit-identical results.
+  bool prepass_planes_cache_ = true;
   bool keep_prepass_outputs_ = false;  // TrainForwardBackward -> SampleAndFilter: this pre-pass is a streaming train step's
   int64_t n_feat_reuse_steps_ = 0;     // steps that took the reuse path (tests: the knob is inert where it must be)
   bool count_pending_ = false;
@@ -413,7 +417,7 @@ class Renderer : public Pipe {
   // feature cache kept); the caller flushes a streaming step first (ExpRunner::FinishPending).
   // Every point query below is the same four steps (helpers at the top of RendererQuery.cpp): locate; LocatedRows = the non-empty
   // points compacted into rows, whose count is the query's one read-back; the query's own field calls on the rows, under a
-  // PrepassCacheGuard that puts Hash3DAnchored::prepass_x_ back on every exit path, an exception included; its own scatter kernel.
+  // PrepassCacheGuard that puts Hash3DAnchored's three pre-pass caches back on every exit path, an exception included; its own scatter kernel.
   Tensor QueryDensity(const Tensor& world);
   Tensor DensityGrid(const std::vector<float>& lo, const std::vector<float>& hi, int res);
   std::tuple<Tensor, Tensor> ExtractMesh(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level);

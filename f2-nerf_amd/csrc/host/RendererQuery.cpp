@@ -45,14 +45,15 @@ struct LocatedRows {
 
 // The side-effect contract of every query: a batch sampled ahead may still be served from the pre-pass feature cache, so whatever a
 // query's field calls make of Hash3DAnchored::prepass_x_ -- and of prepass_feat_h_, the field outputs of the same rows that a
-// streaming train step keeps beside it -- is undone when the guard goes out of scope -- by return or by exception.
+// streaming train step keeps beside it, and of prepass_planes_, the form that step keeps the features in -- is undone when the guard goes out of scope -- by return or by exception.
 struct PrepassCacheGuard {
   Hash3DAnchored* field;
-  Tensor kept, kept_feat_h;
-  explicit PrepassCacheGuard(Hash3DAnchored* f) : field(f), kept(f->prepass_x_), kept_feat_h(f->prepass_feat_h_) {}
+  Tensor kept, kept_feat_h, kept_planes;
+  explicit PrepassCacheGuard(Hash3DAnchored* f) : field(f), kept(f->prepass_x_), kept_feat_h(f->prepass_feat_h_), kept_planes(f->prepass_planes_) {}
   ~PrepassCacheGuard() {
     field->prepass_x_ = kept;
     field->prepass_feat_h_ = kept_feat_h;
+    field->prepass_planes_ = kept_planes;
   }
 };
 

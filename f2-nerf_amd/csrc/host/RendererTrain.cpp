@@ -60,12 +60,14 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
   // ---- forward ----
   Tensor feat = torch::empty({fr.dyn ? std::max(2 * n_edge, 1) : n, F2N_MLP_OUT_PAD}, DevF32());
   // reuse (Renderer.h: prepass_feat_reuse_): the pre-pass of this step kept the field network's outputs beside its hash features
-  const bool reuse = fr.dyn && field->prepass_feat_h_.defined() && field->prepass_x_.defined();
+  // -- as rows [n,32] or, from a large-batch pre-pass, as the gather's planes [8][n][4] (prepass_planes_cache_)
+  const bool planes = fr.dyn && field->prepass_feat_h_.defined() && field->prepass_planes_.defined();
+  const bool reuse = fr.dyn && field->prepass_feat_h_.defined() && (field->prepass_x_.defined() || planes);
   const bool edges_ride = fr.dyn && n_edge > 0 && fr.edge_cache_row >= 0;  // the edge samples' hash features are in the pre-pass cache too
   // the field backward's input rows: a compact copy -- or, with reuse, the cache itself (only edge samples that did not go through
   // the pre-pass keep their 2E rows here)
   Tensor field_x = torch::empty({reuse ? (edges_ride ? 0 : 2 * n_edge) : n, N_LEVELS * N_CHANNELS}, DevF16());
-  Tensor x_cache, feat_h_cache;  // the two pre-pass caches, held until the backward that reads them has been queued
+  Tensor x_cache, feat_h_cache;  // the two pre-pass caches (x_cache: rows or planes), held until the backward that reads them has been queued
   // the density pre-activations of the surviving samples also leave as a compact array: compositing then reads 4 B per
   // sample instead of one 64-byte line of `feat` per sample, and its backward writes a compact d f0 that the colour
   // backward merges into the dfeat rows it writes anyway (column 0 written in place was a read-modify-write of every line)
@@ -77,16 +79,15 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
     // pre-pass of this step kept (reuse), or a second evaluation on the cached hash features in the same launch.  Their `feat` rows
     // are never written (only the 2E edge rows of `feat` exist: the TV loss reads them); the synchronous path below keeps the two
     // separate kernels and is what tests compare this with
-    TORCH_CHECK(field->prepass_x_.defined(), "no pre-pass feature cache for this query");
+    TORCH_CHECK(field->prepass_x_.defined() || planes, "no pre-pass feature cache for this query");
     if (n_edge > 0 && !edges_ride)
       F2N_TIMED_CALL("field_fwd", f2n_field_fwd(st, 2 * n_edge, field->n_volumes_, VoidP(field->feat_pool_h_), I32P(field->prim_pool_),
                              I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
                              F32P(field->level_scale_), F32P(fr.pts_all), I32P(fr.vol_all), 1, VoidP(field->mlp_->params_h_),
                              F32P(feat), nullptr, VoidP(field_x)));
-    const at::Half* cache = field->prepass_x_.data_ptr<at::Half>();
     const int64_t row = (int64_t) N_LEVELS * N_CHANNELS;
     if (reuse) {
-      x_cache = field->prepass_x_;
+      x_cache = planes ? field->prepass_planes_ : field->prepass_x_;
       feat_h_cache = field->prepass_feat_h_;
       n_feat_reuse_steps_++;
       const at::Half* fh = feat_h_cache.data_ptr<at::Half>();
@@ -98,6 +99,7 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
                              edges_ride ? static_cast<const void*>(fh + (int64_t) F2N_MLP_OUT_PAD * fr.edge_cache_row) : nullptr,
                              edges_ride ? F32P(feat) : nullptr));
     } else {
+      const at::Half* cache = field->prepass_x_.data_ptr<at::Half>();
       // survivors: field MLP -> colour path; edge samples (when cached): field MLP only, fp32 rows for the TV loss -- one launch
       F2N_TIMED_CALL("field_shade_fwd", f2n_field_shade_fwd_extra(st, n_kept, n_dev, I32P(fr.src_rows),
                              static_cast<const void*>(cache + row * fr.sample_cache_row), VoidP(field->mlp_->params_h_), F32P(es.dirs),
@@ -158,10 +160,23 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
   const bool fused_tail = fr.dyn && step_tail_builder_ && !digest_taps_ && step_tail_builder_(&tail);
   // reuse: rows [0, 2E) = the edge samples (their cache rows, or the small field_x), rows [2E, ..) = cache rows through src_rows
   const int64_t xrow = (int64_t) N_LEVELS * N_CHANNELS;
+  // (planes: a row is 4 halves of each plane, so the same two offsets in rows move the plane base by 4 halves per row)
+  const int64_t xstep = planes ? 4 : xrow;
   const void* x_edge = !reuse || n_edge == 0 ? nullptr
-                       : edges_ride ? static_cast<const void*>(x_cache.data_ptr<at::Half>() + xrow * fr.edge_cache_row) : VoidP(field_x);
-  const void* x_surv = reuse ? static_cast<const void*>(x_cache.data_ptr<at::Half>() + xrow * fr.sample_cache_row) : nullptr;
-  if (fused_tail && reuse) {
+                       : edges_ride ? static_cast<const void*>(x_cache.data_ptr<at::Half>() + xstep * fr.edge_cache_row) : VoidP(field_x);
+  const void* x_surv = reuse ? static_cast<const void*>(x_cache.data_ptr<at::Half>() + xstep * fr.sample_cache_row) : nullptr;
+  const int plane_rows = planes ? (int) x_cache.size(1) : 0;
+  const bool edge_in_planes = planes && n_edge > 0 && edges_ride;
+  if (fused_tail && planes) {
+    field->grad_clean_ = false;
+    F2N_TIMED_CALL("field_bwd", f2n_field_bwd_step_tail_planes(st, TailStream()->stream(), n, n_dev, 2 * n_edge, field->n_volumes_, I32P(field->prim_pool_),
+                           I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
+                           F32P(field->level_scale_), F32P(fr.pts_all), I32P(fr.vol_all), 1, VoidP(field->mlp_->params_h_),
+                           edge_in_planes ? nullptr : x_edge, edge_in_planes ? x_edge : nullptr, x_surv, plane_rows, I32P(fr.src_rows),
+                           F32P(dfeat), field->mlp_->loss_scale_, F32P(field->mlp_->grad_scaled_), VoidP(field->grad_h_),
+                           field->pool_size_ / N_LEVELS, &tail, nullptr));
+    step_tail_done_ = true;
+  } else if (fused_tail && reuse) {
     field->grad_clean_ = false;
     F2N_TIMED_CALL("field_bwd", f2n_field_bwd_step_tail_rows(st, TailStream()->stream(), n, n_dev, 2 * n_edge, field->n_volumes_, I32P(field->prim_pool_),
                            I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
@@ -179,6 +194,15 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
                            VoidP(field_x), F32P(dfeat), field->mlp_->loss_scale_, F32P(field->mlp_->grad_scaled_),
                            VoidP(field->grad_h_), field->pool_size_ / N_LEVELS, &tail, nullptr));
     step_tail_done_ = true;
+  } else if (planes) {
+    field->grad_clean_ = false;
+    F2N_TIMED_CALL("field_bwd", f2n_field_bwd_dyn_planes(st, n, n_dev, 2 * n_edge, field->n_volumes_, I32P(field->prim_pool_),
+                           I32P(field->feat_local_idx_), I32P(field->feat_local_size_), F32P(field->bias_pool_),
+                           F32P(field->level_scale_), F32P(fr.pts_all), I32P(fr.vol_all), 1, VoidP(field->mlp_->params_h_),
+                           edge_in_planes ? nullptr : x_edge, edge_in_planes ? x_edge : nullptr, x_surv, plane_rows, I32P(fr.src_rows),
+                           F32P(dfeat), field->mlp_->loss_scale_, F32P(field->mlp_->grad_scaled_), VoidP(field->grad_h_),
+                           field->pool_size_ / N_LEVELS, /*defer_reduce=*/1));
+    F2N_TIMED_CALL("reduce_partials", f2n_reduce_deferred(st));
   } else if (reuse) {
     field->grad_clean_ = false;
     F2N_TIMED_CALL("field_bwd", f2n_field_bwd_dyn_rows(st, n, n_dev, 2 * n_edge, field->n_volumes_, I32P(field->prim_pool_),

@@ -499,6 +499,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              Tensor none = torch::empty({0}, torch::kFloat16);
              return std::vector<Tensor>{f->prepass_x_.defined() ? f->prepass_x_ : none, f->prepass_feat_h_.defined() ? f->prepass_feat_h_ : none};
            })
+      // the third cache, which a streaming train step's pre-pass keeps in place of the rows: density_prepass_planes runs
+      // QueryDensityPreAct(keep_features, keep_outputs, keep_planes), prepass_planes returns h16 [8,n,4] or an empty tensor
+      .def("density_prepass_planes",
+           [](ExpRunner& r, const Tensor& warped, const Tensor& anchors) {
+             py::gil_scoped_release no_gil;
+             r.FinishPending();
+             return FieldOf(r)->QueryDensityPreAct(warped, anchors, /*keep_features=*/true, /*keep_outputs=*/true, /*keep_planes=*/true);
+           },
+           py::arg("warped"), py::arg("anchors"))
+      .def("prepass_planes",
+           [](ExpRunner& r) {
+             auto* f = FieldOf(r);
+             return f->prepass_planes_.defined() ? f->prepass_planes_ : torch::empty({0}, torch::kFloat16);
+           })
       .def("density_grid",  // [nz, ny, nx] densities on the grid of grid_spec(lo, hi, res)
            [](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res) {
              py::gil_scoped_release no_gil;
@@ -753,6 +767,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_property("prepass_feat_reuse",  // streaming steps: grad pass from the pre-pass's field outputs, field backward on the cache rows (A/B: False = field_shade_fwd + field_x copy)
                     [](ExpRunner& r) { return r.renderer_->prepass_feat_reuse_; },
                     [](ExpRunner& r, bool on) { r.renderer_->prepass_feat_reuse_ = on; })
+      .def_property("prepass_planes_cache",  // with reuse: the pre-pass keeps the gather's planes as its feature cache, no row copy (A/B: False = rows, the _rows calls)
+                    [](ExpRunner& r) { return r.renderer_->prepass_planes_cache_; },
+                    [](ExpRunner& r, bool on) { r.renderer_->prepass_planes_cache_ = on; })
       .def_property_readonly("prepass_reuse_steps", [](ExpRunner& r) { return r.renderer_->n_feat_reuse_steps_; })  // steps that took that path
       .def_readwrite("spec_start_without_event", &ExpRunner::spec_start_without_event_)
       .def_readwrite("draws_off_main", &ExpRunner::draws_off_main_)  // ExpRunner::Train's batch draws on the tail stream (A/B: False = main queue)

@@ -808,6 +808,31 @@ int f2n_field_bwd_step_tail_rows(void* stream, void* tail_stream /* or NULL */, 
                                  const void* mlp_params_h, const void* x_edge_h, const void* x_cache_h, const int32_t* src_rows,
                                  const float* dfeat, float loss_scale, float* dparams_f32_scaled, void* grad_table_h, int level_entries,
                                  const F2nStepTail* tail, int* table_stepped_by_owners /* out, or NULL */);
+/* ---------------------------------------------------------------------------------------------------
+ * The gather's planes as the pre-pass cache (same ABI version: additions only).  The large-batch pre-pass gathers the hash features
+ * as h16 planes [8][plane_rows][4] (f2n_hash_gather_planes_*: plane p holds features 4p..4p+3 of every row); with save_x_h = NULL
+ * f2n_field_mlp_planes_ex writes no row-major copy of them, and the field backward of the same step reads the planes themselves.
+ *   f2n_field_bwd_dyn_planes / f2n_field_bwd_step_tail_planes: the _rows calls with a different saved input.  x_planes_h is the
+ *     plane base ALREADY offset to the survivors' first row (by 4 halves per row), plane_rows the row count of one plane: row
+ *     s >= n_off is the 8 halves at ((g * plane_rows + src_rows[s - n_off]) * 4) followed by the 8 halves at
+ *     (((4 + g) * plane_rows + src_rows[s - n_off]) * 4), g = 0..3 -- the pre-pass MLP's own read of that row.  Row s < n_off is
+ *     row s of x_edge_h [n_off,32] as in the _rows calls, or -- x_edge_planes_h not NULL: the same planes offset to the edge
+ *     samples' first row -- row s of those planes (x_edge_h is then ignored).  Both bases are 8-byte aligned.  Everything behind
+ *     the load is the _rows calls' code: same weight gradients, dL/dx planes, mask words and gradient table.
+ * ------------------------------------------------------------------------------------------------- */
+int f2n_field_bwd_dyn_planes(void* stream, int n_max, const int32_t* n_dev, int n_off, int n_volumes, const int32_t* prim_pool,
+                             const int32_t* local_idx, const int32_t* local_size, const float* bias_pool, const float* level_scale,
+                             const float* pts_warped, const int32_t* volume_idx, int vol_stride, const void* mlp_params_h,
+                             const void* x_edge_h /* or NULL */, const void* x_edge_planes_h /* or NULL */, const void* x_planes_h,
+                             int plane_rows, const int32_t* src_rows, const float* dfeat, float loss_scale, float* dparams_f32_scaled,
+                             void* grad_table_h, int level_entries, int defer_reduce);
+int f2n_field_bwd_step_tail_planes(void* stream, void* tail_stream /* or NULL */, int n_max, const int32_t* n_dev, int n_off, int n_volumes,
+                                   const int32_t* prim_pool, const int32_t* local_idx, const int32_t* local_size, const float* bias_pool,
+                                   const float* level_scale, const float* pts_warped, const int32_t* volume_idx, int vol_stride,
+                                   const void* mlp_params_h, const void* x_edge_h /* or NULL */, const void* x_edge_planes_h /* or NULL */,
+                                   const void* x_planes_h, int plane_rows, const int32_t* src_rows, const float* dfeat, float loss_scale,
+                                   float* dparams_f32_scaled, void* grad_table_h, int level_entries, const F2nStepTail* tail,
+                                   int* table_stepped_by_owners /* out, or NULL */);
 /* h16 gradient table produced by f2n_hash_bwd / f2n_field_bwd (true gradient = float(grad_h) * grad_scale,
  * grad_scale = 1/128): fuses the fp16->fp32 cast, the /128 (Hash3DAnchored.cu:232), Adam, the fp32->fp16
  * refresh of the table (Hash3DAnchored.cu:186) and the re-zeroing of the gradient (:222) in one pass. */
