@@ -77,6 +77,12 @@ def debug_counters(reset=False):
     return [int(v) for v in out]
 
 
+def set_scatter_producer(variant):
+    """Which producer kernel the owner-binned hash-gradient scatter launches from now on, process-wide (f2n_set_scatter_producer):
+    1 = hash constants staged in LDS (the default), 0 = the previous kernel.  Same gradient table either way."""
+    _ck(lib().f2n_set_scatter_producer(_i(variant)), "f2n_set_scatter_producer")
+
+
 def _debug_only(name):
     if not hasattr(lib(), name):
         raise RuntimeError("%s exists in the debug variant of the library only (include/f2n_debug.h): set F2N_DEBUG_BUILD=1 before "

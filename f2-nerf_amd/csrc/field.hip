@@ -878,6 +878,186 @@ __global__ __launch_bounds__(256) void hash_bin_kernel(int n, int chunk, F2nHash
   }
 }
 
+// The producers again (f2n_set_scatter_producer: this one is the default, hash_bin_kernel stays reachable as variant 0).  Same
+// records into the same segments -- only the slot a record takes inside its segment can differ (fewer blocks share a CU and take
+// their slots in another order), which the owners' exact sums do not see.  What differs: the level's hash constants
+// [V][prim xyz, bias xyz] sit in (dynamic) LDS, as the gather's (hash_gather_planes_kernel<STAGED>), so a tile's cell lookup does
+// not wait for six global loads that can only start once the prefetched transform index has landed; they are fetched into
+// registers at the block's very start and written to LDS behind the rest of the prologue.  With the 24 V bytes on top of the
+// 37 KB of static LDS three blocks share a CU instead of four -- measured, that is the better residency for this kernel (fewer
+// blocks' scattered record stores in flight; more blocks, from an index list sized for the launch, were slower): the launch asks
+// for at least F2N_BIN_LDS_FLOOR bytes so that the residency does not depend on V.  DESIGN.md section 3 / 7.3,
+// profiles/scatter_producers.txt.  More than F2N_BIN_STAGE_BUDGET bytes of constants: f2n_binned_scatter launches hash_bin_kernel.
+#define F2N_BIN_STAGE_BUDGET 12288  // bytes of hash constants (24 per transform) a producer block stages: 6 x 256 words of each pool
+#define F2N_BIN_LDS_FLOOR 5120      // 37080 B static + this > 160 KiB / 4
+
+template <bool OVF>
+__global__ __launch_bounds__(256) void hash_bin_staged_kernel(int n, int chunk, F2nHashArgs h, const int32_t* __restrict__ local_idx,
+                                                              const int32_t* __restrict__ local_size,
+                                                              const float* __restrict__ level_scale, const float* __restrict__ pts,
+                                                              int pts_are_warped, const int32_t* __restrict__ volume_idx, int vol_stride,
+                                                              const half_t* __restrict__ gx, long gx_sample_stride,
+                                                              long gx_pair_stride, const uint16_t* __restrict__ nz_mask,
+                                                              F2nBinQueues q, half_t* __restrict__ grad_table,
+                                                              const int32_t* __restrict__ n_dev, int n_off) {
+  F2N_RAISE_PRIO();
+  if (n_dev != nullptr) n = min(n, *n_dev + n_off);  // the row count is still on the device
+  const int l = blockIdx.x % F2N_N_LEVELS, B = blockIdx.x / F2N_N_LEVELS;
+  const int nb = f2n_bin_nb(n, q.nb_force);
+  if (B >= nb) return;  // (block-uniform, before any barrier)
+  chunk = (((n + nb - 1) / nb) + 255) & ~255;  // split what there really is over the producer blocks in use
+  const int cap_nb = q.cap * (F2N_BIN_NB / nb);
+  __shared__ F2nLevelTab lt;
+  __shared__ int s_cnt[F2N_BIN_MAX_BINS];
+  __shared__ uint16_t s_idx[F2N_BIN_MAX_CHUNK];  // offsets (inside the chunk) of the samples with a non-zero gradient
+  __shared__ int s_wave_tot[4], s_n_nz, s_ovf;
+  extern __shared__ uint32_t pb_lds[];  // [V][prim xyz, bias xyz] of level l
+  const int tid = threadIdx.x, c = tid & 15;
+  // the level's 3 V + 3 V constants: every load in flight at once (3 V <= 6 x 256: F2N_BIN_STAGE_BUDGET)
+  uint32_t pool_p[6], pool_b[6];
+#pragma unroll
+  for (int u = 0; u < 6; u++) {
+    const int i = tid + 256 * u;
+    if (i < 3 * h.n_volumes) {
+      pool_p[u] = (uint32_t) h.prim_pool[3 * (size_t) l * h.n_volumes + i];
+      pool_b[u] = __float_as_uint(h.bias_pool[3 * (size_t) l * h.n_volumes + i]);
+    }
+  }
+  f2n_level_tab_fill(lt, level_scale, local_idx, local_size, tid);
+  for (int i = tid; i < q.n_bins; i += 256) s_cnt[i] = 0;
+#pragma unroll
+  for (int u = 0; u < 6; u++) {
+    const int i = tid + 256 * u, r = i / 3, k = i - 3 * r;
+    if (i < 3 * h.n_volumes) {
+      pb_lds[6 * r + k] = pool_p[u];
+      pb_lds[6 * r + 3 + k] = pool_b[u];
+    }
+  }
+  if (tid == 0) s_ovf = 0;
+  __syncthreads();
+  const int s_begin = B * chunk, s_end = min(n, s_begin + chunk);
+  const half_t* gl = gx + (size_t) (l >> 1) * gx_pair_stride + 2 * (l & 1);
+  half2_t* tab = (half2_t*) (grad_table + lt.base[l]);
+  // segment (l, bin, B) = my_rec + bin * bin_stride
+  uint2* my_rec = q.producer_major ? q.rec + ((size_t) l * nb + B) * q.n_bins * cap_nb : q.rec + ((size_t) l * q.n_bins * nb + B) * cap_nb;
+  const size_t bin_stride = q.producer_major ? (size_t) cap_nb : (size_t) nb * cap_nb;
+  // the samples with a non-zero gradient, in order (as hash_bin_kernel)
+  int n_nz = s_end - s_begin;
+  if (nz_mask != nullptr && n_nz > 0) {
+    if (tid == 0) s_n_nz = 0;
+    __syncthreads();
+    const int n_words = (s_end - s_begin + 15) / 16;  // s_begin is a multiple of 256
+    for (int w0 = 0; w0 < n_words; w0 += 256) {
+      const int w = w0 + tid;
+      unsigned m = w < n_words ? nz_mask[s_begin / 16 + w] : 0u;
+      if (w < n_words && s_begin + 16 * w + 16 > s_end) m &= (1u << (s_end - s_begin - 16 * w)) - 1u;
+      const int cnt = __popc(m);
+      int incl = cnt;  // block-wide exclusive prefix of the popcounts
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(incl, off);
+        if ((tid & 63) >= off) incl += up;
+      }
+      if ((tid & 63) == 63) s_wave_tot[tid >> 6] = incl;
+      __syncthreads();
+      int base = s_n_nz;
+      for (int k = 0; k < (tid >> 6); k++) base += s_wave_tot[k];
+      int dst = base + incl - cnt;
+      while (m) {
+        const int b = __ffs(m) - 1;
+        m &= m - 1u;
+        s_idx[dst++] = (uint16_t) (16 * w + b);
+      }
+      __syncthreads();
+      if (tid == 255) s_n_nz = base + incl;
+      __syncthreads();
+    }
+    n_nz = s_n_nz;
+  }
+  // one record {entry index inside the level, packed f16 pair} to its segment: slot from the LDS counter, full segment -> overflow list
+  auto append = [&](uint32_t pos, uint32_t bits) {
+    const int bin = (int) (pos >> F2N_BIN_SHIFT);
+#if F2N_DEBUG_BUILD
+    if ((q.dissect & 3) == 2) {
+      if ((pos ^ bits) == 0x12345u) s_cnt[bin] = 1;  // (keeps the record's operands alive)
+      return;
+    }
+#endif
+    const int slot = atomicAdd(&s_cnt[bin], 1);
+#if F2N_DEBUG_BUILD
+    if ((q.dissect & 3) == 1) {
+      if (((unsigned) slot ^ pos ^ bits) == 0x12345u) s_cnt[bin] = 1;
+      return;
+    }
+#endif
+    if (slot < cap_nb) {
+      uint2 r;
+      r.x = pos & (F2N_BIN_ENTRIES - 1);
+      r.y = bits;
+      my_rec[(uint32_t) bin * (uint32_t) bin_stride + (uint32_t) slot] = r;  // (a segment index inside the block's region fits 32 bits)
+    } else {
+      const int os = OVF ? atomicAdd(&s_ovf, 1) : F2N_BIN_OVF_CAP;
+      if (OVF && os < F2N_BIN_OVF_CAP) {
+        q.ovf_rec[((size_t) l * F2N_BIN_NB + B) * F2N_BIN_OVF_CAP + os] = uint2{pos, bits};
+      } else {  // (an overflow list full as well: the one order-dependent addition that is left, counted)
+        atomicAdd(&f2n_dbg_counters[0], 1);
+        __builtin_amdgcn_global_atomic_fadd_v2f16((__attribute__((address_space(1))) half2_t*) (tab + pos), __builtin_bit_cast(half2_t, bits));
+      }
+    }
+  };
+  // software pipeline: the next tile's gradient pair, point and transform index are in flight while this tile is hashed and appended
+  struct Tile {
+    half2_t gpair;
+    float p[3];
+    int vol;
+  };
+  auto load_tile = [&](int i0, Tile& t) {
+    const int i = min(i0 + tid, n_nz - 1);
+    const int sc = s_begin + (nz_mask != nullptr ? (int) s_idx[i] : i);
+    t.gpair = *(const half2_t*) (gl + (size_t) sc * gx_sample_stride);
+#pragma unroll
+    for (int k = 0; k < 3; k++) t.p[k] = pts[3 * (size_t) sc + k];
+    t.vol = volume_idx[(size_t) sc * vol_stride];
+  };
+  Tile cur, nxt;
+  if (n_nz > 0) load_tile(0, cur);
+  for (int i0 = 0; i0 < n_nz; i0 += 256) {
+    if (i0 + 256 < n_nz) load_tile(i0 + 256, nxt);
+    const bool valid = i0 + tid < n_nz;
+    const float g0 = valid ? (float) cur.gpair[0] : 0.f, g1 = valid ? (float) cur.gpair[1] : 0.f;
+    if (__ballot(g0 != 0.f || g1 != 0.f) != 0ull) {  // Hash3DAnchored.cu:149, wave-uniform
+      float p01[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) p01[k] = pts_are_warped ? (cur.p[k] + 1.f) * .5f : cur.p[k];
+      const int vol = cur.vol;
+      F2nCell cell;
+      const uint32_t* row = pb_lds + 6 * vol;
+      const int32_t prim3[3] = {(int32_t) row[0], (int32_t) row[1], (int32_t) row[2]};
+      const float bias3[3] = {__uint_as_float(row[3]), __uint_as_float(row[4]), __uint_as_float(row[5])};
+      f2n_hash_cell(p01, lt.scale[l], prim3, bias3, lt.size[l], cell);
+      float v[16];
+      if (f2n_combine_runs(cell, vol, c, g0, g1, v)) {
+#pragma unroll
+        for (int d = 0; d < 8; d++) {
+          const half2_t val = {(half_t) v[2 * d], (half_t) v[2 * d + 1]};
+          const uint32_t bits = __builtin_bit_cast(uint32_t, val);
+          if ((bits & 0x7fff7fffu) != 0u) append(cell.pos[d], bits);  // not (+-0, +-0)
+        }
+      }
+    }
+    cur = nxt;
+  }
+  __syncthreads();
+  for (int i = tid; i < q.n_bins; i += 256) q.cnt[((size_t) l * q.n_bins + i) * nb + B] = min(s_cnt[i], cap_nb);
+  if (OVF && tid == 0) {
+    q.ovf_cnt[l * F2N_BIN_NB + B] = min(s_ovf, F2N_BIN_OVF_CAP);
+    if (s_ovf > 0) {
+      q.ovf_any[l] = q.stamp;  // (every writer of a launch stores the same value)
+      atomicAdd(&f2n_dbg_counters[3], min(s_ovf, F2N_BIN_OVF_CAP));
+    }
+  }
+}
+
 // ADAM (round 6; f2n_field_bwd_step_tail): the owner does not write its slice's sums to the gradient table for a streaming
 // optimiser pass behind the step -- it steps the slice's parameters itself (adam_fused_kernel's table arithmetic, element for
 // element: gradient = the f16 value the table WOULD hold; widening, / 128, Adam, f16 refresh) and leaves the gradient table zero.
@@ -1697,6 +1877,14 @@ struct F2nBucketHook {
 };
 static F2nBucketHook g_bucket_hook[16];
 
+// f2n_set_scatter_producer: 0 = hash_bin_kernel, 1 = hash_bin_staged_kernel (profiles/scatter_producers.txt)
+static std::atomic<int> g_scatter_producer{1};
+int f2n_set_scatter_producer(int variant) {
+  if (variant != 0 && variant != 1) return F2N_ERR_INVALID_ARG;
+  g_scatter_producer.store(variant);
+  return F2N_OK;
+}
+
 // Owner-binned scatter of f16 gradients gx (pair (l, ch) of sample s at gx[s*ss + (l>>1)*ps + 2*(l&1) + ch]).
 static int f2n_binned_scatter(hipStream_t st, int n, const F2nHashArgs& h, const int32_t* local_idx, const int32_t* local_size,
                               const float* level_scale, const float* pts, int warped, const int32_t* volume_idx, int vol_stride,
@@ -1749,7 +1937,24 @@ static int f2n_binned_scatter(hipStream_t st, int n, const F2nHashArgs& h, const
   static std::atomic<int> g_scatter_stamp{0};
   q.stamp = (g_scatter_stamp.fetch_add(1) & 0x3fffffff) + 1;  // (the workspace starts out zeroed: never a launch's stamp)
   const bool ovf = level_entries > (1 << 19);  // (see hash_bin_kernel)
-  if (ovf)
+  // f2n_set_scatter_producer; a pool of more transforms than a block stages keeps the previous producer (its global loads)
+  const bool staged = g_scatter_producer.load() != 0 && 24 * (size_t) h.n_volumes <= F2N_BIN_STAGE_BUDGET;
+  size_t lds = staged ? 24 * (size_t) h.n_volumes : 0;
+  if (staged && lds < F2N_BIN_LDS_FLOOR) lds = F2N_BIN_LDS_FLOOR;
+#if F2N_DEBUG_BUILD  // measurement knob: more dynamic LDS, i.e. fewer producer blocks per CU
+  static const int lds_pad = []() {
+    const char* e = getenv("F2N_BIN_LDS_PAD");
+    return e != nullptr ? atoi(e) : 0;
+  }();
+  if (staged && lds_pad > 0 && lds + (size_t) lds_pad <= 27000) lds += (size_t) lds_pad;  // (with the static 37 KB: inside 64 KB)
+#endif
+  if (staged && ovf)
+    hipLaunchKernelGGL(hash_bin_staged_kernel<true>, dim3(F2N_N_LEVELS * F2N_BIN_NB), dim3(256), lds, st, n, chunk, h, local_idx, local_size,
+                       level_scale, pts, warped, volume_idx, vol_stride, gx, ss, ps, nz_mask, q, grad_table, n_dev, n_off);
+  else if (staged)
+    hipLaunchKernelGGL(hash_bin_staged_kernel<false>, dim3(F2N_N_LEVELS * F2N_BIN_NB), dim3(256), lds, st, n, chunk, h, local_idx, local_size,
+                       level_scale, pts, warped, volume_idx, vol_stride, gx, ss, ps, nz_mask, q, grad_table, n_dev, n_off);
+  else if (ovf)
     hipLaunchKernelGGL(hash_bin_kernel<true>, dim3(F2N_N_LEVELS * F2N_BIN_NB), dim3(256), 0, st, n, chunk, h, local_idx, local_size,
                        level_scale, pts, warped, volume_idx, vol_stride, gx, ss, ps, nz_mask, q, grad_table, n_dev, n_off);
   else

@@ -17,6 +17,8 @@ Hash3DAnchored* FieldOf(ExpRunner& r) { return static_cast<Hash3DAnchored*>(r.re
 SHShader* ShaderOf(ExpRunner& r) { return static_cast<SHShader*>(r.renderer_->shader_.get()); }
 PersSampler* SamplerOf(ExpRunner& r) { return static_cast<PersSampler*>(r.renderer_->pts_sampler_.get()); }
 
+int g_scatter_producer = 1;  // what f2n_set_scatter_producer was last given (the library keeps it per process, not per runner)
+
 // the runner in validation mode for the length of an inference call (as ExpRunner::RenderGeometry), put back on every exit path
 struct InferenceMode {
   GlobalDataPool* gdp;
@@ -771,6 +773,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                     [](ExpRunner& r) { return r.renderer_->prepass_planes_cache_; },
                     [](ExpRunner& r, bool on) { r.renderer_->prepass_planes_cache_ = on; })
       .def_property_readonly("prepass_reuse_steps", [](ExpRunner& r) { return r.renderer_->n_feat_reuse_steps_; })  // steps that took that path
+      .def_property("scatter_producer",  // f2n_set_scatter_producer: 1 = hash constants in LDS (default), 0 = the previous producer kernel (A/B knob; per process)
+                    [](ExpRunner&) { return g_scatter_producer; },
+                    [](ExpRunner&, int variant) {
+                      if (f2n_set_scatter_producer(variant) != F2N_OK) throw std::invalid_argument("scatter_producer: 0 or 1");
+                      g_scatter_producer = variant;
+                    })
       .def_readwrite("spec_start_without_event", &ExpRunner::spec_start_without_event_)
       .def_readwrite("draws_off_main", &ExpRunner::draws_off_main_)  // ExpRunner::Train's batch draws on the tail stream (A/B: False = main queue)
       .def_readwrite("exact_flag_order", &ExpRunner::exact_flag_order_)  // the step's tail inside the field backward's call (A/B: False = separate launches)
