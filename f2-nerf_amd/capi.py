@@ -78,8 +78,8 @@ def debug_counters(reset=False):
 
 
 def set_scatter_producer(variant):
-    """Which producer kernel the owner-binned hash-gradient scatter launches from now on, process-wide (f2n_set_scatter_producer):
-    1 = hash constants staged in LDS (the default), 0 = the previous kernel.  Same gradient table either way."""
+    """Which instantiation of the producer kernel the owner-binned hash-gradient scatter launches from now on, process-wide
+    (f2n_set_scatter_producer): 1 = staged, hash constants in LDS (the default), 0 = non-staged.  Same gradient table either way."""
     _ck(lib().f2n_set_scatter_producer(_i(variant)), "f2n_set_scatter_producer")
 
 

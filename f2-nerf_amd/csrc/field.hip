@@ -714,10 +714,24 @@ struct F2nBinQueues {
   int producer_major;  // record layout: 1 = [level][chunk][slice][slot] (a producer block's 128 segments contiguous), 0 = [level][slice][chunk][slot] (an owner's, rounds 1-5)
 };
 
-// OVF: with overflow lists (F2nBinQueues) -- tables of more than 2^19 entries per level, where segments do fill up (f2n_binned_scatter picks the instantiation); the
-// benched 2^19 tables keep the code without them (their trainings never filled a segment, and the lists' code, cold as it is, cost the
-// converged step ~5 us: 0.678-0.682 against 0.667-0.674 ms).
-template <bool OVF>
+// The producers.  f2n_binned_scatter picks the instantiation.
+// OVF: with overflow lists (F2nBinQueues) -- tables of more than 2^19 entries per level, where segments do fill up; the benched 2^19
+// tables keep the code without them (their trainings never filled a segment, and the lists' code, cold as it is, cost the converged
+// step ~5 us: 0.678-0.682 against 0.667-0.674 ms).
+// STAGED (the default, f2n_set_scatter_producer): the level's hash constants [V][prim xyz, bias xyz] sit in (dynamic) LDS, as the
+// gather's (hash_gather_planes_kernel<STAGED>), so a tile's cell lookup does not wait for six global loads that can only start once
+// the prefetched transform index has landed; they are fetched into registers at the block's very start and written to LDS behind the
+// rest of the prologue.  With the 24 V bytes on top of the 37 KB of static LDS three blocks share a CU instead of four -- measured,
+// that is the better residency for this kernel (fewer blocks' scattered record stores in flight; more blocks, from an index list
+// sized for the launch, were slower): the launch asks for at least F2N_BIN_LDS_FLOOR bytes so that the residency does not depend on
+// V.  DESIGN.md section 3 / 7.3, profiles/scatter_producers.txt.  The non-staged instantiation (variant 0, and any pool of more than
+// F2N_BIN_STAGE_BUDGET bytes of constants) reads them from the global pools, four blocks to a CU.  Both put the same records into the
+// same segments -- only the slot a record takes inside its segment can differ (the blocks that share a CU take their slots in
+// another order), which the owners' exact sums do not see.
+#define F2N_BIN_STAGE_BUDGET 12288  // bytes of hash constants (24 per transform) a producer block stages: 6 x 256 words of each pool
+#define F2N_BIN_LDS_FLOOR 5120      // 37080 B static + this > 160 KiB / 4
+
+template <bool OVF, bool STAGED>
 __global__ __launch_bounds__(256) void hash_bin_kernel(int n, int chunk, F2nHashArgs h, const int32_t* __restrict__ local_idx,
                                                        const int32_t* __restrict__ local_size,
                                                        const float* __restrict__ level_scale, const float* __restrict__ pts,
@@ -737,188 +751,14 @@ __global__ __launch_bounds__(256) void hash_bin_kernel(int n, int chunk, F2nHash
   __shared__ int s_cnt[F2N_BIN_MAX_BINS];
   __shared__ uint16_t s_idx[F2N_BIN_MAX_CHUNK];  // offsets (inside the chunk) of the samples with a non-zero gradient
   __shared__ int s_wave_tot[4], s_n_nz, s_ovf;
+  extern __shared__ uint32_t pb_lds[];  // STAGED: [V][prim xyz, bias xyz] of level l
   const int tid = threadIdx.x, c = tid & 15;
-  f2n_level_tab_fill(lt, level_scale, local_idx, local_size, tid);
-  for (int i = tid; i < q.n_bins; i += 256) s_cnt[i] = 0;
-  if (tid == 0) s_ovf = 0;
-  __syncthreads();
-  const int s_begin = B * chunk, s_end = min(n, s_begin + chunk);
-  const half_t* gl = gx + (size_t) (l >> 1) * gx_pair_stride + 2 * (l & 1);
-  half2_t* tab = (half2_t*) (grad_table + lt.base[l]);
-  // segment (l, bin, B) = my_rec + bin * bin_stride
-  uint2* my_rec = q.producer_major ? q.rec + ((size_t) l * nb + B) * q.n_bins * cap_nb : q.rec + ((size_t) l * q.n_bins * nb + B) * cap_nb;
-  const size_t bin_stride = q.producer_major ? (size_t) cap_nb : (size_t) nb * cap_nb;
-  // Samples whose whole f16 gradient is zero (most of them while the loss-scaled gradients sit at the f16 underflow
-  // boundary) are dropped up front: nz_mask has one bit per sample (16-sample words, written by the MLP backward).
-  // Order is preserved, so runs of equal cells stay adjacent.
-  int n_nz = s_end - s_begin;
-  if (nz_mask != nullptr && n_nz > 0) {
-    if (tid == 0) s_n_nz = 0;
-    __syncthreads();
-    const int n_words = (s_end - s_begin + 15) / 16;  // s_begin is a multiple of 256
-    for (int w0 = 0; w0 < n_words; w0 += 256) {
-      const int w = w0 + tid;
-      unsigned m = w < n_words ? nz_mask[s_begin / 16 + w] : 0u;
-      if (w < n_words && s_begin + 16 * w + 16 > s_end) m &= (1u << (s_end - s_begin - 16 * w)) - 1u;
-      const int cnt = __popc(m);
-      int incl = cnt;  // block-wide exclusive prefix of the popcounts
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off);
-        if ((tid & 63) >= off) incl += up;
-      }
-      if ((tid & 63) == 63) s_wave_tot[tid >> 6] = incl;
-      __syncthreads();
-      int base = s_n_nz;
-      for (int k = 0; k < (tid >> 6); k++) base += s_wave_tot[k];
-      int dst = base + incl - cnt;
-      while (m) {
-        const int b = __ffs(m) - 1;
-        m &= m - 1u;
-        s_idx[dst++] = (uint16_t) (16 * w + b);
-      }
-      __syncthreads();
-      if (tid == 255) s_n_nz = base + incl;
-      __syncthreads();
-    }
-    n_nz = s_n_nz;
-  }
-  // software pipeline: the next tile's gradient pair, point and transform index are in flight while this tile is
-  // hashed and appended (three dependent HBM round trips per tile otherwise)
-  struct Tile {
-    half2_t gpair;
-    float p[3];
-    int vol;
-  };
-  auto load_tile = [&](int i0, Tile& t) {
-    const int i = min(i0 + tid, n_nz - 1);
-    const int sc = s_begin + (nz_mask != nullptr ? (int) s_idx[i] : i);
-    t.gpair = *(const half2_t*) (gl + (size_t) sc * gx_sample_stride);
-#pragma unroll
-    for (int k = 0; k < 3; k++) t.p[k] = pts[3 * (size_t) sc + k];
-    t.vol = volume_idx[(size_t) sc * vol_stride];
-  };
-  Tile cur, nxt;
-  if (n_nz > 0) load_tile(0, cur);
-  for (int i0 = 0; i0 < n_nz; i0 += 256) {
-    if (i0 + 256 < n_nz) load_tile(i0 + 256, nxt);
-    const bool valid = i0 + tid < n_nz;
-    const float g0 = valid ? (float) cur.gpair[0] : 0.f, g1 = valid ? (float) cur.gpair[1] : 0.f;
-    if (__ballot(g0 != 0.f || g1 != 0.f) != 0ull) {  // Hash3DAnchored.cu:149, wave-uniform
-      float p01[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) p01[k] = pts_are_warped ? (cur.p[k] + 1.f) * .5f : cur.p[k];
-      const int vol = cur.vol;
-      const int tf = l * h.n_volumes + vol;
-      F2nCell cell;
-      f2n_hash_cell(p01, lt.scale[l], h.prim_pool + 3 * tf, h.bias_pool + 3 * tf, lt.size[l], cell);
-      float v[16];
-      if (f2n_combine_runs(cell, vol, c, g0, g1, v)) {
-#pragma unroll
-        for (int d = 0; d < 8; d++) {
-          const half2_t val = {(half_t) v[2 * d], (half_t) v[2 * d + 1]};
-          const uint32_t bits = __builtin_bit_cast(uint32_t, val);
-          if ((bits & 0x7fff7fffu) != 0u) {  // not (+-0, +-0)
-            const uint32_t pos = cell.pos[d];
-            const int bin = (int) (pos >> F2N_BIN_SHIFT);
-#if F2N_DEBUG_BUILD
-            if ((q.dissect & 3) == 2) {
-              if ((pos ^ bits) == 0x12345u) s_cnt[bin] = 1;  // (keeps the record's operands alive)
-              continue;
-            }
-#endif
-            const int slot = atomicAdd(&s_cnt[bin], 1);
-#if F2N_DEBUG_BUILD
-            if ((q.dissect & 3) == 1) {
-              if (((unsigned) slot ^ pos ^ bits) == 0x12345u) s_cnt[bin] = 1;
-              continue;
-            }
-            if (q.dissect & 8) {  // half the bytes, as many stores: 4-byte "records" 4 bytes apart
-              if (slot < cap_nb) ((uint32_t*) (my_rec + (size_t) bin * bin_stride))[slot] = bits ^ pos;
-              continue;
-            }
-            if (q.dissect & 16) {  // 6-byte records 6 bytes apart, as three 2-byte stores
-              if (slot < cap_nb) {
-                uint16_t* r6 = (uint16_t*) (my_rec + (size_t) bin * bin_stride) + 3 * (size_t) slot;
-                r6[0] = (uint16_t) (pos & (F2N_BIN_ENTRIES - 1));
-                r6[1] = (uint16_t) bits;
-                r6[2] = (uint16_t) (bits >> 16);
-              }
-              continue;
-            }
-#endif
-            if (slot < cap_nb) {
-              uint2 r;
-              r.x = pos & (F2N_BIN_ENTRIES - 1);
-              r.y = bits;
-              my_rec[(uint32_t) bin * (uint32_t) bin_stride + (uint32_t) slot] = r;  // (a segment index inside the block's region fits 32 bits: one scalar base, one vector offset)
-            } else {
-              const int os = OVF ? atomicAdd(&s_ovf, 1) : F2N_BIN_OVF_CAP;
-              if (OVF && os < F2N_BIN_OVF_CAP) {
-                q.ovf_rec[((size_t) l * F2N_BIN_NB + B) * F2N_BIN_OVF_CAP + os] = uint2{pos, bits};
-              } else {  // (an overflow list full as well: the one order-dependent addition that is left, counted)
-                atomicAdd(&f2n_dbg_counters[0], 1);
-                __builtin_amdgcn_global_atomic_fadd_v2f16((__attribute__((address_space(1))) half2_t*) (tab + pos), val);
-              }
-            }
-          }
-        }
-      }
-    }
-    cur = nxt;
-  }
-  __syncthreads();
-  for (int i = tid; i < q.n_bins; i += 256) q.cnt[((size_t) l * q.n_bins + i) * nb + B] = min(s_cnt[i], cap_nb);
-  if (OVF && tid == 0) {
-    q.ovf_cnt[l * F2N_BIN_NB + B] = min(s_ovf, F2N_BIN_OVF_CAP);
-    if (s_ovf > 0) {
-      q.ovf_any[l] = q.stamp;  // (every writer of a launch stores the same value)
-      atomicAdd(&f2n_dbg_counters[3], min(s_ovf, F2N_BIN_OVF_CAP));
-    }
-  }
-}
-
-// The producers again (f2n_set_scatter_producer: this one is the default, hash_bin_kernel stays reachable as variant 0).  Same
-// records into the same segments -- only the slot a record takes inside its segment can differ (fewer blocks share a CU and take
-// their slots in another order), which the owners' exact sums do not see.  What differs: the level's hash constants
-// [V][prim xyz, bias xyz] sit in (dynamic) LDS, as the gather's (hash_gather_planes_kernel<STAGED>), so a tile's cell lookup does
-// not wait for six global loads that can only start once the prefetched transform index has landed; they are fetched into
-// registers at the block's very start and written to LDS behind the rest of the prologue.  With the 24 V bytes on top of the
-// 37 KB of static LDS three blocks share a CU instead of four -- measured, that is the better residency for this kernel (fewer
-// blocks' scattered record stores in flight; more blocks, from an index list sized for the launch, were slower): the launch asks
-// for at least F2N_BIN_LDS_FLOOR bytes so that the residency does not depend on V.  DESIGN.md section 3 / 7.3,
-// profiles/scatter_producers.txt.  More than F2N_BIN_STAGE_BUDGET bytes of constants: f2n_binned_scatter launches hash_bin_kernel.
-#define F2N_BIN_STAGE_BUDGET 12288  // bytes of hash constants (24 per transform) a producer block stages: 6 x 256 words of each pool
-#define F2N_BIN_LDS_FLOOR 5120      // 37080 B static + this > 160 KiB / 4
-
-template <bool OVF>
-__global__ __launch_bounds__(256) void hash_bin_staged_kernel(int n, int chunk, F2nHashArgs h, const int32_t* __restrict__ local_idx,
-                                                              const int32_t* __restrict__ local_size,
-                                                              const float* __restrict__ level_scale, const float* __restrict__ pts,
-                                                              int pts_are_warped, const int32_t* __restrict__ volume_idx, int vol_stride,
-                                                              const half_t* __restrict__ gx, long gx_sample_stride,
-                                                              long gx_pair_stride, const uint16_t* __restrict__ nz_mask,
-                                                              F2nBinQueues q, half_t* __restrict__ grad_table,
-                                                              const int32_t* __restrict__ n_dev, int n_off) {
-  F2N_RAISE_PRIO();
-  if (n_dev != nullptr) n = min(n, *n_dev + n_off);  // the row count is still on the device
-  const int l = blockIdx.x % F2N_N_LEVELS, B = blockIdx.x / F2N_N_LEVELS;
-  const int nb = f2n_bin_nb(n, q.nb_force);
-  if (B >= nb) return;  // (block-uniform, before any barrier)
-  chunk = (((n + nb - 1) / nb) + 255) & ~255;  // split what there really is over the producer blocks in use
-  const int cap_nb = q.cap * (F2N_BIN_NB / nb);
-  __shared__ F2nLevelTab lt;
-  __shared__ int s_cnt[F2N_BIN_MAX_BINS];
-  __shared__ uint16_t s_idx[F2N_BIN_MAX_CHUNK];  // offsets (inside the chunk) of the samples with a non-zero gradient
-  __shared__ int s_wave_tot[4], s_n_nz, s_ovf;
-  extern __shared__ uint32_t pb_lds[];  // [V][prim xyz, bias xyz] of level l
-  const int tid = threadIdx.x, c = tid & 15;
-  // the level's 3 V + 3 V constants: every load in flight at once (3 V <= 6 x 256: F2N_BIN_STAGE_BUDGET)
+  // STAGED: the level's 3 V + 3 V constants, every load in flight at once (3 V <= 6 x 256: F2N_BIN_STAGE_BUDGET)
   uint32_t pool_p[6], pool_b[6];
 #pragma unroll
   for (int u = 0; u < 6; u++) {
     const int i = tid + 256 * u;
-    if (i < 3 * h.n_volumes) {
+    if (STAGED && i < 3 * h.n_volumes) {
       pool_p[u] = (uint32_t) h.prim_pool[3 * (size_t) l * h.n_volumes + i];
       pool_b[u] = __float_as_uint(h.bias_pool[3 * (size_t) l * h.n_volumes + i]);
     }
@@ -928,7 +768,7 @@ __global__ __launch_bounds__(256) void hash_bin_staged_kernel(int n, int chunk, 
 #pragma unroll
   for (int u = 0; u < 6; u++) {
     const int i = tid + 256 * u, r = i / 3, k = i - 3 * r;
-    if (i < 3 * h.n_volumes) {
+    if (STAGED && i < 3 * h.n_volumes) {
       pb_lds[6 * r + k] = pool_p[u];
       pb_lds[6 * r + 3 + k] = pool_b[u];
     }
@@ -941,7 +781,9 @@ __global__ __launch_bounds__(256) void hash_bin_staged_kernel(int n, int chunk, 
   // segment (l, bin, B) = my_rec + bin * bin_stride
   uint2* my_rec = q.producer_major ? q.rec + ((size_t) l * nb + B) * q.n_bins * cap_nb : q.rec + ((size_t) l * q.n_bins * nb + B) * cap_nb;
   const size_t bin_stride = q.producer_major ? (size_t) cap_nb : (size_t) nb * cap_nb;
-  // the samples with a non-zero gradient, in order (as hash_bin_kernel)
+  // Samples whose whole f16 gradient is zero (most of them while the loss-scaled gradients sit at the f16 underflow
+  // boundary) are dropped up front: nz_mask has one bit per sample (16-sample words, written by the MLP backward).
+  // Order is preserved, so runs of equal cells stay adjacent.
   int n_nz = s_end - s_begin;
   if (nz_mask != nullptr && n_nz > 0) {
     if (tid == 0) s_n_nz = 0;
@@ -989,12 +831,25 @@ __global__ __launch_bounds__(256) void hash_bin_staged_kernel(int n, int chunk, 
       if (((unsigned) slot ^ pos ^ bits) == 0x12345u) s_cnt[bin] = 1;
       return;
     }
+    if (q.dissect & 8) {  // half the bytes, as many stores: 4-byte "records" 4 bytes apart
+      if (slot < cap_nb) ((uint32_t*) (my_rec + (size_t) bin * bin_stride))[slot] = bits ^ pos;
+      return;
+    }
+    if (q.dissect & 16) {  // 6-byte records 6 bytes apart, as three 2-byte stores
+      if (slot < cap_nb) {
+        uint16_t* r6 = (uint16_t*) (my_rec + (size_t) bin * bin_stride) + 3 * (size_t) slot;
+        r6[0] = (uint16_t) (pos & (F2N_BIN_ENTRIES - 1));
+        r6[1] = (uint16_t) bits;
+        r6[2] = (uint16_t) (bits >> 16);
+      }
+      return;
+    }
 #endif
     if (slot < cap_nb) {
       uint2 r;
       r.x = pos & (F2N_BIN_ENTRIES - 1);
       r.y = bits;
-      my_rec[(uint32_t) bin * (uint32_t) bin_stride + (uint32_t) slot] = r;  // (a segment index inside the block's region fits 32 bits)
+      my_rec[(uint32_t) bin * (uint32_t) bin_stride + (uint32_t) slot] = r;  // (a segment index inside the block's region fits 32 bits: one scalar base, one vector offset)
     } else {
       const int os = OVF ? atomicAdd(&s_ovf, 1) : F2N_BIN_OVF_CAP;
       if (OVF && os < F2N_BIN_OVF_CAP) {
@@ -1005,7 +860,8 @@ __global__ __launch_bounds__(256) void hash_bin_staged_kernel(int n, int chunk, 
       }
     }
   };
-  // software pipeline: the next tile's gradient pair, point and transform index are in flight while this tile is hashed and appended
+  // software pipeline: the next tile's gradient pair, point and transform index are in flight while this tile is
+  // hashed and appended (three dependent HBM round trips per tile otherwise)
   struct Tile {
     half2_t gpair;
     float p[3];
@@ -1031,10 +887,15 @@ __global__ __launch_bounds__(256) void hash_bin_staged_kernel(int n, int chunk, 
       for (int k = 0; k < 3; k++) p01[k] = pts_are_warped ? (cur.p[k] + 1.f) * .5f : cur.p[k];
       const int vol = cur.vol;
       F2nCell cell;
-      const uint32_t* row = pb_lds + 6 * vol;
-      const int32_t prim3[3] = {(int32_t) row[0], (int32_t) row[1], (int32_t) row[2]};
-      const float bias3[3] = {__uint_as_float(row[3]), __uint_as_float(row[4]), __uint_as_float(row[5])};
-      f2n_hash_cell(p01, lt.scale[l], prim3, bias3, lt.size[l], cell);
+      if (STAGED) {
+        const uint32_t* row = pb_lds + 6 * vol;
+        const int32_t prim3[3] = {(int32_t) row[0], (int32_t) row[1], (int32_t) row[2]};
+        const float bias3[3] = {__uint_as_float(row[3]), __uint_as_float(row[4]), __uint_as_float(row[5])};
+        f2n_hash_cell(p01, lt.scale[l], prim3, bias3, lt.size[l], cell);
+      } else {
+        const int tf = l * h.n_volumes + vol;
+        f2n_hash_cell(p01, lt.scale[l], h.prim_pool + 3 * tf, h.bias_pool + 3 * tf, lt.size[l], cell);
+      }
       float v[16];
       if (f2n_combine_runs(cell, vol, c, g0, g1, v)) {
 #pragma unroll
@@ -1877,13 +1738,20 @@ struct F2nBucketHook {
 };
 static F2nBucketHook g_bucket_hook[16];
 
-// f2n_set_scatter_producer: 0 = hash_bin_kernel, 1 = hash_bin_staged_kernel (profiles/scatter_producers.txt)
+// f2n_set_scatter_producer: 0 = hash_bin_kernel<OVF, false>, 1 = hash_bin_kernel<OVF, true> (profiles/scatter_producers.txt)
 static std::atomic<int> g_scatter_producer{1};
 int f2n_set_scatter_producer(int variant) {
   if (variant != 0 && variant != 1) return F2N_ERR_INVALID_ARG;
   g_scatter_producer.store(variant);
   return F2N_OK;
 }
+
+#if F2N_DEBUG_BUILD
+static int f2n_debug_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e != nullptr ? atoi(e) : dflt;
+}
+#endif
 
 // Owner-binned scatter of f16 gradients gx (pair (l, ch) of sample s at gx[s*ss + (l>>1)*ps + 2*(l&1) + ch]).
 static int f2n_binned_scatter(hipStream_t st, int n, const F2nHashArgs& h, const int32_t* local_idx, const int32_t* local_size,
@@ -1893,27 +1761,15 @@ static int f2n_binned_scatter(hipStream_t st, int n, const F2nHashArgs& h, const
                               hipEvent_t wait_before_owners = nullptr, int* adam_applied = nullptr) {
   if (adam_applied != nullptr) *adam_applied = 0;
   F2nBinQueues q;
-#if F2N_DEBUG_BUILD  // measurement knob of the debug variant: the producer chunk count whatever the sample count
-  static const int nb_force = []() {
-    const char* e = getenv("F2N_BIN_NB");
-    const int v = e != nullptr ? atoi(e) : 0;
-    return (v == 32 || v == 64 || v == 128) ? v : 0;
-  }();
-  q.nb_force = nb_force;
-  static const int force_f64 = []() {
-    const char* e = getenv("F2N_OWNER_F64");
-    return e != nullptr && atoi(e) != 0 ? 1 : 0;
-  }();
-  q.force_f64 = force_f64;
-  static const int dissect = []() {
-    const char* e = getenv("F2N_BIN_DISSECT");
-    return e != nullptr ? atoi(e) : 0;
-  }();
+#if F2N_DEBUG_BUILD  // measurement knobs of the debug variant, read once
+  static const int nb_force = f2n_debug_env_int("F2N_BIN_NB", 0);  // the producer chunk count whatever the sample count
+  static const int force_f64 = f2n_debug_env_int("F2N_OWNER_F64", 0);
+  static const int dissect = f2n_debug_env_int("F2N_BIN_DISSECT", 0);
+  static const int layout = f2n_debug_env_int("F2N_BIN_LAYOUT", 1);
+  static const int lds_pad = f2n_debug_env_int("F2N_BIN_LDS_PAD", 0);  // more dynamic LDS, i.e. fewer producer blocks per CU
+  q.nb_force = (nb_force == 32 || nb_force == 64 || nb_force == 128) ? nb_force : 0;
+  q.force_f64 = force_f64 != 0 ? 1 : 0;
   q.dissect = dissect;
-  static const int layout = []() {
-    const char* e = getenv("F2N_BIN_LAYOUT");
-    return e != nullptr ? atoi(e) : 1;
-  }();
   q.producer_major = layout;
 #else
   q.nb_force = 0;
@@ -1921,8 +1777,6 @@ static int f2n_binned_scatter(hipStream_t st, int n, const F2nHashArgs& h, const
   q.dissect = 0;
   q.producer_major = 1;
 #endif
-
-
   q.n_bins = level_entries >> F2N_BIN_SHIFT;
   const int chunk = (((n + F2N_BIN_NB - 1) / F2N_BIN_NB) + 255) & ~255;
   q.cap = (int) (1.25 * 8.0 * (double) chunk / (double) q.n_bins) + 64;
@@ -1937,34 +1791,21 @@ static int f2n_binned_scatter(hipStream_t st, int n, const F2nHashArgs& h, const
   static std::atomic<int> g_scatter_stamp{0};
   q.stamp = (g_scatter_stamp.fetch_add(1) & 0x3fffffff) + 1;  // (the workspace starts out zeroed: never a launch's stamp)
   const bool ovf = level_entries > (1 << 19);  // (see hash_bin_kernel)
-  // f2n_set_scatter_producer; a pool of more transforms than a block stages keeps the previous producer (its global loads)
+  // f2n_set_scatter_producer; a pool of more transforms than a block stages takes the non-staged instantiation (its global loads)
   const bool staged = g_scatter_producer.load() != 0 && 24 * (size_t) h.n_volumes <= F2N_BIN_STAGE_BUDGET;
   size_t lds = staged ? 24 * (size_t) h.n_volumes : 0;
   if (staged && lds < F2N_BIN_LDS_FLOOR) lds = F2N_BIN_LDS_FLOOR;
-#if F2N_DEBUG_BUILD  // measurement knob: more dynamic LDS, i.e. fewer producer blocks per CU
-  static const int lds_pad = []() {
-    const char* e = getenv("F2N_BIN_LDS_PAD");
-    return e != nullptr ? atoi(e) : 0;
-  }();
+#if F2N_DEBUG_BUILD
   if (staged && lds_pad > 0 && lds + (size_t) lds_pad <= 27000) lds += (size_t) lds_pad;  // (with the static 37 KB: inside 64 KB)
 #endif
-  if (staged && ovf)
-    hipLaunchKernelGGL(hash_bin_staged_kernel<true>, dim3(F2N_N_LEVELS * F2N_BIN_NB), dim3(256), lds, st, n, chunk, h, local_idx, local_size,
-                       level_scale, pts, warped, volume_idx, vol_stride, gx, ss, ps, nz_mask, q, grad_table, n_dev, n_off);
-  else if (staged)
-    hipLaunchKernelGGL(hash_bin_staged_kernel<false>, dim3(F2N_N_LEVELS * F2N_BIN_NB), dim3(256), lds, st, n, chunk, h, local_idx, local_size,
-                       level_scale, pts, warped, volume_idx, vol_stride, gx, ss, ps, nz_mask, q, grad_table, n_dev, n_off);
-  else if (ovf)
-    hipLaunchKernelGGL(hash_bin_kernel<true>, dim3(F2N_N_LEVELS * F2N_BIN_NB), dim3(256), 0, st, n, chunk, h, local_idx, local_size,
-                       level_scale, pts, warped, volume_idx, vol_stride, gx, ss, ps, nz_mask, q, grad_table, n_dev, n_off);
-  else
-    hipLaunchKernelGGL(hash_bin_kernel<false>, dim3(F2N_N_LEVELS * F2N_BIN_NB), dim3(256), 0, st, n, chunk, h, local_idx, local_size,
-                       level_scale, pts, warped, volume_idx, vol_stride, gx, ss, ps, nz_mask, q, grad_table, n_dev, n_off);
-#define F2N_LAUNCH_OWNERS(ADAM_, GRID, FIRST, AD)                                                                                         \
-  do {                                                                                                                                    \
-    if (ovf) hipLaunchKernelGGL((hash_bin_accumulate_kernel<ADAM_, true>), dim3(GRID), dim3(256), 0, st, q, H, grad_table, n, n_dev, n_off, FIRST, AD);  \
-    else hipLaunchKernelGGL((hash_bin_accumulate_kernel<ADAM_, false>), dim3(GRID), dim3(256), 0, st, q, H, grad_table, n, n_dev, n_off, FIRST, AD);     \
-  } while (0)
+#define F2N_LAUNCH_PRODUCERS(OVF, ST)                                                                                                  \
+  hipLaunchKernelGGL((hash_bin_kernel<OVF, ST>), dim3(F2N_N_LEVELS * F2N_BIN_NB), dim3(256), lds, st, n, chunk, h, local_idx, local_size, \
+                     level_scale, pts, warped, volume_idx, vol_stride, gx, ss, ps, nz_mask, q, grad_table, n_dev, n_off)
+  if (staged && ovf) F2N_LAUNCH_PRODUCERS(true, true);
+  else if (staged) F2N_LAUNCH_PRODUCERS(false, true);
+  else if (ovf) F2N_LAUNCH_PRODUCERS(true, false);
+  else F2N_LAUNCH_PRODUCERS(false, false);
+#undef F2N_LAUNCH_PRODUCERS
 #if F2N_DEBUG_BUILD
   if (q.dissect & 4) return f2n_launch_status();  // (timing only: the producers alone)
 #endif
@@ -1975,6 +1816,11 @@ static int f2n_binned_scatter(hipStream_t st, int n, const F2nHashArgs& h, const
   int dev = 0;
   (void) hipGetDevice(&dev);
   const F2nBucketHook hook = (dev >= 0 && dev < 16) ? g_bucket_hook[dev] : F2nBucketHook{nullptr, nullptr, 0, nullptr};
+#define F2N_LAUNCH_OWNERS(ADAM_, GRID, FIRST, AD)                                                                                         \
+  do {                                                                                                                                    \
+    if (ovf) hipLaunchKernelGGL((hash_bin_accumulate_kernel<ADAM_, true>), dim3(GRID), dim3(256), 0, st, q, H, grad_table, n, n_dev, n_off, FIRST, AD);  \
+    else hipLaunchKernelGGL((hash_bin_accumulate_kernel<ADAM_, false>), dim3(GRID), dim3(256), 0, st, q, H, grad_table, n, n_dev, n_off, FIRST, AD);     \
+  } while (0)
   if (hook.fn != nullptr && hook.n > 1 && S >= hook.n && (hook.table == nullptr || hook.table == (const void*) grad_table)) {
     for (int b = 0; b < hook.n; b++) {
       const int g0 = (int) ((long) b * S / hook.n), g1 = (int) ((long) (b + 1) * S / hook.n);

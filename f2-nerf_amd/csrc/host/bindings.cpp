@@ -773,7 +773,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                     [](ExpRunner& r) { return r.renderer_->prepass_planes_cache_; },
                     [](ExpRunner& r, bool on) { r.renderer_->prepass_planes_cache_ = on; })
       .def_property_readonly("prepass_reuse_steps", [](ExpRunner& r) { return r.renderer_->n_feat_reuse_steps_; })  // steps that took that path
-      .def_property("scatter_producer",  // f2n_set_scatter_producer: 1 = hash constants in LDS (default), 0 = the previous producer kernel (A/B knob; per process)
+      .def_property("scatter_producer",  // f2n_set_scatter_producer: 1 = hash constants in LDS (default), 0 = the non-staged instantiation (A/B knob; per process)
                     [](ExpRunner&) { return g_scatter_producer; },
                     [](ExpRunner&, int variant) {
                       if (f2n_set_scatter_producer(variant) != F2N_OK) throw std::invalid_argument("scatter_producer: 0 or 1");

@@ -68,10 +68,10 @@ int f2n_set_scatter_buckets(int n_buckets, f2n_bucket_fn fn, void* user);
  * reports them; any other f2n_hash_bwd / f2n_field_bwd on the device (a second runner, a test, a taped backward into another
  * buffer) runs its owner launch in one piece and calls nobody.  grad_table_h16 == NULL: whatever table (the v12 behaviour). */
 int f2n_set_scatter_buckets_for(int n_buckets, f2n_bucket_fn fn, void* user, const void* grad_table_h16);
-/* (an addition to ABI v13) Which producer kernel the owner-binned scatter behind f2n_hash_bwd / f2n_field_bwd[_dyn] / the step tail
- * launches, for the whole process: 1 (the default) = the producer that keeps its level's hash constants in LDS (three blocks per CU;
- * pools of more than 512 transforms still get the previous one); 0 = the previous producer (constants from global memory behind the
- * transform index, four blocks per CU), kept for A/B measurements.  Both fill the same queue segments with the same records -- in
+/* (an addition to ABI v13) Which instantiation of the producer kernel the owner-binned scatter behind f2n_hash_bwd / f2n_field_bwd[_dyn] /
+ * the step tail launches, for the whole process: 1 (the default) = the staged instantiation, which keeps its level's hash constants in
+ * LDS (three blocks per CU; pools of more than 512 transforms still get the non-staged one); 0 = the non-staged instantiation (constants
+ * from global memory behind the transform index, four blocks per CU), kept for A/B measurements.  Both fill the same queue segments with the same records -- in
  * another order, which the owners' exact sums do not see: the gradient table is the same byte for byte as long as
  * f2n_debug_counters()[0] stays 0.  Host-only; takes effect with the next launch.  Any other value: F2N_ERR_INVALID_ARG. */
 int f2n_set_scatter_producer(int variant);

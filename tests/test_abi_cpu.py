@@ -153,4 +153,5 @@ def test_no_kernel_of_the_product_spills_vector_registers_or_uses_scratch(lib):
               "hash_bin_accumulate_kernel<true, true>"):
         assert by[k]["waves_per_simd"] >= 4 and by[k]["vgpr"] <= 128 and by[k]["lds"] <= 160 * 1024 // 4, (k, by[k])
     assert by["field_shade_fwd_kernel"]["waves_per_simd"] >= 5  # (weights in LDS: 152 -> 80 registers)
-    assert by["hash_bin_kernel<false>"]["waves_per_simd"] >= 4 and by["hash_bin_kernel<true>"]["waves_per_simd"] >= 4
+    for k in ("hash_bin_kernel<false, false>", "hash_bin_kernel<true, false>", "hash_bin_kernel<false, true>", "hash_bin_kernel<true, true>"):
+        assert by[k]["waves_per_simd"] >= 4, (k, by[k])

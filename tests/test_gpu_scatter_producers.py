@@ -1,8 +1,9 @@
-"""GPU (run with `-m gpu`): the two producers of the owner-binned hash-gradient scatter leave the same gradient table.
+"""GPU (run with `-m gpu`): the two instantiations of the owner-binned hash-gradient scatter's producer kernel leave the same
+gradient table.
 
-f2n_set_scatter_producer(0) is the producer kernel as it was (hash constants from global memory, four blocks per CU); the default
-producer keeps its level's hash constants in dynamic LDS when they fit (the previous kernel otherwise), so three blocks share a CU
-and take their slots in another order.  Which
+f2n_set_scatter_producer(0) is the non-staged instantiation (hash constants from global memory, four blocks per CU); the default,
+the staged instantiation, keeps its level's hash constants in dynamic LDS when they fit (the non-staged one otherwise), so three
+blocks share a CU and take their slots in another order.  Which
 slot of a queue segment a record lands in differs between them; what the owners make of a segment does not: they sum its records
 exactly (fixed-point image or fp64).  So as long as no record takes the packed-f16 atomic of last resort
 (f2n_debug_counters()[0] == 0) the two f16 tables are equal byte for byte -- the criterion here is equality, there is no tolerance.
@@ -174,7 +175,7 @@ def test_producers_agree_when_segments_overflow(hip, fox_state):
 
 def test_producers_agree_with_more_transforms_than_the_lds_budget_holds(hip, fox_state):
     """A synthetic pool of 600 transforms: 24 B each, more than the 12288 B a producer block stages per level -- the launch falls back
-    to global loads of the hash constants (the previous kernel) whatever the setter says."""
+    to global loads of the hash constants (the non-staged instantiation) whatever the setter says."""
     rng = np.random.default_rng(600)
     V, log2, n = 600, 14, 32769
     prim = (rng.integers(1, 1 << 30, (16, V, 3)) * 2 + 1).astype(np.int32)

@@ -1,5 +1,5 @@
-"""CPU: the two producers of the owner-binned scatter (f2n_set_scatter_producer) on the emulated wavefront -- the kernel source's
-own meaning, whatever the compiler made of it for the GPU: the hash constants staged in dynamic LDS.  One case of
+"""CPU: the non-staged and the staged instantiation of the owner-binned scatter's producer kernel (f2n_set_scatter_producer) on the
+emulated wavefront -- the kernel source's own meaning, whatever the compiler made of it for the GPU.  One case of
 tests/test_gpu_scatter_producers.py at the smallest shape the binned path takes: n = 32768, 2^14 entries per level, the
 50-samples-per-ray input (about 12 s here)."""
 import os

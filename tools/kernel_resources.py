@@ -20,14 +20,19 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 
 
-def code_object_metadata(obj_path):
-    """amdhsa.kernels of the gfx950 code object embedded in one host object file (hipcc -c output)."""
+def code_object_dump(obj_path, tool, *args):
+    """stdout of an LLVM tool run on the gfx950 code object embedded in one host object file (hipcc -c output)."""
     with tempfile.TemporaryDirectory() as tmp:
         fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co")
         subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", obj_path, fat], check=True)
         subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
                         "--targets=" + TARGET, "--output=" + co], check=True)
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+        return subprocess.run([os.path.join(LLVM, tool)] + list(args) + [co], check=True, capture_output=True, text=True).stdout
+
+
+def code_object_metadata(obj_path):
+    """amdhsa.kernels of the gfx950 code object embedded in one host object file (hipcc -c output)."""
+    notes = code_object_dump(obj_path, "llvm-readelf", "--notes")
     start = notes.index("---")
     end = notes.index("\n...", start)
     return yaml.safe_load(notes[start:end])["amdhsa.kernels"]

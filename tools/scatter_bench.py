@@ -17,7 +17,7 @@ ap.add_argument("--only", default="", help="substring of the one sample set to r
 ap.add_argument("--amps", default="2e-4,0.05", help="standard deviations of the synthetic f16 gradients: a training's loss-scaled gradients sum to "
                 "~1 per table slice (f2n_debug_counters()[2] of the debug variant: 0.6 converged, 1.2 fresh), which 2e-4 reproduces; "
                 "0.05 drives every slice's sum of |addend| past the fixed-point route's range, i.e. times the owners' fp64 route")
-ap.add_argument("--variant", type=int, default=1, help="the producer kernel (f2n_set_scatter_producer): 1 = staged hash constants (default), 0 = the previous one")
+ap.add_argument("--variant", type=int, default=1, help="the producer kernel's instantiation (f2n_set_scatter_producer): 1 = staged hash constants (default), 0 = non-staged")
 args = ap.parse_args()
 capi.set_scatter_producer(args.variant)
 dev = "cuda"
