@@ -583,6 +583,23 @@ def weight_var_bwd(n_rays, weights, pts_se, dvars, dweights):
                                  _p(dweights, "f32")), "f2n_weight_var_bwd")
 
 
+def distortion_fwd(n_rays, pts_se, weights, dt, dist):
+    """dist [R]: the distortion loss of every ray on its warped intervals (f2n_distortion_fwd; no reference counterpart)."""
+    _ck(lib().f2n_distortion_fwd(_stream(), _i(n_rays), _p(pts_se, "i32"), _p(weights, "f32"), _p(dt, "f32"), _p(dist, "f32")),
+        "f2n_distortion_fwd")
+
+
+def distortion_bwd(n_rays, pts_se, weights, dt, ddist, dweights, dist=None):
+    """dweights [M] = ddist[ray] * d dist / d w for the samples of non-empty rays (the rest is untouched); dist [R] if given."""
+    _ck(lib().f2n_distortion_bwd(_stream(), _i(n_rays), _p(pts_se, "i32"), _p(weights, "f32"), _p(dt, "f32"), _p(ddist, "f32"),
+                                 _p(dweights, "f32"), _p(dist, "f32", True)), "f2n_distortion_bwd")
+
+
+def loss_add_mean(n, x, weight, losses, slot):
+    """losses[slot] = mean(x[:n]), losses[0] += weight * mean (f2n_loss_add_mean: one workgroup, fp64, a fixed order)."""
+    _ck(lib().f2n_loss_add_mean(_stream(), _i(n), _p(x, "f32"), _f(weight), _p(losses, "f32"), _i(slot)), "f2n_loss_add_mean")
+
+
 def flex_sum_fwd(n_rays, vec, val, se, out):
     _ck(lib().f2n_flex_sum_fwd(_stream(), _i(n_rays), _i(vec), _p(val, "f32"), _p(se, "i32"), _p(out, "f32")), "f2n_flex_sum_fwd")
 

@@ -27,6 +27,10 @@ ExpRunner::ExpRunner(const std::map<std::string, std::string>& flat_config, int 
   var_loss_weight_ = c.Float("train.var_loss_weight");
   var_loss_start_ = c.Int("train.var_loss_start");
   var_loss_end_ = c.Int("train.var_loss_end");
+  // (no reference counterpart and no default in the configuration: absent = 0 = off, and a step is then what it was without the key)
+  dist_loss_weight_ = c.Has("train.dist_loss_weight") ? c.Float("train.dist_loss_weight") : 0.f;
+  TORCH_CHECK(std::isfinite(dist_loss_weight_) && dist_loss_weight_ >= 0.f, "train.dist_loss_weight must be finite and >= 0, got ",
+              c.Has("train.dist_loss_weight") ? c.Str("train.dist_loss_weight") : std::string("0"));
   gradient_scaling_start_ = c.Int("train.gradient_scaling_start");
   gradient_scaling_end_ = c.Int("train.gradient_scaling_end");
   global_data_pool_->n_volumes_ = c.Has("runtime.n_volumes") ? c.Int("runtime.n_volumes") : 1;
@@ -382,7 +386,7 @@ TrainStats ExpRunner::TrainStep(const Tensor& rays_o, const Tensor& rays_d, cons
   {
     F2N_HOST_SCOPE("step.fwd_bwd");
     out = renderer_->TrainForwardBackward(rays_o, rays_d, bounds, gt_colors, emb_idx, CurVarLossWeight(), disp_loss_weight_,
-                                          tv_loss_weight_);
+                                          tv_loss_weight_, dist_loss_weight_);
   }
   renderer_->async_count_ = false;
   renderer_->after_octree_update_ = nullptr;
@@ -398,6 +402,8 @@ TrainStats ExpRunner::TrainStep(const Tensor& rays_o, const Tensor& rays_d, cons
   stats.n_meaningful = renderer_->count_pending_ ? -1 : renderer_->last_n_kept_pts_;  // -1: still on the device (see counters())
   stats.loss = out.losses.slice(0, 0, 1).squeeze(0);
   stats.mse = out.losses.slice(0, 5, 6).squeeze(0);
+  last_losses_ = out.losses;
+  last_loss_terms_.clear();
   bool applied = false;
   // (a data-parallel replica whose batch missed the scene still joins the gradient exchange, with its zero gradients)
   if (out.has_samples || sync_.Installed()) {
@@ -573,9 +579,22 @@ TrainStats ExpRunner::TrainStepAutograd(const Tensor& rays_o, const Tensor& rays
     Tensor var_loss = (sampled_var + 1e-2).sqrt().mean();
     const float var_w = CurVarLossWeight();
     loss = color_loss + var_loss * var_w + disparity_loss * disp_loss_weight_ + tv_loss * tv_loss_weight_;
+    Tensor dist_loss;
+    if (dist_loss_weight_ > 0.f) {
+      dist_loss = CustomOps::Distortion(rr.weights, rr.dt, rr.idx_start_end).mean();
+      loss = loss + dist_loss * dist_loss_weight_;
+    }
+    last_loss_terms_ = {Tensor(), color_loss, var_loss, disparity_loss, tv_loss, Tensor(), dist_loss, Tensor()};
+  } else {
+    last_loss_terms_ = {Tensor(), color_loss, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
   stats.loss = loss.detach();
   stats.mse = (pred_colors.detach() - gt_colors).square().mean();
+  last_losses_ = Tensor();  // (put together by LastLosses() when somebody asks: the taped step itself launches nothing for it)
+  last_loss_terms_[0] = stats.loss;
+  last_loss_terms_[5] = stats.mse;
+  for (auto& t : last_loss_terms_)
+    if (t.defined()) t = t.detach();  // (handles only: the tape is not kept alive)
   // (a data-parallel replica whose batch missed the scene still joins the gradient exchange, with its zero gradients: every
   // rank must enter the collective, and the ranks that did see samples average over the whole world)
   const bool has_grad = loss.requires_grad();
@@ -689,6 +708,43 @@ GeometryResult ExpRunner::RenderGeometry(const Tensor& rays_o, const Tensor& ray
   out.surf_points = cat([](const GeometryResult& p) { return p.surf_points; });
   out.surf_normals = cat([](const GeometryResult& p) { return p.surf_normals; });
   return out;
+}
+
+// The distortion of rendered rays (diagnostics; no reference counterpart): RenderForward's launches per chunk of render_chunk_rays_
+// rays, then f2n_distortion_fwd on its weights and the sampler's dt.  RenderForward's side-effect contract: VALIDATE mode, a
+// streaming step flushed first; a chunk that meets no sample contributes zeros.
+Tensor ExpRunner::RayDistortion(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds) {
+  FinishPending();
+  torch::NoGradGuard no_grad;
+  const int n_rays = rays_d.size(0);
+  const int chunk = std::max(render_chunk_rays_, 1);
+  Tensor out = torch::zeros({n_rays}, DevF32());
+  auto prev = global_data_pool_->mode_;
+  global_data_pool_->mode_ = RunningMode::VALIDATE;
+  try {
+    for (int i = 0; i < n_rays; i += chunk) {
+      const int hi = std::min(i + chunk, n_rays);
+      auto rr = renderer_->RenderForward(rays_o.index({Slc(i, hi)}).contiguous(), rays_d.index({Slc(i, hi)}).contiguous(),
+                                         bounds.index({Slc(i, hi)}).contiguous());
+      if (!rr.weights.defined()) continue;
+      out.index_put_({Slc(i, hi)}, CustomOps::Distortion(rr.weights, rr.dt, rr.idx_start_end));
+    }
+  } catch (...) {
+    global_data_pool_->mode_ = prev;
+    throw;
+  }
+  global_data_pool_->mode_ = prev;
+  return out;
+}
+
+Tensor ExpRunner::LastLosses() {
+  if (last_losses_.defined()) return last_losses_;
+  TORCH_CHECK(last_loss_terms_.size() == 8, "no training step has run yet");
+  torch::NoGradGuard no_grad;
+  std::vector<Tensor> v;
+  for (const auto& t : last_loss_terms_) v.push_back(t.defined() ? t.detach().to(torch::kFloat32).reshape({}) : torch::zeros({}, DevF32()));
+  last_losses_ = torch::stack(v);
+  return last_losses_;
 }
 
 // The per-image body of ExpRunner::TestImages (ExpRunner.cpp:353-369): render camera idx of the data set, quantise the

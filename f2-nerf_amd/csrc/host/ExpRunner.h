@@ -69,6 +69,8 @@ class ExpRunner {
   // Renderer::RenderGeometry over any number of rays in chunks of render_chunk_rays_ (VALIDATE mode, a streaming step flushed first).
   // keep_samples needs all rays in one chunk; over several chunks surf_idx counts within the ray's own chunk.
   GeometryResult RenderGeometry(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds, float tau, bool keep_samples);
+  // [N]: the distortion (CustomOps::Distortion) of any number of rays, rendered as RenderRays renders them, in chunks of render_chunk_rays_
+  Tensor RayDistortion(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds);
   float TestImagePSNR(Dataset& dataset, int idx);       // 8-bit quantised prediction, as ExpRunner.cpp:360-369
   std::vector<float> TestImages(Dataset& dataset);      // per-view PSNR of the test set, then the mean
   // One test view with everything ExpRunner::TestImages of the reference measures or writes (ExpRunner.cpp:353-379), from ONE render:
@@ -144,6 +146,12 @@ class ExpRunner {
   float ray_march_init_fineness_;
   int ray_march_fineness_decay_end_iter_;
   float tv_loss_weight_, disp_loss_weight_, var_loss_weight_;
+  // train.dist_loss_weight (absent = 0 = off): the weight of the mean distortion of the batch's rays on their warped intervals
+  // (f2n_distortion_*; no reference counterpart).  > 0: TrainStep takes the three compositing launches on both routes (RendererTrain.cpp).
+  float dist_loss_weight_ = 0.f;
+  Tensor last_losses_;  // device [8] of the last training step: loss, colour, var, disp, tv, mse, dist, 0
+  std::vector<Tensor> last_loss_terms_;  // ... of a taped step: its terms as the tape left them (undefined = 0), stacked on demand
+  Tensor LastLosses();
   int var_loss_start_, var_loss_end_;
   float gradient_scaling_start_, gradient_scaling_end_;
   float cur_lr_ = 0.f;

@@ -65,10 +65,33 @@ struct WeightVarFunction : public torch::autograd::Function<WeightVarFunction> {
   }
 };
 
+// Distortion loss on the warped ray intervals (no reference counterpart; include/f2n_abi.h: f2n_distortion_*).  dt is data of the
+// sampler: only the weights receive a gradient.
+struct DistortionFunction : public torch::autograd::Function<DistortionFunction> {
+  static variable_list forward(AutogradContext* ctx, Tensor weights, Tensor dt, Tensor se) {
+    const int n = se.size(0);
+    Tensor out = torch::empty({n}, DevF32());
+    F2N_TIMED_CALL("distortion_fwd", f2n_distortion_fwd(CurStream(), n, I32P(se), F32P(weights), F32P(dt), F32P(out)));
+    ctx->save_for_backward({weights, dt, se});
+    return {out};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list g) {
+    auto s = ctx->get_saved_variables();
+    Tensor dd = g[0].contiguous();
+    Tensor dw = torch::zeros_like(s[0]);  // (the rows of empty rays are not written)
+    F2N_TIMED_CALL("distortion_bwd", f2n_distortion_bwd(CurStream(), (int) s[2].size(0), I32P(s[2]), F32P(s[0]), F32P(s[1]), F32P(dd), F32P(dw), nullptr));
+    return {dw, Tensor(), Tensor()};
+  }
+};
+
 }  // namespace
 
 Tensor CustomOps::WeightVar(Tensor weights, Tensor idx_start_end) {
   return WeightVarFunction::apply(weights.contiguous(), idx_start_end.contiguous())[0];
+}
+
+Tensor CustomOps::Distortion(Tensor weights, Tensor dt, Tensor idx_start_end) {
+  return DistortionFunction::apply(weights.contiguous(), dt.to(torch::kFloat32).contiguous().detach(), idx_start_end.contiguous())[0];
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -589,7 +612,7 @@ RenderResult Renderer::Render(const Tensor& rays_o, const Tensor& rays_d, const 
                                                  fr.sample_emb_idx, fr.emb ? &app_emb_grad_ : nullptr);
   auto out = CompositeFunction::apply(scene_feat, sampled_colors, es.dt, es.t, fr.bg_color, es.pts_idx_bounds,
                                       (double) gdp->gradient_scaling_progress_);
-  return {out[0], es.first_oct_dis, out[1], edge_feat, out[2], out[3], es.pts_idx_bounds};
+  return {out[0], es.first_oct_dis, out[1], edge_feat, out[2], out[3], es.pts_idx_bounds, es.dt};
 }
 
 // Forward-only rendering (ExpRunner::RenderWholeImage's chunk body, TestImages, RenderPath): the kernels of the streaming
@@ -624,7 +647,7 @@ RenderResult Renderer::RenderForward(const Tensor& rays_o, const Tensor& rays_d,
   Tensor bg = fr.bg_color.contiguous();
   F2N_TIMED_CALL("composite_fwd", f2n_composite_fwd(st, n_rays, I32P(es.pts_idx_bounds), F32P(f0c), 1, F32P(es.dt), F32P(es.t), F32P(rgb),
                              F32P(bg), F32P(colors), F32P(disparity), F32P(depth), F32P(weights), nullptr));
-  return {colors, es.first_oct_dis, disparity, Tensor(), depth, weights, es.pts_idx_bounds};
+  return {colors, es.first_oct_dis, disparity, Tensor(), depth, weights, es.pts_idx_bounds, es.dt};
 }
 
 int Renderer::LoadStates(const std::vector<Tensor>& states, int idx) {  // Renderer.cpp:216-224

@@ -34,6 +34,7 @@ struct RenderResult {  // Renderer.h:18-27 of the reference
   Tensor depth;
   Tensor weights;
   Tensor idx_start_end;
+  Tensor dt;  // [M]: the warped step lengths of the surviving samples (what compositing integrates over; CustomOps::Distortion)
 };
 
 // Everything Render() knows after sampling, pre-pass, early stop, compaction and the occupancy update.
@@ -200,7 +201,7 @@ struct GeometryResult {
 };
 
 struct TrainOutputs {
-  Tensor losses;  // device [8]: loss, color, var, disp, tv, mse, 0, 0 (f2n_train_loss)
+  Tensor losses;  // device [8]: loss, color, var, disp, tv, mse, dist (0 unless dist_w > 0), 0 (f2n_train_loss, f2n_loss_add_mean)
   Tensor colors;
   bool has_samples = false;
 };
@@ -409,7 +410,7 @@ class Renderer : public Pipe {
   int64_t total_kept_pts_ = 0, total_all_pts_ = 0;  // running totals over training-mode calls (resolved counts only)
   // forward + ExpRunner::Train's loss + backward into the gradient buffers, without the autograd tape
   TrainOutputs TrainForwardBackward(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds, const Tensor& gt_colors,
-                                    const Tensor& emb_idx, float var_w, float disp_w, float tv_w);
+                                    const Tensor& emb_idx, float var_w, float disp_w, float tv_w, float dist_w = 0.f);
 
   // World-space density (RendererQuery.cpp): exp(f0 - 3) at world points [n,3], exactly 0 where no listed leaf holds the point;
   // on the grid of MakeGridSpec as [nz, ny, nx] (x fastest), in z-slabs of at most density_slab_points_ points; and the
@@ -524,6 +525,8 @@ class Renderer : public Pipe {
 
 namespace CustomOps {
 Tensor WeightVar(Tensor weights, Tensor idx_start_end);  // CustomOps.cu:12-66 via f2n_weight_var_*
+// [R]: the distortion loss of every ray on its warped intervals via f2n_distortion_* (no reference counterpart); differentiable in weights
+Tensor Distortion(Tensor weights, Tensor dt, Tensor idx_start_end);
 }
 
 }  // namespace f2n

@@ -20,7 +20,8 @@ using torch::autograd::variable_list;
 // dfeat[:,1:16]; the loss kernel: the edge rows of dfeat), so there is no zero-fill, no gradient accumulation pass and
 // no slice/cat copy: ~100 ATen launches and ~0.5 GB of HBM traffic per step less than the taped version.
 TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds,
-                                            const Tensor& gt_colors, const Tensor& emb_idx, float var_w, float disp_w, float tv_w) {
+                                            const Tensor& gt_colors, const Tensor& emb_idx, float var_w, float disp_w, float tv_w,
+                                            float dist_w) {
   auto* gdp = global_data_pool_;
   auto* field = static_cast<Hash3DAnchored*>(scene_field_.get());
   auto* shader = static_cast<SHShader*>(shader_.get());
@@ -121,7 +122,12 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
   Tensor bg = fr.bg_color.contiguous();
   Tensor dfeat = torch::empty({n, F2N_MLP_OUT_PAD}, DevF32());
   Tensor drgb = torch::empty({std::max(n_kept, 1), 3}, DevF32());  // (WeightVarLoss backward rides inside the compositing backward)
-  if (fr.dyn) {
+  // The distortion term (dist_w > 0; no reference counterpart) needs every weight of a ray before the first gradient of that ray: the
+  // step then takes the three launches below on both routes -- per-ray kernels, so the device-side survivor count is no obstacle,
+  // and bit-identical to the fused launch without the term.  Their loss values are final when train_loss has run: nothing of them
+  // is left to the step's deferred reduction, which on this route folds the colour and field networks' partial sums only.
+  const bool with_dist = dist_w > 0.f;
+  if (fr.dyn && !with_dist) {
     // ---- compositing forward, loss, compositing backward: one launch (f2n_composite_train); the TV gradient goes straight
     // into the edge rows of dfeat, the loss values are completed by the step's deferred reduction below ----
     F2N_TIMED_CALL("composite_train", f2n_composite_train(st, n_rays, I32P(es.pts_idx_bounds), F32P(f0c), 1, F32P(es.dt), F32P(es.t), F32P(rgb),
@@ -140,9 +146,19 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
                             F32P(feat) + F2N_MLP_OUT_PAD * eo, var_w, disp_w, tv_w, F32P(out.losses), F32P(dcolors),
                             F32P(ddisp), F32P(dvar), F32P(dfeat) + F2N_MLP_OUT_PAD * eo));
 
+    // ---- distortion: d (dist_w * mean dist) / d w per sample, handed to the compositing backward as dweights; losses[6], losses[0] ----
+    Tensor dweights;
+    if (with_dist) {
+      Tensor ddist = torch::full({n_rays}, dist_w / (float) n_rays, DevF32()), dist = torch::empty({n_rays}, DevF32());
+      dweights = torch::empty({std::max(n_kept, 1)}, DevF32());  // (only the samples of non-empty rays are written, and only they are read)
+      F2N_TIMED_CALL("distortion_bwd", f2n_distortion_bwd(st, n_rays, I32P(es.pts_idx_bounds), F32P(weights), F32P(es.dt), F32P(ddist),
+                                                          F32P(dweights), F32P(dist)));
+      F2N_TIMED_CALL("loss_add_mean", f2n_loss_add_mean(st, n_rays, F32P(dist), dist_w, F32P(out.losses), 6));
+    }
+
     // ---- backward ----
     F2N_TIMED_CALL("composite_bwd", f2n_composite_bwd(st, n_rays, I32P(es.pts_idx_bounds), F32P(f0c), 1, F32P(es.dt), F32P(es.t), F32P(rgb), F32P(bg),
-                               F32P(dcolors), F32P(ddisp), nullptr, nullptr, gdp->gradient_scaling_progress_, F32P(drgb),
+                               F32P(dcolors), F32P(ddisp), nullptr, with_dist ? F32P(dweights) : nullptr, gdp->gradient_scaling_progress_, F32P(drgb),
                                F32P(df0c), 1, F32P(weights), F32P(dvar)));
   }
   if (digest_taps_) DigestTap(TAP_GRAD_BEFORE, field->grad_h_);  // (must be all zeros: Adam's zero_grad / ZeroGrad)

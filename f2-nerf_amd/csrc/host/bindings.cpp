@@ -200,6 +200,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("verts"), py::arg("faces"), py::arg("passes"), py::arg("lam") = 0.5, py::arg("mu") = -0.53,
         py::arg("max_move") = std::numeric_limits<float>::infinity());
   // [F] float64: 1 for an equilateral face, towards 0 for a sliver, 0 for a degenerate or invalid face, NaN for a coordinate not finite
+  // [R]: the distortion loss of every ray on its warped intervals (f2n_distortion_fwd; no reference counterpart), on any device arrays:
+  // weights [M], dt [M], idx_start_end [R,2] int32, e.g. those of render_geometry(return_samples=True)
+  m.def("ray_distortion",
+        [](const Tensor& weights, const Tensor& dt, const Tensor& idx_start_end) {
+          TORCH_CHECK(idx_start_end.dim() == 2 && idx_start_end.size(1) == 2, "idx_start_end must be [R,2]");
+          TORCH_CHECK(weights.dim() == 1 && dt.dim() == 1 && weights.size(0) == dt.size(0), "weights and dt must be [M]");
+          CheckDev(weights, torch::kFloat32, "weights");
+          CheckDev(dt, torch::kFloat32, "dt");
+          CheckDev(idx_start_end, torch::kInt32, "idx_start_end");
+          torch::NoGradGuard no_grad;
+          return CustomOps::Distortion(weights, dt, idx_start_end);
+        },
+        py::arg("weights"), py::arg("dt"), py::arg("idx_start_end"));
   m.def("mesh_face_quality", [](const Tensor& verts, const Tensor& faces) { return MeshFaceQuality(verts, faces); }, py::arg("verts"),
         py::arg("faces"));
   // the raw per-iteration update of the level-set projection on the caller's device arrays; cand .. evals are updated in place
@@ -385,6 +398,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("end_iter", &ExpRunner::end_iter_)
       .def_readwrite("forward_render", &ExpRunner::forward_render_)
       .def_readwrite("render_chunk_rays", &ExpRunner::render_chunk_rays_)
+      .def_readwrite("dist_loss_weight", &ExpRunner::dist_loss_weight_)  // train.dist_loss_weight (0 = off; no reference counterpart)
+      .def("last_losses", &ExpRunner::LastLosses)  // device [8] of the last training step: loss, colour, var, disp, tv, mse, dist, 0
+      .def("ray_distortion",  // [N]: the distortion of any number of rays, rendered as render_rays renders them
+           [](ExpRunner& r, const Tensor& ro, const Tensor& rd, const Tensor& b) {
+             py::gil_scoped_release no_gil;
+             return r.RayDistortion(ro, rd, b);
+           },
+           py::arg("rays_o"), py::arg("rays_d"), py::arg("bounds"))
       .def("render_rays", &ExpRunner::RenderRays)
       .def("render_whole_image", &ExpRunner::RenderWholeImage)
       .def("test_image_psnr", &ExpRunner::TestImagePSNR)
@@ -429,6 +450,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              d["colors"] = rr.colors; d["first_oct_dis"] = rr.first_oct_dis; d["disparity"] = rr.disparity;
              d["edge_feats"] = rr.edge_feats; d["depth"] = rr.depth; d["weights"] = rr.weights;
              d["idx_start_end"] = rr.idx_start_end;
+             d["dt"] = rr.dt;  // [M]: the survivors' warped step lengths
              return d;
            })
       .def("get_samples",

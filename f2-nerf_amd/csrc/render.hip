@@ -649,6 +649,124 @@ __global__ __launch_bounds__(256) void weight_var_bwd_kernel(int n_rays, const f
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Distortion loss of mip-NeRF 360 (eq. 15) on the warped step length dt, the coordinate compositing integrates over (no reference
+// counterpart; include/f2n_abi.h has the definition and every rounding).  Sample k is the interval of length dt_k behind the
+// intervals of the ray's earlier survivors, m_k its midpoint: dist = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 dt_i, in O(n)
+// from four running sums of non-negative terms -- no cumulative coordinate, no subtraction, nothing cancels:
+//   forward   P_k = sum_{j<k} w_j      D_k = D_{k-1} + P_k h_k   = sum_{j<k} w_j (m_k - m_j)     h_k = (dt_{k-1} + dt_k) / 2
+//   reverse   S_k = sum_{j>k} w_j      U_k = U_{k+1} + S_k h_{k+1} = sum_{j>k} w_j (m_j - m_k)
+// The walks are those of composite_bwd_kernel: one row per ray, 16-sample chunks, the next chunk's loads in flight; P feeds D (and D
+// the ray's sum), so the chains of a chunk depend on one another and run one behind the other.  The neighbour's dt comes from the
+// neighbouring lane (lane 0: the previous chunk's last lane), not from a second load.
+// ---------------------------------------------------------------------------------------------------
+// the forward walk: lane c's D_k of every sample goes to d_out (if given), returns the ray's dist in every lane
+template <bool STORE_D>
+__device__ __forceinline__ float f2n_distortion_walk(int s, int e, int c, const float* __restrict__ weights, const float* __restrict__ dt,
+                                                     float* d_out) {
+  float P = 0.f, D = 0.f, dist = 0.f, dt_last = 0.f;
+  float n_w = weights[min(s + c, e - 1)], n_dt = dt[min(s + c, e - 1)];
+  for (int base = s; base < e; base += 16) {
+    const int i = base + c;
+    const bool in = i < e;
+    const float w = in ? n_w : 0.f, dti = in ? n_dt : 0.f;
+    if (base + 16 < e) {
+      n_w = weights[min(i + 16, e - 1)];
+      n_dt = dt[min(i + 16, e - 1)];
+    }
+    const float dt_prev = f2n_row_exclusive(dti, dt_last, c);
+    dt_last = f2n_row_last(dti);
+    const float h = (in && i > s) ? .5f * (dt_prev + dti) : 0.f;
+    float Pk;
+    f2n_row_chain1x(w, P, Pk);
+    f2n_row_chain1(Pk * h, D);
+    if (STORE_D && in) d_out[i] = D;
+    const float l = in ? w * (2.f * D) + ((w * w) * dti) * (1.f / 3.f) : 0.f;
+    f2n_row_chain1(l, dist);
+  }
+  return f2n_row_last(dist);
+}
+
+__global__ __launch_bounds__(256) void distortion_fwd_kernel(int n_rays, const int32_t* __restrict__ se, const float* __restrict__ weights,
+                                                             const float* __restrict__ dt, float* __restrict__ dist) {
+  const int c = threadIdx.x & 15;
+  const int ray = blockIdx.x * F2N_ROW_RAYS_PER_BLOCK + (threadIdx.x >> 4);
+  if (ray >= n_rays) return;
+  const int s = se[2 * ray], e = se[2 * ray + 1];
+  float d = 0.f;
+  if (s < e) d = f2n_distortion_walk<false>(s, e, c, weights, dt, nullptr);
+  if (c == 0) dist[ray] = d;
+}
+
+// D_k is made by lane (k - s) % 16 of the forward walk and needed by lane (e - 1 - k) % 16 of the reverse walk.  It travels through
+// the output itself: the forward walk parks D_k in dweights[k], the reverse walk reads it back and overwrites it with g_k (the lane
+// that reads a slot is the only one that writes it again).  dweights is therefore NOT __restrict__, and a workgroup-scope fence
+// stands between the walks: the row's stores have to be visible to the other lanes of its wave before they load, and the compiler
+// may move neither across it.  No LDS and no second [M] buffer.
+__global__ __launch_bounds__(256) void distortion_bwd_kernel(int n_rays, const int32_t* __restrict__ se, const float* __restrict__ weights,
+                                                             const float* __restrict__ dt, const float* __restrict__ ddist,
+                                                             float* dweights, float* __restrict__ dist) {
+  const int c = threadIdx.x & 15;
+  const int ray = blockIdx.x * F2N_ROW_RAYS_PER_BLOCK + (threadIdx.x >> 4);
+  if (ray >= n_rays) return;
+  const int s = se[2 * ray], e = se[2 * ray + 1];
+  if (s >= e) {
+    if (dist != nullptr && c == 0) dist[ray] = 0.f;
+    return;
+  }
+  const float total = f2n_distortion_walk<true>(s, e, c, weights, dt, dweights);
+  if (dist != nullptr && c == 0) dist[ray] = total;
+  const float dd = ddist[ray];
+  __threadfence_block();
+  // reverse walk: lane c takes sample hi-1-c, the row chains run over descending sample indices
+  struct RIn {
+    float w, dt, D;
+  };
+  auto rfetch = [&](int i) {
+    RIn r;
+    r.w = weights[i];
+    r.dt = dt[i];
+    r.D = dweights[i];
+    return r;
+  };
+  float S = 0.f, U = 0.f, dt_last = 0.f;
+  RIn rn = rfetch(max(e - 1 - c, s));
+  for (int hi = e; hi > s; hi -= 16) {
+    const int i = hi - 1 - c;
+    const bool in = i >= s;
+    const RIn rc = rn;
+    if (hi - 16 > s) rn = rfetch(max(i - 16, s));
+    const float w = in ? rc.w : 0.f, dti = in ? rc.dt : 0.f;
+    const float dt_next = f2n_row_exclusive(dti, dt_last, c);
+    dt_last = f2n_row_last(dti);
+    const float h = (in && i < e - 1) ? .5f * (dti + dt_next) : 0.f;
+    float Sk;
+    f2n_row_chain1x(w, S, Sk);
+    f2n_row_chain1(Sk * h, U);
+    if (in) dweights[i] = dd * (2.f * (rc.D + U) + ((2.f / 3.f) * w) * dti);
+  }
+}
+
+// losses[slot] = mean(x), losses[0] += weight * mean(x): one workgroup, fp64 accumulators, a fixed stride and a fixed tree, so the
+// result is a function of the inputs alone.
+__global__ __launch_bounds__(256) void loss_add_mean_kernel(int n, const float* __restrict__ x, float weight, float* __restrict__ losses,
+                                                            int slot) {
+  __shared__ double s_sum[256];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) acc += (double) x[i];
+  s_sum[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = 128; off >= 1; off >>= 1) {
+    if ((int) threadIdx.x < off) s_sum[threadIdx.x] += s_sum[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float mean = (float) (s_sum[0] / (double) n);
+    losses[slot] = mean;
+    losses[0] = losses[0] + weight * mean;
+  }
+}
+
 // Geometry buffers of rendered rays (no reference counterpart): per sample the world-space direction of the density gradient,
 // g = J^T df0/dw with J = f2n_warp_jac of the sample's leaf at x = o + t d (the point the march warped), and n = -g / |g| -- the
 // expressions of density_grad_scatter_kernel (f2n_warp_jac_t_mul / f2n_unit3, f2n_dev.h), so the two agree bit for bit; per ray
@@ -922,6 +1040,25 @@ int f2n_weight_var_fwd(void* stream, int n_rays, const float* weights, const int
 int f2n_weight_var_bwd(void* stream, int n_rays, const float* weights, const int32_t* pts_start_end, const float* dvars,
                        float* dweights) {
   F2N_ROW_LAUNCH(weight_var_bwd_kernel, n_rays, weights, pts_start_end, dvars, dweights);
+}
+
+int f2n_distortion_fwd(void* stream, int n_rays, const int32_t* pts_start_end, const float* weights, const float* dt, float* dist) {
+  if (n_rays > 0 && (pts_start_end == nullptr || weights == nullptr || dt == nullptr || dist == nullptr)) return F2N_ERR_INVALID_ARG;
+  F2N_ROW_LAUNCH(distortion_fwd_kernel, n_rays, pts_start_end, weights, dt, dist);
+}
+
+int f2n_distortion_bwd(void* stream, int n_rays, const int32_t* pts_start_end, const float* weights, const float* dt, const float* ddist,
+                       float* dweights, float* dist) {
+  if (n_rays > 0 && (pts_start_end == nullptr || weights == nullptr || dt == nullptr || ddist == nullptr || dweights == nullptr ||
+                     dweights == weights || dweights == dt))
+    return F2N_ERR_INVALID_ARG;
+  F2N_ROW_LAUNCH(distortion_bwd_kernel, n_rays, pts_start_end, weights, dt, ddist, dweights, dist);
+}
+
+int f2n_loss_add_mean(void* stream, int n, const float* x, float weight, float* losses, int slot) {
+  if (n < 1 || x == nullptr || losses == nullptr || slot < 1 || slot > 7) return F2N_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(loss_add_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t) stream, n, x, weight, losses, slot);
+  return f2n_launch_status();
 }
 
 int f2n_composite_geometry(void* stream, int n_rays, const int32_t* pts_start_end, const float* weights, const float* t, const float* rays_o,

@@ -21,10 +21,11 @@ import numpy as np
 
 
 def launcher_options(cfg):
-    """test.ssim and test.write_images of the launcher (run.py): both off unless asked for."""
+    """test.ssim, test.write_images and test.distortion of the launcher (run.py): all off unless asked for."""
     from .mesh import _flag
     t = cfg.get("test") or {}
-    return {"ssim": _flag(t.get("ssim", False)), "write_images": _flag(t.get("write_images", False))}
+    return {"ssim": _flag(t.get("ssim", False)), "write_images": _flag(t.get("write_images", False)),
+            "distortion": _flag(t.get("distortion", False))}
 
 
 def ssim(a, b, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, return_map=False):

@@ -12,7 +12,8 @@
     (split.npy)} -- the reference's layout (Dataset.cpp:16-146); NormalizeScene, bounds relaxation and the 8th-image test split
     are applied as there; images are decoded with PIL and kept resident in HBM.
   * modes (ExpRunner::Execute): train (ExpRunner::Train with checkpoints every save_freq and the final TestImages),
-    test (TestImages of the latest checkpoint; with test.ssim=true info.yaml gains `ssim: {view: value}` and `mean_ssim` -- the
+    test (TestImages of the latest checkpoint; with test.distortion=true info.yaml gains `distortion: {view: mean}` and
+    `mean_distortion`, the distortion loss of the views' rays on their warped intervals; with test.ssim=true `ssim: {view: value}` and `mean_ssim` -- the
     reference's rgb_ssim of scripts/eval.py on the device, metrics.py -- and with test.write_images=true the reference's
     test_images/color_<iter>_<idx>.png, depth_... and oct_depth_... are written), render_path (RenderPath over poses_render.npy), extract_mesh (with is_continue:
     <exp>/meshes/<iter>_<res>.ply, the density iso-surface in the data set's world frame, or with mesh.source=tsdf the surface fused from
@@ -151,7 +152,7 @@ def main(argv=None):
             os.symlink(os.path.join(d, f), link)
 
     from . import metrics
-    topt = metrics.launcher_options(cfg)  # (test.ssim / test.write_images: a bad value raises before anything is trained or rendered)
+    topt = metrics.launcher_options(cfg)  # (test.ssim / test.write_images / test.distortion: a bad value raises before anything is trained or rendered)
 
     def test_images():  # ExpRunner.cpp:343-383
         if rank != 0:
@@ -178,12 +179,21 @@ def main(argv=None):
         if topt["ssim"]:
             out["ssim"] = ssims
             out["mean_ssim"] = sum(ssims.values()) / len(ssims) if ssims else 0.
+        if topt["distortion"]:  # the mean over a view's rays of runner.ray_distortion (the distortion loss on the warped intervals)
+            dist = {}
+            for i in sc["test_set"]:
+                co, cd, cb = ds.rays_of_camera(int(i))
+                dist[str(int(i))] = float(runner.ray_distortion(co, cd, cb).mean(dtype=torch.float64))
+            out["distortion"] = dist
+            out["mean_distortion"] = sum(dist.values()) / len(dist) if dist else 0.
         os.makedirs(os.path.join(exp_dir, "test_images"), exist_ok=True)
         with open(os.path.join(exp_dir, "test_images", "info.yaml"), "w") as f:
             yaml.safe_dump(out, f)
         print("Mean psnr: %s" % views[-1])
         if topt["ssim"]:
             print("Mean ssim: %s" % out["mean_ssim"])
+        if topt["distortion"]:
+            print("Mean distortion: %s" % out["mean_distortion"])
         return out
 
     try:

@@ -641,6 +641,40 @@ int f2n_weight_var_fwd(void* stream, int n_rays, const float* weights, const int
 int f2n_weight_var_bwd(void* stream, int n_rays, const float* weights, const int32_t* pts_start_end,
                        const float* dvars, float* dweights);
 
+/* Distortion loss on the warped ray intervals: no reference counterpart (mip-NeRF 360, eq. 15, on the coordinate compositing
+ * itself integrates over: the step length dt, sec = sigma * dt).  Sample k of a ray is the interval of length dt_k that follows the
+ * intervals of the ray's earlier surviving samples; m_k is its midpoint, m_{k+1} - m_k = (dt_k + dt_{k+1}) / 2.  Per ray, over its
+ * samples s <= k < e (pts_start_end [R,2]) with weights w [M]:
+ *     dist         = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 dt_i
+ *     d dist/d w_k = 2 sum_j w_j |m_k - m_j| + (2/3) w_k dt_k
+ * evaluated without a cumulative coordinate and without a subtraction.  All arithmetic is fp32, EVERY operation below is one
+ * rounding (never an FMA), every running sum adds left to right in the order written, starting from 0.f:
+ *   forward, k = s .. e-1:   h_k = 0.5f * (dt[k-1] + dt[k])                    (h_s = 0.f)
+ *                            P_k = P_{k-1} + w[k-1]                            (P_s = 0.f: the exclusive running sum of w)
+ *                            D_k = D_{k-1} + P_k * h_k                         (D before s is 0.f)
+ *                            l_k = w[k] * (2.f * D_k) + ((w[k] * w[k]) * dt[k]) * (1.f / 3.f)
+ *                            dist = (((0.f + l_s) + l_{s+1}) + ...) + l_{e-1}
+ *   reverse, k = e-1 .. s:   S_k = S_{k+1} + w[k+1]                            (S_{e-1} = 0.f)
+ *                            U_k = U_{k+1} + S_k * (0.5f * (dt[k] + dt[k+1]))  (U behind e-1 is 0.f; the term of k = e-1 is 0.f)
+ *                            g_k = ddist[ray] * (2.f * (D_k + U_k) + ((2.f / 3.f) * w[k]) * dt[k])
+ * (1.f / 3.f and 2.f / 3.f are the fp32 constants.)  Every term is non-negative for non-negative w and dt, so nothing cancels: the
+ * relative error of dist is below (3n+8) 2^-24 and that of every g_k below (2n+8) 2^-24 for a ray of n samples.
+ * f2n_distortion_fwd writes dist [R] (0.f for an empty ray).  f2n_distortion_bwd writes dweights[k] = g_k for the samples of
+ * non-empty rays -- the rows of empty rays and everything outside [s, e) are untouched -- and, if dist is not NULL, dist [R] with the
+ * bits of f2n_distortion_fwd.  dweights is also the kernel's scratch for D_k between its two walks: it must not alias weights or dt.
+ * A NaN or infinite weight stays inside its own ray.  F2N_ERR_INVALID_ARG: n_rays < 0, or n_rays > 0 and a NULL pointer other than
+ * f2n_distortion_bwd's dist, or dweights == weights or dt.  n_rays == 0: F2N_OK, nothing is touched. */
+int f2n_distortion_fwd(void* stream, int n_rays, const int32_t* pts_start_end, const float* weights, const float* dt,
+                       float* dist /*[R]*/);
+int f2n_distortion_bwd(void* stream, int n_rays, const int32_t* pts_start_end, const float* weights, const float* dt,
+                       const float* ddist /*[R]*/, float* dweights /*[M]: rows of empty rays untouched*/,
+                       float* dist /*[R] or NULL*/);
+/* f2n_loss_add_mean: no reference counterpart.  mean = (float) (sum / (double) n) with sum the fp64 sum of x [n]: work-item t of ONE
+ * workgroup of 256 adds x[t], x[t + 256], ... in that order to its own fp64 accumulator (from 0.0), then a[t] += a[t + off] for
+ * off = 128, 64, .., 1 over t < off.  Then losses[slot] = mean and losses[0] = losses[0] + weight * mean (two fp32 roundings): the
+ * result is a function of the inputs alone.  n < 1, slot outside [1, 7] or a NULL pointer: F2N_ERR_INVALID_ARG. */
+int f2n_loss_add_mean(void* stream, int n, const float* x, float weight, float* losses /*[8]*/, int slot);
+
 /* Seam-level FlexOps (FlexOps.cu:5-93) for callers that keep the reference's op-by-op structure. */
 int f2n_flex_sum_fwd(void* stream, int n_rays, int vec, const float* val, const int32_t* start_end, float* sum);
 int f2n_flex_sum_bwd(void* stream, int n_rays, int vec, const float* dsum, const int32_t* start_end, float* dval);
