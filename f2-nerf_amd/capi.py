@@ -543,7 +543,7 @@ def compact_samples_src(n_rays, old_se, new_se, mask, pts, dirs, dt, t, anchors,
     _ck(lib().f2n_compact_samples_src(_stream(), _i(n_rays), _p(old_se, "i32"), _p(new_se, "i32"), _p(mask, "i32"),
                                       _p(pts, "f32"), _p(dirs, "f32"), _p(dt, "f32"), _p(t, "f32"), _p(anchors, "i32"),
                                       _p(o_pts, "f32"), _p(o_dirs, "f32"), _p(o_dt, "f32"), _p(o_t, "f32"),
-                                      _p(o_anchors, "i32"), _p(o_src, "i32"), _p(o_vol, "i32", True), _p(ray_val, "i32", True),
+                                      _p(o_anchors, "i32", True), _p(o_src, "i32"), _p(o_vol, "i32", True), _p(ray_val, "i32", True),
                                       _p(o_ray_val, "i32", True)), "f2n_compact_samples_src")
 
 

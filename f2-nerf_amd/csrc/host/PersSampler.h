@@ -151,6 +151,8 @@ class PersSampler : public PtsSampler {
     int n_also = 0;
   };
   void FinishOctUpdate(const ScanArgs* scan = nullptr);
+  // (Votes off the main queue, Renderer::votes_off_main_: UpdateOctNodes is called with the tail stream current, behind a VoteBuffer()
+  // call on the main stream -- a rebuild of the buffer is torch work of the current stream.)
   Tensor& VoteBuffer();
   // [K, N] of the sampling calls in flight, written by the scan kernel itself (MappedHost.h); eight rotating pairs: up to
   // Renderer::kPendingSlots prefetched batches and one synchronous GetSamples hold a pair each, a dropped batch's kernels are

@@ -192,6 +192,7 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
   F2N_HOST_SCOPE("step.sample_and_filter");
   auto* gdp = global_data_pool_;
   ResolvePendingCount();
+  JoinTailVotes();  // (a step that left its stat update on the tail stream and did not end in TrainForwardBackward's wait)
   if (gdp->mode_ == RunningMode::TRAIN) DebugSkew(2);
   auto* field = static_cast<Hash3DAnchored*>(scene_field_.get());
   const bool train = gdp->mode_ == RunningMode::TRAIN;
@@ -440,8 +441,22 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
     }
     Tensor weights = torch::empty({n_all_pts}, DevF32()), alphas = torch::empty({n_all_pts}, DevF32());
     Tensor mask = torch::empty({n_all_pts}, DevI32()), kept = torch::empty({n_rays}, DevI32());
-    // training: the occupancy votes (first half of UpdateOctNodes, Renderer.cpp:140-149) ride in the early-stop launch
-    if (train) ps->EarlyStopAndVote(sample_result_, f0p, weights, alphas, mask, kept);
+    // Votes off the main queue (Renderer.h: votes_off_main_): which steps
+    const bool votes_off = train && async_count && votes_off_main_ != 0 && dp_world_ == 1 && !ps->occupancy_sync_hook_ &&
+                           !ps->MaintenanceDue(0) && !digest_taps_ && (votes_off_main_ == 1 || !two_deep);
+    Tensor new_se = torch::empty({n_rays, 2}, DevI32()), total = torch::empty({1}, DevI32());
+    n_kept_words_.Ensure(2);  // [0] data-parallel: the previous step's count summed over the ranks; [1] this step's count
+    // training: the occupancy votes (first half of UpdateOctNodes, Renderer.cpp:140-149) ride in the early-stop launch -- unless
+    // they are cast on the tail stream further down
+    if (votes_off) {
+      // the early stop alone (f2n_early_stop, 256-thread blocks) and the survivor scan in a launch of its own.  (One launch whose last
+      // block to arrive scans was built and measured: the release every block needs before its arrival writes the XCD's L2 back,
+      // 46 us in the step against 25 + 5 for these two -- profiles/votes_off_main.txt.)
+      ps->VoteBuffer();  // (a rebuild is queued here, on the main stream in front of the event the votes' stream waits for)
+      F2N_TIMED_CALL("early_stop", f2n_early_stop(st, n_rays, I32P(sample_result_.pts_idx_bounds), f0p, 1, F32P(sample_result_.dt),
+                              F32P(weights), F32P(alphas), I32P(mask), I32P(kept)));
+      F2N_CALL(f2n_segment_scan_ex(st, n_rays, I32P(kept), I32P(new_se), I32P(total), n_kept_words_.Dev(1), nullptr, 0));
+    } else if (train) ps->EarlyStopAndVote(sample_result_, f0p, weights, alphas, mask, kept);
     else F2N_TIMED_CALL("early_stop", f2n_early_stop(st, n_rays, I32P(sample_result_.pts_idx_bounds), f0p, 1, F32P(sample_result_.dt),
                             F32P(weights), F32P(alphas), I32P(mask), I32P(kept)));
     // The occupancy update (Renderer.cpp:140-149) is all the NEXT batch's sampling waits for, and that sampling is the longer
@@ -449,8 +464,10 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
     // stream -- before the survivor scan, whose result nothing waits for.  (Data-parallel: the survivor count rides in the
     // occupancy exchange, so the scan stays first; synchronous steps: the host is about to wait for the count.)
     const bool octree_first = train && async_count;
-    auto octree_update_issued = [&]() {
-      octree_ready_ev_.record();  // everything the NEXT step's ray sampling depends on has been issued ...
+    auto octree_update_issued = [&](c10::hip::HIPStreamMasqueradingAsCUDA* on = nullptr) {  // (on: the stream that holds the update)
+      // everything the NEXT step's ray sampling depends on has been issued ...
+      if (on != nullptr) octree_ready_ev_.record(*on);
+      else octree_ready_ev_.record();
       // ... so the speculatively sampled batch of the next step is repaired and packed now (a batch for the step after it
       // stays as it is: it is repaired behind the NEXT stat update, against every death since it was walked)
       const int nslot = next_batch_.valid ? FindPending(next_batch_.rays_o, next_batch_.rays_d) : -1;
@@ -462,10 +479,33 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
         f();
       }
     };
-    Tensor new_se = torch::empty({n_rays, 2}, DevI32()), total = torch::empty({1}, DevI32());
-    n_kept_words_.Ensure(2);  // [0] data-parallel: the previous step's count summed over the ranks; [1] this step's count
     bool scan_issued = false;
-    if (octree_first) {
+    if (votes_off) {
+      // ONE event behind the early stop and the scan: the tail stream's votes wait for it, and so does the host's read of the count
+      early_stop_ev_.record();
+      auto* tail = TailStream();
+      early_stop_ev_.block(*tail);
+      // the tail stream reads sample_result_'s bounds / anchors and weights / alphas: all four are handed to the RenderFront below
+      // and outlive the main stream's wait for octree_ready_ev_ (TrainForwardBackward)
+      TORCH_CHECK(!ps->occupancy_sync_hook_ && !ps->MaintenanceDue(0), "votes off the main queue: not on a step with an exchange or octree maintenance");
+      fr.votes_weights = weights;
+      fr.votes_alphas = alphas;
+      fr.votes_deferred = true;
+      // (a step that throws between here and TrainForwardBackward's join destroys `fr`: the main stream then waits for the tail stream
+      // before weights / alphas go back to its pool -- JoinTailVotes() does nothing once the step's own join has run)
+      fr.votes_join = std::shared_ptr<void>(nullptr, [this](void*) { try { JoinTailVotes(); } catch (...) {} });
+      tail_votes_pending_ = true;
+      {
+        // UpdateOctNodes itself with the tail stream current: f2n_oct_mark_visit, then FinishOctUpdate, of which the stat update
+        // (f2n_oct_update_stats_ex with the epoch stamp) is all that is left on a step with no exchange hook and no maintenance due.
+        // The vote buffer was prepared on the main stream above: nothing is allocated or rebuilt under the guard.
+        c10::hip::HIPStreamGuardMasqueradingAsCUDA guard(*tail);
+        ps->UpdateOctNodes(sample_result_, weights, alphas);
+      }
+      n_votes_off_main_steps_++;
+      scan_issued = true;
+      octree_update_issued(tail);  // (octree_ready_ev_ on the tail stream: its waiters -- the side streams -- wait on that event)
+    } else if (octree_first) {
       // the survivor scan rides in the stat update's launch (f2n_oct_update_stats_scan: one dependent launch less on the main queue)
       PersSampler::ScanArgs sa;
       sa.n = n_rays; sa.counts = I32P(kept); sa.start_end = I32P(new_se); sa.total = I32P(total);
@@ -496,7 +536,7 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
       F2N_CALL(f2n_segment_scan_ex(st, n_rays, I32P(kept), I32P(new_se), I32P(total), n_kept_words_.Dev(1), nullptr, 0));
     }
     // (octree_first: octree_ready_ev_ was recorded behind the launch that holds the scan -- the count hides behind that recording)
-    kept_wait_ev_ = scan_issued ? &octree_ready_ev_ : &n_kept_ev_;
+    kept_wait_ev_ = votes_off ? &early_stop_ev_ : scan_issued ? &octree_ready_ev_ : &n_kept_ev_;
     if (!scan_issued) n_kept_ev_.record();
     if (digest_taps_ && train) DigestTap(TAP_SURVIVORS, new_se);
     if (dp_lagged) {  // this step's count: summed over the ranks inside the NEXT step's occupancy exchange (in place)
@@ -539,7 +579,9 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
     es.dirs = torch::empty({n_kept, 3}, DevF32());
     es.dt = torch::empty({n_kept}, DevF32());
     es.t = torch::empty({n_kept}, DevF32());
-    es.anchors = torch::empty({n_kept, 3}, DevI32());
+    // (the streaming training step reads vol_all of the survivors' anchors and nothing else: no array, no stores)
+    const bool want_anchors = !(train && fr.dyn);
+    if (want_anchors) es.anchors = torch::empty({n_kept, 3}, DevI32());
     es.first_oct_dis = sample_result_.first_oct_dis;
     es.pts_idx_bounds = new_se;
     src_rows = torch::empty({std::max(n_kept, 1)}, DevI32());
@@ -554,7 +596,7 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
     F2N_TIMED_CALL("compact_samples", f2n_compact_samples_src(st, n_rays, I32P(sample_result_.pts_idx_bounds), I32P(new_se), I32P(mask),
                                  F32P(sample_result_.pts), F32P(sample_result_.dirs), F32P(sample_result_.dt),
                                  F32P(sample_result_.t), I32P(sample_result_.anchors), F32P(pts_all) + 3 * so, F32P(es.dirs),
-                                 F32P(es.dt), F32P(es.t), I32P(es.anchors), I32P(src_rows), I32P(vol_all) + so,
+                                 F32P(es.dt), F32P(es.t), want_anchors ? I32P(es.anchors) : nullptr, I32P(src_rows), I32P(vol_all) + so,
                                  want_emb ? I32P(emb_contig) : nullptr, want_emb ? I32P(fr.sample_emb_idx) : nullptr));
     if (train) {
       if (!fr.dyn) {
@@ -577,6 +619,8 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
     fr.presamples_keepalive = std::move(sample_result_);
     fr.consumed_deferred = true;
     consumed_side_samples_ = false;
+  } else if (fr.votes_deferred) {
+    fr.presamples_keepalive = std::move(sample_result_);  // (main-stream buffers the tail stream's votes read: see RenderFront)
   }
   sample_result_ = SampleResultFlex();  // drop the pre-early-stop buffers
   if (consumed_side_samples_) {         // (see above: every reader of the side stream's sample buffers has been queued)
@@ -588,6 +632,12 @@ RenderFront Renderer::SampleAndFilter(const Tensor& rays_o, const Tensor& rays_d
   // already, and nothing since has touched the tree: no second packet)
   if (!streaming_train) octree_ready_ev_.record();
   return fr;
+}
+
+void Renderer::JoinTailVotes() {
+  if (!tail_votes_pending_) return;
+  octree_ready_ev_.block(c10::hip::getCurrentHIPStreamMasqueradingAsCUDA());
+  tail_votes_pending_ = false;
 }
 
 RenderResult Renderer::Render(const Tensor& rays_o, const Tensor& rays_d, const Tensor& bounds, const Tensor& emb_idx) {

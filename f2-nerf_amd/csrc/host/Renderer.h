@@ -63,6 +63,14 @@ struct RenderFront {
   // command processor ~5 us: profiles/r06_event_cost.txt).
   SampleResultFlex presamples_keepalive;
   bool consumed_deferred = false;
+  // Votes off the main queue (Renderer::votes_off_main_): the tail stream's vote walk reads the pre-early-stop bounds / anchors
+  // (presamples_keepalive) and the early stop's weights / alphas, main-stream allocations held here.  TrainForwardBackward makes the
+  // main stream wait for the tail stream's update before it records `consumed` and before any of these is released.
+  Tensor votes_weights, votes_alphas;
+  bool votes_deferred = false;
+  // The same wait for a step that does not get that far (an exception between SampleAndFilter and TrainForwardBackward's join): its
+  // deleter runs Renderer::JoinTailVotes().  Declared behind the tensors above, so destroyed -- and the main stream ordered -- first.
+  std::shared_ptr<void> votes_join;
 };
 
 // The implicit grid of Renderer::DensityGrid: point (ix, iy, iz) = lo + step * i (f2n_oct_locate_warp_grid), n[k] points along axis k.
@@ -403,6 +411,25 @@ class Renderer : public Pipe {
   // writes no row-major copy; the field backward reads the planes (f2n_field_bwd_*_planes).  ExpRunner.prepass_planes_cache;
   // false = the row cache and the _rows calls, bit-identical results.
   bool prepass_planes_cache_ = true;
+  // Occupancy votes and stat update OFF the main queue (ExpRunner.votes_off_main, profiles/votes_off_main.txt).  They feed only the
+  // repair and pack of the NEXT batch, yet sat on the main queue in front of compaction (the fused f2n_early_stop_votes /
+  // f2n_oct_update_stats_scan launches).  On an eligible step -- streaming, single GPU, no exchange hook, no octree maintenance due,
+  // no digest taps -- the main stream runs f2n_early_stop and f2n_segment_scan_ex, records ONE event (early_stop_ev_: the tail stream and the host's
+  // count read wait for it) and goes on with compaction; the device's tail stream casts the votes (f2n_oct_mark_visit), runs the stat
+  // update and records octree_ready_ev_.  0 = never (the fused launches), 1 = every eligible step, 2 = eligible steps of the
+  // one-batch-ahead regime only (not two_deep: there the cycle stat update -> next sampling bounds the step).  Same bytes either way.
+  // Ordering: (a) the tail stream is in order, so the next step's votes follow this step's stat update, which re-arms the vote rows;
+  // (b) the main stream waits for octree_ready_ev_ at the end of the step (TrainForwardBackward) -- before `consumed` is recorded and
+  // before the tensors the votes read are released (RenderFront) -- and at the top of the next SampleAndFilter if that did not happen
+  // (tail_votes_pending_), so whatever replaces the octree or the vote buffer on the main stream later (ProcOctree in a fused step,
+  // LoadStates, InstallOctree, a VoteBuffer() rebuild) is ordered behind the tail stream's last update; (c) the batch draws on the
+  // tail stream keep their `consumed` wait in front (BeginDraw) and queue behind the update.
+  // Default 2: the fresh fox step gains 9 us (1.087 -> 1.078 ms); the two-deep regime keeps its program.
+  int votes_off_main_ = 2;
+  int64_t n_votes_off_main_steps_ = 0;  // steps that took that route
+  at::cuda::CUDAEvent early_stop_ev_;
+  bool tail_votes_pending_ = false;  // the tail stream holds an update the main stream has not been ordered behind yet
+  void JoinTailVotes();              // ... orders it (one wait on octree_ready_ev_)
   bool keep_prepass_outputs_ = false;  // TrainForwardBackward -> SampleAndFilter: this pre-pass is a streaming train step's
   int64_t n_feat_reuse_steps_ = 0;     // steps that took the reuse path (tests: the knob is inert where it must be)
   bool count_pending_ = false;

@@ -255,6 +255,9 @@ TrainOutputs Renderer::TrainForwardBackward(const Tensor& rays_o, const Tensor& 
     DigestTap(TAP_TABLE_GRAD, field->grad_h_);
     DigestTap(TAP_SMALL_GRADS, small_grads_flat_);
   }
+  // votes off the main queue: the tail stream's vote walk is a reader of the pre-early-stop buffers too, and of weights / alphas that
+  // the main stream's pool gets back when `fr` goes -- the main stream is ordered behind the tail stream's update first
+  if (fr.votes_deferred) JoinTailVotes();
   if ((fr.side_pool_buffers || fr.consumed_deferred) && side_shared_) {  // (see RenderFront: their last readers have been queued only now)
     side_shared_->consumed.record();
     side_shared_->seq++;

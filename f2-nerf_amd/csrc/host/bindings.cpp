@@ -794,6 +794,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_property("prepass_planes_cache",  // with reuse: the pre-pass keeps the gather's planes as its feature cache, no row copy (A/B: False = rows, the _rows calls)
                     [](ExpRunner& r) { return r.renderer_->prepass_planes_cache_; },
                     [](ExpRunner& r, bool on) { r.renderer_->prepass_planes_cache_ = on; })
+      .def_property("votes_off_main",  // occupancy votes + stat update on the tail stream, early stop and survivor scan alone on the main queue: 0 never (the fused launches), 1 every eligible step, 2 eligible steps of the one-batch-ahead regime
+                    [](ExpRunner& r) { return r.renderer_->votes_off_main_; },
+                    [](ExpRunner& r, int mode) {
+                      if (mode < 0 || mode > 2) throw std::invalid_argument("votes_off_main: 0, 1 or 2");
+                      r.renderer_->votes_off_main_ = mode;
+                    })
+      .def_property_readonly("votes_off_main_steps", [](ExpRunner& r) { return r.renderer_->n_votes_off_main_steps_; })  // steps that took that route
       .def_property_readonly("prepass_reuse_steps", [](ExpRunner& r) { return r.renderer_->n_feat_reuse_steps_; })  // steps that took that path
       .def_property("scatter_producer",  // f2n_set_scatter_producer: 1 = hash constants in LDS (default), 0 = the non-staged instantiation (A/B knob; per process)
                     [](ExpRunner&) { return g_scatter_producer; },

@@ -84,7 +84,10 @@ __global__ __launch_bounds__(256) void compact_kernel(int n_rays, const int32_t*
       for (int c = 0; c < 3; c++) {
         o_pts[3 * (size_t) k + c] = pts[3 * (size_t) i + c];
         o_dirs[3 * (size_t) k + c] = dirs[3 * (size_t) i + c];
-        o_anchors[3 * (size_t) k + c] = anchors[3 * (size_t) i + c];
+      }
+      if (o_anchors != nullptr) {  // (a streaming training step reads only o_vol of the survivors' anchors)
+#pragma unroll
+        for (int c = 0; c < 3; c++) o_anchors[3 * (size_t) k + c] = anchors[3 * (size_t) i + c];
       }
       o_dt[k] = dt[i];
       o_t[k] = t[i];

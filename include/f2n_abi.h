@@ -600,7 +600,8 @@ int f2n_early_stop_votes(void* stream, int n_rays, const int32_t* pts_start_end,
                          int anchor_stride, int32_t* w_adder, int32_t* a_adder, int32_t* mark, int32_t* visit_cnt);
 
 /* Compaction of the surviving samples (Renderer.cpp:128-135: the five index-gathers).  Sample order is
- * preserved; new_start_end comes from f2n_segment_scan(kept). */
+ * preserved; new_start_end comes from f2n_segment_scan(kept).  f2n_compact_samples_src: o_anchors may be NULL (the
+ * compacted anchors are then not written: a streaming training step reads only o_vol of them). */
 int f2n_compact_samples(void* stream, int n_rays, const int32_t* old_start_end, const int32_t* new_start_end,
                         const int32_t* mask, const float* pts, const float* dirs, const float* dt, const float* t,
                         const int32_t* anchors, float* o_pts, float* o_dirs, float* o_dt, float* o_t,
