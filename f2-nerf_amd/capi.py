@@ -1471,3 +1471,95 @@ def mesh_from_grid_masked(grid, valid, lo=(0.0, 0.0, 0.0), step=1.0, level=0.0):
         _ck(lib().f2n_mesh_emit(_stream(), _i(nx), _i(ny), _i(nz), _p(grid, "f32"), _f(level), _lo3(lo), _f(step), _p(mask, "u8"),
                                 _p(vse, "i32"), _p(fse, "i32"), _p(verts, "f32"), _p(faces, "i32")), "f2n_mesh_emit")
     return verts, faces
+
+
+# ---------------------------------------------------------------- sparse meshing on bricks (include/f2n_abi.h)
+def _brick_counts(n, B):
+    """(nbx, nby, nbz) of the virtual grid n = (nx, ny, nz); ValueError for what the library refuses (F2N_ERR_INVALID_ARG / _UNSUPPORTED)."""
+    if B not in (4, 8, 16):
+        raise ValueError("brick size must be 4, 8 or 16, got %r" % (B,))
+    if len(n) != 3 or any(int(v) < 2 or int(v) > (1 << 19) for v in n):
+        raise ValueError("the grid must have 2 .. 2^19 points per axis")
+    nb = tuple((int(v) - 1 + B - 1) // B for v in n)
+    if nb[0] * nb[1] * nb[2] > 0x7fffffff:
+        raise ValueError("the grid has %d bricks; at most 2^31 - 1 are supported" % (nb[0] * nb[1] * nb[2]))
+    return nb
+
+
+def brick_mark(tree_nodes, lo, step, n, B):
+    """flags [nbz, nby, nbx] uint8: 1 for the bricks of B^3 cells of the virtual grid (lo, step, n = (nx, ny, nz)) whose closed box can
+    hold a non-empty point of the octree `tree_nodes` (uint8, 64 B per node) -- f2n_brick_mark, a pure function of its arguments."""
+    nb = _brick_counts(n, B)
+    flags = torch.empty((nb[2], nb[1], nb[0]), dtype=torch.uint8, device=tree_nodes.device)
+    _ck(lib().f2n_brick_mark(_stream(), _p(tree_nodes, "u8"), _lo3(lo), _f(step), _i(n[0]), _i(n[1]), _i(n[2]), _i(B), _p(flags, "u8")),
+        "f2n_brick_mark")
+    return flags
+
+
+def locate_warp_bricks(brick_ids, lo, step, n, B, tree_nodes, transes):
+    """(warped [m,3], anchors [m,3] int32), m = len(brick_ids) (B+1)^3: f2n_oct_locate_warp_grid for the corners of the listed bricks, brick
+    major, local x fastest; a corner outside the grid is an empty point (f2n_oct_locate_warp_bricks)."""
+    _brick_counts(n, B)
+    m = int(brick_ids.numel()) * (B + 1) ** 3
+    warped = torch.empty((m, 3), dtype=torch.float32, device=brick_ids.device)
+    anchors = torch.empty((m, 3), dtype=torch.int32, device=brick_ids.device)
+    _ck(lib().f2n_oct_locate_warp_bricks(_stream(), _lo3(lo), _f(step), _i(n[0]), _i(n[1]), _i(n[2]), _i(B), _i(brick_ids.numel()),
+                                         _p(brick_ids, "i32", m == 0), _p(tree_nodes, "u8"), _p(transes, "u8"), _p(warped, "f32", m == 0),
+                                         _p(anchors, "i32", m == 0)), "f2n_oct_locate_warp_bricks")
+    return warped, anchors
+
+
+def mesh_from_bricks(values, brick_ids, n, lo, step, level, B, batch_bricks=0):
+    """(verts [V,3], faces [F,3] int32) of values [n_bricks, (B+1)^3] float32 for brick_ids [n_bricks] (any order, each id once):
+    f2n_brick_mesh_count -> cumsum (int64) -> f2n_brick_mesh_emit per batch of batch_bricks bricks (0: one batch), then the plumbing of the
+    host's BrickMeshAssemble: vertices sorted by key, faces = searchsorted(sorted keys, face_vert_keys) sorted by face key -- the bits of
+    mesh_from_grid on the dense grid when the list holds every brick with a value on either side of the level.  ValueError: a brick size
+    outside {4, 8, 16}, a brick id outside the grid or listed twice, a list that lacks the owner of a face's vertex, more than
+    2^31 - 1 vertices or faces."""
+    nb = _brick_counts(n, B)
+    total, P, dev = nb[0] * nb[1] * nb[2], (B + 1) ** 3, values.device
+    ids = brick_ids.to(torch.int64).reshape(-1)
+    nbr = int(ids.numel())
+    if nbr:
+        s = torch.sort(ids)[0]
+        if int(s[0]) < 0 or int(s[-1]) >= total:
+            raise ValueError("a brick id lies outside the grid's %d bricks" % total)
+        if nbr > 1 and bool((s[1:] == s[:-1]).any()):
+            raise ValueError("a brick id is listed twice")
+    ids = ids.to(torch.int32).contiguous()
+    if values.numel() != nbr * P:
+        raise F2nError("values must be [n_bricks, (B+1)^3]")
+    values = values.reshape(nbr, P)
+    per = int(batch_bricks) if batch_bricks > 0 else max(nbr, 1)
+    i64 = dict(dtype=torch.int64, device=dev)
+    vk, vv, fk, fv = [torch.empty(0, **i64)], [torch.empty((0, 3), dtype=torch.float32, device=dev)], [torch.empty(0, **i64)], [torch.empty((0, 3), **i64)]
+    for j0 in range(0, nbr, per):
+        b, val = ids[j0:j0 + per].contiguous(), values[j0:j0 + per].contiguous()
+        c = int(b.numel())
+        vc, fc = torch.empty(c, dtype=torch.int32, device=dev), torch.empty(c, dtype=torch.int32, device=dev)
+        _ck(lib().f2n_brick_mesh_count(_stream(), _i(n[0]), _i(n[1]), _i(n[2]), _i(B), _i(c), _p(b, "i32"), _p(val, "f32"), _f(level),
+                                       _p(vc, "i32"), _p(fc, "i32")), "f2n_brick_mesh_count")
+        vend, fend = torch.cumsum(vc, 0, dtype=torch.int64), torch.cumsum(fc, 0, dtype=torch.int64)
+        nv, nf = int(vend[-1]), int(fend[-1])
+        if nv == 0 and nf == 0:
+            continue
+        # (a batch may own vertices but no face, or the other way round: the emit wants its four outputs, at least one row each)
+        bvk, bvv = torch.empty(max(nv, 1), **i64), torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev)
+        bfk, bfv = torch.empty(max(nf, 1), **i64), torch.empty((max(nf, 1), 3), **i64)
+        vstart, fstart = (vend - vc).contiguous(), (fend - fc).contiguous()  # (named: they must outlive the call's argument list)
+        _ck(lib().f2n_brick_mesh_emit(_stream(), _i(n[0]), _i(n[1]), _i(n[2]), _i(B), _i(c), _p(b, "i32"), _p(val, "f32"), _f(level), _lo3(lo),
+                                      _f(step), _p(vstart, "i64"), _p(fstart, "i64"), _p(bvk, "i64"), _p(bvv, "f32"), _p(bfk, "i64"),
+                                      _p(bfv, "i64")), "f2n_brick_mesh_emit")
+        vk.append(bvk[:nv]), vv.append(bvv[:nv]), fk.append(bfk[:nf]), fv.append(bfv[:nf])
+    keys, verts, fkeys, fverts = torch.cat(vk), torch.cat(vv), torch.cat(fk), torch.cat(fv)
+    if keys.numel() > 0x7fffffff or fkeys.numel() > 0x7fffffff:
+        raise ValueError("the mesh has %d vertices and %d faces; at most 2^31 - 1 of each are supported" % (keys.numel(), fkeys.numel()))
+    skeys, perm = torch.sort(keys)
+    verts = verts[perm].contiguous()
+    if fkeys.numel() == 0:
+        return verts, torch.empty((0, 3), dtype=torch.int32, device=dev)
+    want = fverts.reshape(-1)
+    at = torch.searchsorted(skeys, want).clamp_(max=max(int(skeys.numel()) - 1, 0))
+    if skeys.numel() == 0 or not bool((skeys[at] == want).all()):
+        raise ValueError("the brick list lacks the owner of a face's vertex")
+    return verts, at.to(torch.int32).reshape(-1, 3)[torch.argsort(fkeys)].contiguous()

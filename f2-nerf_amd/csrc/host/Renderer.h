@@ -85,6 +85,24 @@ std::tuple<Tensor, Tensor> MeshFromGrid(const Tensor& grid, float level, const f
 // The same with a uint8 mask [nz, ny, nx] of the grid points that carry a value (f2n_mesh_count_masked): faces only from cells whose
 // eight corners are valid, vertices only where a face uses them
 std::tuple<Tensor, Tensor> MeshFromGridMasked(const Tensor& grid, const Tensor& valid, float level, const float lo[3], float step);
+// Sparse meshing on bricks of B^3 cells of the virtual grid (lo, step, n = (nx, ny, nz)); include/f2n_abi.h, "Sparse mesh extraction
+// on bricks".  std::invalid_argument: B outside {4, 8, 16}, a grid of 2^31 bricks or more, a brick id outside the grid or listed twice,
+// a brick list that lacks the owner of a face's vertex, more than 2^31 - 1 vertices or faces.
+// BrickMark: flags [nbz, nby, nbx] uint8 of f2n_brick_mark for the octree records tree_nodes (uint8, 64 B per node).
+Tensor BrickMark(const Tensor& tree_nodes, const float lo[3], float step, const int n[3], int B);
+// One batch of listed bricks through f2n_brick_mesh_count -> cumsum (int64) -> f2n_brick_mesh_emit: keyed vertices and faces
+struct BrickMeshPart {
+  Tensor vert_keys, verts, face_keys, face_vert_keys;  // [nv] int64, [nv,3] f32, [nf] int64, [nf,3] int64
+  int64_t meshed_bricks = 0;                           // bricks of the batch that own a vertex or a face
+};
+BrickMeshPart BrickMeshBatch(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step, float level, int B);
+// The parts as one mesh in f2n_mesh_emit's order: vertices sorted by key, faces = searchsorted(sorted keys, face_vert_keys) as int32,
+// sorted by face key
+std::tuple<Tensor, Tensor> BrickMeshAssemble(const std::vector<BrickMeshPart>& parts);
+// (verts, faces) of values [n_bricks, (B+1)^3] for brick_ids [n_bricks] (any order, each id once); batch_bricks > 0: in batches of
+// that many bricks (the same mesh)
+std::tuple<Tensor, Tensor> MeshFromBricks(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step,
+                                          float level, int B, int64_t batch_bricks = 0);
 // TSDF fusion on any grid (f2n_tsdf_integrate / f2n_tsdf_finalize).  TsdfIntegrate adds depth [V,h,w] (conf [V,h,w] or undefined) seen
 // from poses [V,3,4] / intri [V,3,3] / dist [V,4] into the device tensors S, W [nz, ny, nx] IN PLACE; TsdfFinalize: (g, valid uint8).
 void TsdfIntegrate(const Tensor& S, const Tensor& W, const float lo[3], float step, const Tensor& poses, const Tensor& intri,
@@ -193,8 +211,16 @@ struct MeshRefineOptions {
   float max_step_steps = 0.5f, max_move_steps = 1.0f, tol = 1e-3f;
 };
 
+struct SparseMeshStats {  // Renderer::ExtractMeshSparse
+  int64_t bricks = 0, active_bricks = 0, meshed_bricks = 0;  // of the grid; flagged by BrickMark; owning a vertex or a face
+  int64_t points_evaluated = 0, points_nonempty = 0;         // existing corners of the active bricks' rows; those in a live leaf
+  int64_t batches = 0;
+  int grid[3] = {0, 0, 0};                                   // (nx, ny, nz) of the virtual grid
+};
+
 struct MeshAttrs {  // Renderer::ExtractMeshAttrs; normals / colors are undefined unless asked for
   Tensor verts, faces, normals, colors;
+  SparseMeshStats sparse;  // sparse > 0 only
   int64_t verts_in = -1, faces_in = -1;  // simplify >= 2: the size of the mesh that went into MeshSimplify
   std::vector<std::pair<std::string, double>> refine;  // the refine stage's statistics, in order (empty: the stage was off)
 };
@@ -449,8 +475,14 @@ class Renderer : public Pipe {
   Tensor QueryDensity(const Tensor& world);
   Tensor DensityGrid(const std::vector<float>& lo, const std::vector<float>& hi, int res);
   std::tuple<Tensor, Tensor> ExtractMesh(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level);
-  static GridSpec MakeGridSpec(const std::vector<float>& lo, const std::vector<float>& hi, int res);
+  static GridSpec MakeGridSpec(const std::vector<float>& lo, const std::vector<float>& hi, int res, int max_res = 1024);
   Tensor DensityOfLocated(const Tensor& warped, const Tensor& anchors);
+  // ExtractMesh's mesh, bit for bit, without the dense grid (res up to 8192): BrickMark, then the flagged bricks in ascending order in
+  // batches of max(1, density_slab_points_ / (brick + 1)^3) bricks through f2n_oct_locate_warp_bricks -> DensityOfLocated ->
+  // BrickMeshBatch, then BrickMeshAssemble.  Exact for level >= 0 (a crossing edge then has a non-empty endpoint, and every
+  // non-empty point lies in flagged bricks only); std::invalid_argument for level < 0.  The side-effect contract of QueryDensity.
+  std::tuple<Tensor, Tensor> ExtractMeshSparse(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int brick,
+                                               SparseMeshStats* stats = nullptr);
   // (density [n], rgb [n,3]) at world points seen from the UNIT directions dirs [n,3] (not normalised here): the density of
   // QueryDensity, bit for bit, and the shader's colour for the point's field features without appearance embedding -- what
   // RenderForward computes per sample; zeros where no listed leaf holds the point.  The same side-effect contract as QueryDensity.
@@ -459,9 +491,11 @@ class Renderer : public Pipe {
   // the same density grid, colours = the radiance at each vertex seen along its inward normal ((0, 0, -1) where the normal is 0)
   // normal_source "field": the normals are FieldNormals at the kept vertices (a vertex whose field normal is the zero vector takes
   // its grid normal) and the colours follow them; "grid" (the default): the density grid's normals
+  // sparse in {4, 8, 16}: the mesh comes from ExtractMeshSparse with that brick size (the same bits) and no dense grid exists -- the
+  // normals are FieldNormals alone ((0, 0, 0) where that vanishes); normal_source "grid" with normals or colours: std::invalid_argument
   MeshAttrs ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
                              bool normals, bool colors, const std::string& normal_source = "grid", int simplify = 0,
-                             const MeshRefineOptions& refine = MeshRefineOptions());
+                             const MeshRefineOptions& refine = MeshRefineOptions(), int sparse = 0);
   // Points moved onto the level set sigma = level by a damped Newton iteration on h = ln(sigma) - ln(level) along grad sigma / sigma:
   // `iters` rounds of QueryDensityGrad at the candidates (DensityGradChunk, in slabs), a torch log, f2n_level_step.  A step is at most
   // max_step long and no candidate leaves the ball of radius max_move around its origin (origins undefined: the point's own start).

@@ -306,9 +306,9 @@ GeometryResult Renderer::RenderGeometry(const Tensor& rays_o_in, const Tensor& r
   return out;
 }
 
-GridSpec Renderer::MakeGridSpec(const std::vector<float>& lo, const std::vector<float>& hi, int res) {
+GridSpec Renderer::MakeGridSpec(const std::vector<float>& lo, const std::vector<float>& hi, int res, int max_res) {
   TORCH_CHECK(lo.size() == 3 && hi.size() == 3, "lo / hi must have three coordinates");
-  TORCH_CHECK(res >= 1 && res <= 1024, "resolution must be in [1, 1024]");
+  TORCH_CHECK(res >= 1 && res <= max_res, "resolution must be in [1, ", max_res, "]");
   GridSpec s;
   float ext[3], longest = 0.f;
   for (int k = 0; k < 3; k++) {
@@ -384,6 +384,173 @@ std::tuple<Tensor, Tensor> MeshFromGrid(const Tensor& grid, float level, const f
 std::tuple<Tensor, Tensor> MeshFromGridMasked(const Tensor& grid, const Tensor& valid, float level, const float lo[3], float step) {
   TORCH_CHECK(valid.defined(), "valid is required");
   return MeshFromGridImpl(grid, valid, level, lo, step);
+}
+
+// ---- sparse meshing on bricks (include/f2n_abi.h, "Sparse mesh extraction on bricks") ----------------------------------------
+namespace {
+constexpr int kSparseMaxRes = 8192;
+
+torch::TensorOptions DevI64() { return DevI32().dtype(torch::kInt64); }
+
+// bricks per axis and their number; std::invalid_argument for what f2n_brick_mark refuses
+int64_t BrickCounts(const int n[3], int B, int nb[3]) {
+  if (B != 4 && B != 8 && B != 16) throw std::invalid_argument("brick size must be 4, 8 or 16, got " + std::to_string(B));
+  int64_t total = 1;
+  for (int k = 0; k < 3; k++) {
+    if (n[k] < 2 || n[k] > F2N_BRICK_MAX_POINTS) throw std::invalid_argument("the grid must have 2 .. 2^19 points per axis");
+    nb[k] = (n[k] - 1 + B - 1) / B;
+    total *= nb[k];
+  }
+  if (total > INT32_MAX) throw std::invalid_argument("the grid has " + std::to_string(total) + " bricks; at most 2^31 - 1 are supported");
+  return total;
+}
+
+// brick_ids as a device int32 list, every id inside the grid and listed once
+Tensor CheckedBrickIds(const Tensor& brick_ids, int64_t total) {
+  Tensor ids = brick_ids.to(torch::kCUDA, torch::kInt64).contiguous().view({-1});
+  if (ids.numel() > 0) {
+    Tensor sorted = std::get<0>(torch::sort(ids));
+    Tensor ends = torch::stack({sorted[0], sorted[-1]}).cpu();
+    if (ends.data_ptr<int64_t>()[0] < 0 || ends.data_ptr<int64_t>()[1] >= total)
+      throw std::invalid_argument("a brick id lies outside the grid's " + std::to_string(total) + " bricks");
+    if (ids.numel() > 1 && (sorted.narrow(0, 1, ids.numel() - 1) == sorted.narrow(0, 0, ids.numel() - 1)).any().item<bool>())
+      throw std::invalid_argument("a brick id is listed twice");
+  }
+  return ids.to(torch::kInt32).contiguous();
+}
+}  // namespace
+
+Tensor BrickMark(const Tensor& tree_nodes, const float lo[3], float step, const int n[3], int B) {
+  torch::NoGradGuard g;
+  int nb[3];
+  BrickCounts(n, B, nb);
+  Tensor nodes = tree_nodes.to(torch::kCUDA).contiguous();
+  TORCH_CHECK(nodes.scalar_type() == torch::kUInt8 && nodes.numel() >= 64 && nodes.numel() % 64 == 0, "tree_nodes must be uint8, 64 B per node");
+  Tensor flags = torch::empty({nb[2], nb[1], nb[0]}, torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA));
+  F2N_CALL(f2n_brick_mark(CurStream(), VoidP(nodes), lo, step, n[0], n[1], n[2], B, flags.data_ptr<uint8_t>()));
+  return flags;
+}
+
+BrickMeshPart BrickMeshBatch(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step, float level, int B) {
+  torch::NoGradGuard g;
+  const int64_t nbr = brick_ids.numel(), P = (int64_t) (B + 1) * (B + 1) * (B + 1);
+  TORCH_CHECK(brick_ids.is_cuda() && brick_ids.scalar_type() == torch::kInt32 && brick_ids.is_contiguous(), "brick_ids must be device int32");
+  TORCH_CHECK(values.is_cuda() && values.scalar_type() == torch::kFloat32 && values.is_contiguous() && values.numel() == nbr * P,
+              "values must be device float32 [n_bricks, (B+1)^3]");
+  TORCH_CHECK(nbr <= INT32_MAX, "too many bricks in one batch");
+  BrickMeshPart part;
+  part.vert_keys = torch::empty({0}, DevI64());
+  part.verts = torch::empty({0, 3}, DevF32());
+  part.face_keys = torch::empty({0}, DevI64());
+  part.face_vert_keys = torch::empty({0, 3}, DevI64());
+  if (nbr == 0) return part;
+  Tensor vc = torch::empty({nbr}, DevI32()), fc = torch::empty({nbr}, DevI32());
+  F2N_CALL(f2n_brick_mesh_count(CurStream(), n[0], n[1], n[2], B, (int) nbr, I32P(brick_ids), F32P(values), level, I32P(vc), I32P(fc)));
+  Tensor vend = torch::cumsum(vc, 0, torch::kInt64), fend = torch::cumsum(fc, 0, torch::kInt64);
+  Tensor tot = torch::stack({vend[-1], fend[-1], ((vc > 0) | (fc > 0)).sum()}).cpu();  // the one read-back: the totals size the outputs
+  const int64_t nv = tot.data_ptr<int64_t>()[0], nf = tot.data_ptr<int64_t>()[1];
+  part.meshed_bricks = tot.data_ptr<int64_t>()[2];
+  if (nv == 0 && nf == 0) return part;
+  Tensor vstart = (vend - vc).contiguous(), fstart = (fend - fc).contiguous();
+  // (at least one row each: the emit wants its four outputs, and a batch may own vertices but no face or the other way round)
+  Tensor vk = torch::empty({std::max<int64_t>(nv, 1)}, DevI64()), v = torch::empty({std::max<int64_t>(nv, 1), 3}, DevF32());
+  Tensor fk = torch::empty({std::max<int64_t>(nf, 1)}, DevI64()), fvk = torch::empty({std::max<int64_t>(nf, 1), 3}, DevI64());
+  F2N_CALL(f2n_brick_mesh_emit(CurStream(), n[0], n[1], n[2], B, (int) nbr, I32P(brick_ids), F32P(values), level, lo, step,
+                               vstart.data_ptr<int64_t>(), fstart.data_ptr<int64_t>(), vk.data_ptr<int64_t>(), F32P(v), fk.data_ptr<int64_t>(),
+                               fvk.data_ptr<int64_t>()));
+  part.vert_keys = vk.narrow(0, 0, nv);
+  part.verts = v.narrow(0, 0, nv);
+  part.face_keys = fk.narrow(0, 0, nf);
+  part.face_vert_keys = fvk.narrow(0, 0, nf);
+  return part;
+}
+
+std::tuple<Tensor, Tensor> BrickMeshAssemble(const std::vector<BrickMeshPart>& parts) {
+  torch::NoGradGuard g;
+  std::vector<Tensor> vk, v, fk, fvk;
+  for (const auto& p : parts) {
+    vk.push_back(p.vert_keys);
+    v.push_back(p.verts);
+    fk.push_back(p.face_keys);
+    fvk.push_back(p.face_vert_keys);
+  }
+  if (parts.empty()) return {torch::empty({0, 3}, DevF32()), torch::empty({0, 3}, DevI32())};
+  Tensor keys = torch::cat(vk), verts = torch::cat(v), fkeys = torch::cat(fk), fverts = torch::cat(fvk);
+  const int64_t nv = keys.size(0), nf = fkeys.size(0);
+  if (nv > INT32_MAX || nf > INT32_MAX)
+    throw std::invalid_argument("the mesh has " + std::to_string(nv) + " vertices and " + std::to_string(nf) + " faces; at most 2^31 - 1 of each are supported");
+  auto sorted = torch::sort(keys);
+  const Tensor& skeys = std::get<0>(sorted);
+  verts = verts.index_select(0, std::get<1>(sorted)).contiguous();
+  if (nf == 0) return {verts, torch::empty({0, 3}, DevI32())};
+  if (nv == 0) throw std::invalid_argument("the brick list lacks the owner of a face's vertex");
+  Tensor want = fverts.view({-1});
+  Tensor at = torch::searchsorted(skeys, want).clamp_max(nv - 1);
+  if (!(skeys.index_select(0, at) == want).all().item<bool>()) throw std::invalid_argument("the brick list lacks the owner of a face's vertex");
+  Tensor faces = at.to(torch::kInt32).view({-1, 3}).index_select(0, torch::argsort(fkeys)).contiguous();
+  return {verts, faces};
+}
+
+std::tuple<Tensor, Tensor> MeshFromBricks(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step,
+                                          float level, int B, int64_t batch_bricks) {
+  torch::NoGradGuard g;
+  int nb[3];
+  const int64_t total = BrickCounts(n, B, nb);
+  Tensor ids = CheckedBrickIds(brick_ids, total);
+  const int64_t nbr = ids.numel(), P = (int64_t) (B + 1) * (B + 1) * (B + 1);
+  Tensor vals = values.to(torch::kCUDA, torch::kFloat32).contiguous();
+  TORCH_CHECK(vals.numel() == nbr * P, "values must be [n_bricks, (B+1)^3]");
+  vals = vals.view({nbr, P});
+  const int64_t per = batch_bricks > 0 ? batch_bricks : std::max<int64_t>(nbr, 1);
+  std::vector<BrickMeshPart> parts;
+  for (int64_t j0 = 0; j0 < nbr; j0 += per) {
+    const int64_t c = std::min(per, nbr - j0);
+    parts.push_back(BrickMeshBatch(vals.narrow(0, j0, c), ids.narrow(0, j0, c), n, lo, step, level, B));
+  }
+  return BrickMeshAssemble(parts);
+}
+
+std::tuple<Tensor, Tensor> Renderer::ExtractMeshSparse(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level,
+                                                       int brick, SparseMeshStats* stats) {
+  torch::NoGradGuard g;
+  if (!(level >= 0.f)) throw std::invalid_argument("extract_mesh_sparse: level must be >= 0 (the cull of empty bricks is exact only then)");
+  const GridSpec s = MakeGridSpec(lo, hi, res, kSparseMaxRes);
+  int nb[3];
+  const int64_t total = BrickCounts(s.n, brick, nb);
+  auto& o = *static_cast<PersSampler*>(pts_sampler_.get())->pers_octree_;
+  Tensor flags = BrickMark(o.tree_nodes_gpu_, s.lo, s.step, s.n, brick);
+  Tensor ids = torch::nonzero(flags.view({-1})).view({-1}).to(torch::kInt32).contiguous();  // ascending
+  const int64_t n_active = ids.numel(), S = brick + 1, P = S * S * S;
+  const int64_t per = std::max<int64_t>(1, density_slab_points_ / P);
+  SparseMeshStats st;
+  st.bricks = total;
+  st.active_bricks = n_active;
+  for (int k = 0; k < 3; k++) st.grid[k] = s.n[k];
+  if (n_active > 0) {  // the corners of the listed bricks that exist: per axis min(B + 1, n - b B)
+    Tensor b = ids.to(torch::kInt64), cnt = torch::ones_like(b);
+    Tensor bc[3] = {b % nb[0], torch::floor_divide(b, nb[0]) % nb[1], torch::floor_divide(b, (int64_t) nb[0] * nb[1])};
+    for (int k = 0; k < 3; k++) cnt = cnt * torch::clamp_max(s.n[k] - bc[k] * brick, S);
+    st.points_evaluated = cnt.sum().item<int64_t>();
+  }
+  std::vector<BrickMeshPart> parts;
+  Tensor nonempty = torch::zeros({1}, DevI64());
+  const int64_t cap = std::min(per, std::max<int64_t>(n_active, 1)) * P;
+  Tensor warped = torch::empty({cap, 3}, DevF32()), anchors = torch::empty({cap, 3}, DevI32());
+  for (int64_t j0 = 0; j0 < n_active; j0 += per) {
+    const int64_t c = std::min(per, n_active - j0);
+    Tensor batch = ids.narrow(0, j0, c);
+    Tensor w = warped.narrow(0, 0, c * P), a = anchors.narrow(0, 0, c * P);
+    F2N_CALL(f2n_oct_locate_warp_bricks(CurStream(), s.lo, s.step, s.n[0], s.n[1], s.n[2], brick, (int) c, I32P(batch), VoidP(o.tree_nodes_gpu_),
+                                        VoidP(o.pers_trans_gpu_), F32P(w), I32P(a)));
+    nonempty += (a.select(1, 0) >= 0).sum();
+    Tensor values = DensityOfLocated(w, a);
+    parts.push_back(BrickMeshBatch(values, batch, s.n, s.lo, s.step, level, brick));
+    st.meshed_bricks += parts.back().meshed_bricks;
+    st.batches++;
+  }
+  st.points_nonempty = nonempty.item<int64_t>();
+  if (stats != nullptr) *stats = st;
+  return BrickMeshAssemble(parts);
 }
 
 namespace {
@@ -1014,14 +1181,21 @@ Tensor FaceNormalsF64(const Tensor& verts, const Tensor& faces) {
 
 MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level,
                                      int min_component_faces, bool normals, bool colors, const std::string& normal_source, int simplify,
-                                     const MeshRefineOptions& refine) {
+                                     const MeshRefineOptions& refine, int sparse) {
   torch::NoGradGuard g;
   const bool from_field = normal_source == "field";
   TORCH_CHECK(from_field || normal_source == "grid", "normal_source must be \"grid\" or \"field\", got \"", normal_source, "\"");
-  const GridSpec s = MakeGridSpec(lo, hi, res);
-  Tensor grid = DensityGrid(lo, hi, res);
+  if (sparse != 0 && !from_field && (normals || colors))
+    throw std::invalid_argument("extract_mesh_attrs: sparse extraction builds no dense grid; normals and colours need normal_source=\"field\"");
+  const GridSpec s = MakeGridSpec(lo, hi, res, sparse != 0 ? kSparseMaxRes : 1024);
+  Tensor grid;  // (stays undefined in sparse mode)
   MeshAttrs out;
-  std::tie(out.verts, out.faces) = MeshFromGrid(grid, level, s.lo, s.step);
+  if (sparse != 0) {
+    std::tie(out.verts, out.faces) = ExtractMeshSparse(lo, hi, res, level, sparse, &out.sparse);
+  } else {
+    grid = DensityGrid(lo, hi, res);
+    std::tie(out.verts, out.faces) = MeshFromGrid(grid, level, s.lo, s.step);
+  }
   if (min_component_faces > 1) {
     auto kept = MeshFilterComponents(out.verts, out.faces, min_component_faces);
     out.verts = std::get<0>(kept);
@@ -1083,8 +1257,13 @@ MeshAttrs Renderer::ExtractMeshAttrs(const std::vector<float>& lo, const std::ve
     out.verts = v.contiguous();
   }
   if (!normals && !colors) return out;
-  Tensor nrm = GridNormals(grid, out.verts, s.lo, s.step);
-  if (from_field) {  // the field's own gradient at the vertex; the grid's where that vanishes
+  Tensor nrm;
+  if (sparse != 0) {  // the field's own gradient alone: (0, 0, 0) where it vanishes
+    nrm = FieldNormals(out.verts);
+  } else {
+    nrm = GridNormals(grid, out.verts, s.lo, s.step);
+  }
+  if (from_field && sparse == 0) {  // the field's own gradient at the vertex; the grid's where that vanishes
     Tensor fn = FieldNormals(out.verts);
     nrm = torch::where((fn == 0).all(1, /*keepdim=*/true), nrm, fn).contiguous();
   }

@@ -52,6 +52,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
               F2N_HOST_EXPECTS_ABI, ": rebuild both (python -c 'import __graft_entry__ as g; g.build()')");
   m.attr("abi_version") = F2N_HOST_EXPECTS_ABI;
   auto bounded = [](const BoundedRays& r) { return std::vector<Tensor>{r.origins, r.dirs, r.bounds}; };
+  auto sparse_stats = [](const SparseMeshStats& s) {  // (Renderer::ExtractMeshSparse)
+    py::dict d;
+    d["bricks"] = s.bricks; d["active_bricks"] = s.active_bricks; d["meshed_bricks"] = s.meshed_bricks;
+    d["points_evaluated"] = s.points_evaluated; d["points_nonempty"] = s.points_nonempty; d["batches"] = s.batches;
+    d["grid"] = py::make_tuple(s.grid[0], s.grid[1], s.grid[2]);
+    return d;
+  };
   auto ray_data = [](const std::tuple<BoundedRays, Tensor, Tensor>& t) {
     const auto& r = std::get<0>(t);
     return std::vector<Tensor>{r.origins, r.dirs, r.bounds, std::get<1>(t), std::get<2>(t)};  // + gt colours, image index
@@ -112,10 +119,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readonly("height", &Dataset::height_)
       .def_readonly("width", &Dataset::width_);
   // the implicit grid of ExpRunner.density_grid: (step, nx, ny, nz), point (ix, iy, iz) = lo + step * i (no device needed)
-  m.def("grid_spec", [](const std::vector<float>& lo, const std::vector<float>& hi, int res) {
-    GridSpec s = Renderer::MakeGridSpec(lo, hi, res);
+  m.def("grid_spec", [](const std::vector<float>& lo, const std::vector<float>& hi, int res, int max_res) {
+    GridSpec s = Renderer::MakeGridSpec(lo, hi, res, max_res);
     return py::make_tuple(s.step, s.n[0], s.n[1], s.n[2]);
-  });
+  }, py::arg("lo"), py::arg("hi"), py::arg("res"), py::arg("max_res") = 1024);  // (8192: the virtual grid of extract_mesh_sparse)
+  // sparse meshing on bricks of B^3 cells of the virtual grid (lo, step, n = (nx, ny, nz)): flags [nbz, nby, nbx] uint8 of the bricks
+  // that can hold a non-empty point (f2n_brick_mark; tree_nodes = the octree records as uint8) ...
+  m.def("brick_mark",
+        [](const Tensor& tree_nodes, const std::vector<float>& lo, float step, const std::vector<int>& n, int B) {
+          if (lo.size() != 3 || n.size() != 3) throw std::invalid_argument("lo and n must have three entries");
+          return BrickMark(tree_nodes, lo.data(), step, n.data(), B);
+        },
+        py::arg("tree_nodes"), py::arg("lo"), py::arg("step"), py::arg("n"), py::arg("B"));
+  // ... and (verts, faces) of values [n_bricks, (B+1)^3] for brick_ids [n_bricks] (f2n_brick_mesh_count / _emit, sorted by key): the
+  // bits of mesh_from_grid on the dense grid when the list holds every brick with a value on either side of the level
+  m.def("mesh_from_bricks",
+        [](const Tensor& values, const Tensor& brick_ids, const std::vector<int>& n, const std::vector<float>& lo, float step, float level, int B,
+           int64_t batch_bricks) {
+          if (lo.size() != 3 || n.size() != 3) throw std::invalid_argument("lo and n must have three entries");
+          auto t = MeshFromBricks(values, brick_ids, n.data(), lo.data(), step, level, B, batch_bricks);
+          return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
+        },
+        py::arg("values"), py::arg("brick_ids"), py::arg("n"), py::arg("lo"), py::arg("step"), py::arg("level"), py::arg("B"),
+        py::arg("batch_bricks") = 0);
   // iso-surface of any float32 grid [nz, ny, nx] by marching tetrahedra (f2n_mesh_count / f2n_mesh_emit): (verts, faces)
   m.def("mesh_from_grid",
         [](const Tensor& grid, float level, const std::vector<float>& lo, float step) {
@@ -552,6 +578,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
            },
            py::arg("lo"), py::arg("hi"), py::arg("res"), py::arg("level"))
+      .def("extract_mesh_sparse",  // extract_mesh's bits from the bricks of brick^3 cells that can hold something; res up to 8192
+           [sparse_stats](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int brick) {
+             SparseMeshStats st;
+             std::tuple<Tensor, Tensor> t;
+             {
+               py::gil_scoped_release no_gil;
+               r.FinishPending();
+               t = r.renderer_->ExtractMeshSparse(lo, hi, res, level, brick, &st);
+             }
+             py::dict d;
+             d["verts"] = std::get<0>(t);
+             d["faces"] = std::get<1>(t);
+             d["stats"] = sparse_stats(st);
+             return d;
+           },
+           py::arg("lo"), py::arg("hi"), py::arg("res"), py::arg("level"), py::arg("brick") = 8)
       .def("query_radiance",  // world [n,3], unit dirs [n,3] -> [density [n] (= query_density), rgb [n,3]]; zeros for empty points
            [](ExpRunner& r, const Tensor& world, const Tensor& dirs) {
              py::gil_scoped_release no_gil;
@@ -561,8 +603,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            },
            py::arg("world"), py::arg("dirs"))
       .def("extract_mesh_attrs",  // extract_mesh + floater removal, normals from the density grid, colours along the inward normal
-           [](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
-              bool normals, bool colors, const std::string& normal_source, int simplify, const py::object& refine) {
+           [sparse_stats](ExpRunner& r, const std::vector<float>& lo, const std::vector<float>& hi, int res, float level, int min_component_faces,
+              bool normals, bool colors, const std::string& normal_source, int simplify, const py::object& refine, int sparse) {
              MeshRefineOptions ro;
              if (!refine.is_none()) {  // a dict of the stage's options; an unknown key is an error
                ro.on = true;
@@ -584,11 +626,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                py::gil_scoped_release no_gil;
                r.FinishPending();
                InferenceMode mode(r, ro.on);  // (the projection refuses to run in training mode; without the stage nothing changes)
-               a = r.renderer_->ExtractMeshAttrs(lo, hi, res, level, min_component_faces, normals, colors, normal_source, simplify, ro);
+               a = r.renderer_->ExtractMeshAttrs(lo, hi, res, level, min_component_faces, normals, colors, normal_source, simplify, ro, sparse);
              }
              py::dict d;
              d["verts"] = a.verts;
              d["faces"] = a.faces;
+             if (sparse != 0) d["sparse"] = sparse_stats(a.sparse);
              if (normals) d["normals"] = a.normals;
              if (colors) d["colors"] = a.colors;
              if (simplify >= 2) {  // the size of the mesh before the simplification
@@ -612,7 +655,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("simplify") = 0,  // k >= 2: mesh_simplify on clusters of k^3 grid cells before the attributes are computed
            // a dict (smooth_passes, lam, mu, project, iters, max_step_steps, max_move_steps, tol; {} = the defaults): Taubin smoothing and
            // the projection onto the level set after the simplification, before the attributes; the result gains a "refine" dict
-           py::arg("refine") = py::none())
+           py::arg("refine") = py::none(),
+           // 4, 8 or 16: the mesh from extract_mesh_sparse with that brick size (the same bits, no dense grid; needs normal_source="field"
+           // for normals or colours); the result gains a "sparse" dict, extract_mesh_sparse's stats
+           py::arg("sparse") = 0)
       .def("project_to_level",  // points [n,3] moved onto sigma = level: a dict of points, h_in, h_out (ln(sigma / level)), status, evals
            [](ExpRunner& r, const Tensor& points, float level, int iters, float max_step, float max_move, float tol,
               const c10::optional<Tensor>& origins) {

@@ -271,6 +271,8 @@ int f2n_oct_subdivide(void* stream, int n_nodes, const void* nodes, const int32_
 //            for a single point) -> its perspective warp (f2n_warp), in the anchor layout of GetSamples
 //   density: count -> f2n_segment_scan -> compact of the non-empty points, and the scatter of exp(f0 - 3) back to every point
 //   mesh:    marching tetrahedra on the Kuhn split of every grid cell (six tetrahedra around the (0,0,0)-(1,1,1) diagonal)
+//   bricks:  the same mesh from the bricks of B^3 cells that can hold something: a box-against-octree mark, the locate for the
+//            corners of listed bricks, and the mesher per brick with 64-bit keys in the place of the dense scans
 // =====================================================================================================================
 
 #define F2N_OCT_MAX_DEPTH 32  // a descent longer than this is a corrupt tree: the point is reported empty
@@ -404,6 +406,16 @@ __constant__ int8_t c_tri_count[4] = {0, 1, 1, 2};
 
 __device__ __forceinline__ int64_t corner_index(int x, int y, int z, int nx, int ny) { return ((int64_t) z * ny + y) * nx + x; }
 
+// The rules every mesher of this file shares (f2n_mesh_emit, f2n_brick_mesh_emit): a corner is inside iff g > level ...
+__device__ __forceinline__ bool mesh_inside(float g, float level) { return g > level; }
+
+// ... the vertex of the crossing edge a -> b (a = the lower endpoint) lies at p_a + t (p_b - p_a), t = (level - g_a) / (g_b - g_a) ...
+__device__ __forceinline__ void mesh_edge_point(float level, float ga, float gb, const float pa[3], const float pb[3], float out[3]) {
+  const float s = F2N_DIV_RN(F2N_SUB_RN(level, ga), F2N_SUB_RN(gb, ga));
+#pragma unroll
+  for (int k = 0; k < 3; k++) out[k] = F2N_ADD_RN(pa[k], F2N_MUL_RN(s, F2N_SUB_RN(pb[k], pa[k])));
+}
+
 // (masked meshing, f2n_mesh_count_masked) the cell whose lowest corner is (x, y, z) lies in the grid and all eight of its corners are valid
 __device__ __forceinline__ bool cell_observed(int x, int y, int z, int nx, int ny, int nz, const uint8_t* __restrict__ valid) {
   if (x < 0 || y < 0 || z < 0 || x + 1 >= nx || y + 1 >= ny || z + 1 >= nz) return false;
@@ -423,13 +435,13 @@ __global__ void __launch_bounds__(256) mesh_vert_count_kernel(int nx, int ny, in
   const int64_t c = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= (int64_t) nx * ny * nz) return;
   const int x = (int) (c % nx), y = (int) ((c / nx) % ny), z = (int) (c / ((int64_t) nx * ny));
-  const bool in0 = g[c] > level;
+  const bool in0 = mesh_inside(g[c], level);
   uint32_t m = 0;
 #pragma unroll
   for (int o = 1; o < 8; o++) {
     const int dx = o & 1, dy = (o >> 1) & 1, dz = (o >> 2) & 1;
     if (x + dx >= nx || y + dy >= ny || z + dz >= nz) continue;
-    const bool in1 = g[corner_index(x + dx, y + dy, z + dz, nx, ny)] > level;
+    const bool in1 = mesh_inside(g[corner_index(x + dx, y + dy, z + dz, nx, ny)], level);
     if (in0 == in1) continue;
     if (MASKED) {
       bool used = false;
@@ -450,13 +462,58 @@ __device__ __forceinline__ int cell_mask(int x, int y, int z, int nx, int ny, co
   int m = 0;
 #pragma unroll
   for (int o = 0; o < 8; o++)
-    m |= (g[corner_index(x + (o & 1), y + ((o >> 1) & 1), z + ((o >> 2) & 1), nx, ny)] > level ? 1 : 0) << o;
+    m |= (mesh_inside(g[corner_index(x + (o & 1), y + ((o >> 1) & 1), z + ((o >> 2) & 1), nx, ny)], level) ? 1 : 0) << o;
   return m;  // bit o: cell corner of offset o is inside
 }
 
 __device__ __forceinline__ int tet_inside(int cm, int t) {
   const int a = c_tet_axes[t][0], ab = a | c_tet_axes[t][1];
   return ((cm >> 0) & 1) | (((cm >> a) & 1) << 1) | (((cm >> ab) & 1) << 2) | (((cm >> 7) & 1) << 3);
+}
+
+// ... the number of faces of a cell with the inside mask cm (bit o: the corner of offset o is inside) ...
+__device__ __forceinline__ int cell_face_count(int cm) {
+  int n = 0;
+  if (cm != 0 && cm != 255)
+    for (int t = 0; t < 6; t++) n += c_tri_count[c_tet_case[tet_inside(cm, t)][0]];
+  return n;
+}
+
+// ... and its faces, in the order (tet, triangle), wound outwards: emit(v0, v1, v2) per face, each v = vertex_of(oa, ob), the id of
+// the vertex on the edge between the cell corners of offsets oa and ob (one dominates the other on a Kuhn tetrahedron).
+template <typename Id, typename VertexOf, typename Emit>
+__device__ __forceinline__ void cell_faces(int cm, VertexOf vertex_of, Emit emit) {
+  for (int t = 0; t < 6; t++) {
+    const int a = c_tet_axes[t][0], ab = a | c_tet_axes[t][1];
+    const int mask = tet_inside(cm, t);
+    const int kind = c_tet_case[mask][0];
+    if (kind == 0) continue;
+    // tet vertex v -> cell corner offset (0, a, a|b, 7), without a private array
+    auto off = [a, ab](int v) { return v == 0 ? 0 : v == 1 ? a : v == 2 ? ab : 7; };
+    const int oi = off(c_tet_case[mask][1]), oj = off(c_tet_case[mask][2]), ok = off(c_tet_case[mask][3]),
+              ol = off(c_tet_case[mask][4]);
+    const bool flip = (c_tet_case[mask][5] != 0) != (c_tet_even[t] == 0);
+    Id tri[2][3];
+    int n_tri = 1;
+    if (kind == 1) {
+      tri[0][0] = vertex_of(oi, oj);
+      tri[0][1] = vertex_of(oi, ok);
+      tri[0][2] = vertex_of(oi, ol);
+    } else {
+      const Id vik = vertex_of(oi, ok);
+      const Id vil = vertex_of(oi, ol);
+      const Id vjl = vertex_of(oj, ol);
+      const Id vjk = vertex_of(oj, ok);
+      tri[0][0] = vik; tri[0][1] = vil; tri[0][2] = vjl;
+      tri[1][0] = vik; tri[1][1] = vjl; tri[1][2] = vjk;
+      n_tri = 2;
+    }
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      if (q >= n_tri) break;
+      emit(tri[q][0], flip ? tri[q][2] : tri[q][1], flip ? tri[q][1] : tri[q][2]);
+    }
+  }
 }
 
 template <bool MASKED>
@@ -467,10 +524,7 @@ __global__ void __launch_bounds__(256) mesh_face_count_kernel(int nx, int ny, in
   if (c >= (int64_t) cx * cy * (nz - 1)) return;
   const int x = (int) (c % cx), y = (int) ((c / cx) % cy), z = (int) (c / ((int64_t) cx * cy));
   const int cm = cell_mask(x, y, z, nx, ny, g, level);
-  int n = 0;
-  if (cm != 0 && cm != 255 && (!MASKED || cell_observed(x, y, z, nx, ny, nz, valid)))
-    for (int t = 0; t < 6; t++) n += c_tri_count[c_tet_case[tet_inside(cm, t)][0]];
-  counts[c] = n;
+  counts[c] = cm != 0 && cm != 255 && (!MASKED || cell_observed(x, y, z, nx, ny, nz, valid)) ? cell_face_count(cm) : 0;
 }
 
 __global__ void __launch_bounds__(256) mesh_vert_emit_kernel(int nx, int ny, int nz, const float* __restrict__ g, float level, float lo0,
@@ -492,10 +546,11 @@ __global__ void __launch_bounds__(256) mesh_vert_emit_kernel(int nx, int ny, int
     const int64_t slot = v + __popc(m & ((1u << t) - 1u));
     const int dx = o & 1, dy = (o >> 1) & 1, dz = (o >> 2) & 1;
     const float gb = g[corner_index(x + dx, y + dy, z + dz, nx, ny)];
-    const float s = F2N_DIV_RN(F2N_SUB_RN(level, ga), F2N_SUB_RN(gb, ga));
     const float pb[3] = {grid_coord(lo0, step, x + dx), grid_coord(lo1, step, y + dy), grid_coord(lo2, step, z + dz)};
+    float p[3];
+    mesh_edge_point(level, ga, gb, pa, pb, p);
 #pragma unroll
-    for (int k = 0; k < 3; k++) verts[slot * 3 + k] = F2N_ADD_RN(pa[k], F2N_MUL_RN(s, F2N_SUB_RN(pb[k], pa[k])));
+    for (int k = 0; k < 3; k++) verts[slot * 3 + k] = p[k];
   }
 }
 
@@ -518,39 +573,334 @@ __global__ void __launch_bounds__(256) mesh_face_emit_kernel(int nx, int ny, int
   const int x = (int) (c % cx), y = (int) ((c / cx) % cy), z = (int) (c / ((int64_t) cx * cy));
   const int cm = cell_mask(x, y, z, nx, ny, g, level);
   int64_t f = face_se[c * 2];
-  for (int t = 0; t < 6; t++) {
-    const int a = c_tet_axes[t][0], ab = a | c_tet_axes[t][1];
-    const int mask = tet_inside(cm, t);
-    const int kind = c_tet_case[mask][0];
-    if (kind == 0) continue;
-    // tet vertex v -> cell corner offset (0, a, a|b, 7), without a private array
-    auto off = [a, ab](int v) { return v == 0 ? 0 : v == 1 ? a : v == 2 ? ab : 7; };
-    const int oi = off(c_tet_case[mask][1]), oj = off(c_tet_case[mask][2]), ok = off(c_tet_case[mask][3]),
-              ol = off(c_tet_case[mask][4]);
-    const bool flip = (c_tet_case[mask][5] != 0) != (c_tet_even[t] == 0);
-    int32_t tri[2][3];
-    int n_tri = 1;
-    if (kind == 1) {
-      tri[0][0] = edge_vertex(x, y, z, nx, ny, oi, oj, edge_mask, vert_se);
-      tri[0][1] = edge_vertex(x, y, z, nx, ny, oi, ok, edge_mask, vert_se);
-      tri[0][2] = edge_vertex(x, y, z, nx, ny, oi, ol, edge_mask, vert_se);
-    } else {
-      const int32_t vik = edge_vertex(x, y, z, nx, ny, oi, ok, edge_mask, vert_se);
-      const int32_t vil = edge_vertex(x, y, z, nx, ny, oi, ol, edge_mask, vert_se);
-      const int32_t vjl = edge_vertex(x, y, z, nx, ny, oj, ol, edge_mask, vert_se);
-      const int32_t vjk = edge_vertex(x, y, z, nx, ny, oj, ok, edge_mask, vert_se);
-      tri[0][0] = vik; tri[0][1] = vil; tri[0][2] = vjl;
-      tri[1][0] = vik; tri[1][1] = vjl; tri[1][2] = vjk;
-      n_tri = 2;
-    }
+  cell_faces<int32_t>(
+      cm, [&](int oa, int ob) { return edge_vertex(x, y, z, nx, ny, oa, ob, edge_mask, vert_se); },
+      [&](int32_t v0, int32_t v1, int32_t v2) {
+        faces[f * 3 + 0] = v0;
+        faces[f * 3 + 1] = v1;
+        faces[f * 3 + 2] = v2;
+        f++;
+      });
+}
+
+// ---- sparse meshing on bricks of B^3 cells (include/f2n_abi.h, "Sparse mesh extraction on bricks") -----------------------------
+// The virtual grid is never materialised: a brick is its linear id (x fastest over nb = ceil((n - 1) / B) bricks per axis), its
+// values are the (B + 1)^3 corners b B + l, l in [0, B]^3, local x fastest.
+#define F2N_BRICK_MARK_THREADS 64
+
+struct BrickGrid {
+  float lo[3], step;
+  int n[3], nb[3], B;
+};
+
+__device__ __forceinline__ void brick_coords(const BrickGrid& g, int64_t b, int bc[3]) {
+  bc[0] = (int) (b % g.nb[0]);
+  bc[1] = (int) ((b / g.nb[0]) % g.nb[1]);
+  bc[2] = (int) (b / ((int64_t) g.nb[0] * g.nb[1]));
+}
+
+// flags[b] = the closed box of brick b meets a live leaf.  One thread per brick; the descent keeps (node, next child slot) per level
+// in LDS, [level][thread] -- no private stack, no recursion.  Nodes deeper than F2N_OCT_MAX_DEPTH - 1 are not entered, as in oct_locate.
+__global__ void __launch_bounds__(F2N_BRICK_MARK_THREADS) brick_mark_kernel(BrickGrid g, int64_t n_bricks,
+                                                                           const F2nTreeNode* __restrict__ nodes,
+                                                                           uint8_t* __restrict__ flags) {
+  __shared__ int32_t s_node[F2N_OCT_MAX_DEPTH][F2N_BRICK_MARK_THREADS];
+  __shared__ uint8_t s_next[F2N_OCT_MAX_DEPTH][F2N_BRICK_MARK_THREADS];
+  const int t = threadIdx.x;
+  const int64_t b = (int64_t) blockIdx.x * F2N_BRICK_MARK_THREADS + t;
+  if (b >= n_bricks) return;
+  int bc[3];
+  brick_coords(g, b, bc);
+  float blo[3], bhi[3];
 #pragma unroll
-    for (int q = 0; q < 2; q++) {
-      if (q >= n_tri) break;
-      faces[f * 3 + 0] = tri[q][0];
-      faces[f * 3 + 1] = flip ? tri[q][2] : tri[q][1];
-      faces[f * 3 + 2] = flip ? tri[q][1] : tri[q][2];
-      f++;
+  for (int k = 0; k < 3; k++) {
+    const int i0 = bc[k] * g.B, i1 = min(i0 + g.B, g.n[k] - 1);
+    blo[k] = grid_coord(g.lo[k], g.step, i0);
+    bhi[k] = grid_coord(g.lo[k], g.step, i1);
+  }
+  const F2nTreeNode& root = nodes[0];
+  const float h = root.side_len * .5f;
+  bool meets = true;
+#pragma unroll
+  for (int k = 0; k < 3; k++) meets = meets && bhi[k] >= root.center[k] - h && blo[k] <= root.center[k] + h;  // (NaN: no)
+  uint8_t flag = 0;
+  int d = meets ? 0 : -1;
+  if (meets) {
+    s_node[0][t] = 0;
+    s_next[0][t] = 0;
+  }
+  while (d >= 0) {
+    const int u = s_node[d][t];
+    const int first = s_next[d][t];
+    const F2nTreeNode* nd = nodes + u;
+    // the child slots the box reaches: slot 4 sx + 2 sy + sz with (s_k = 0 and blo_k < c_k) or (s_k = 1 and bhi_k >= c_k)
+    bool any = false;
+    int want = 0;
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      const bool have = nd->childs[c] >= 0;
+      any |= have;
+      bool in = have;
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        const int s = (c >> (2 - k)) & 1;
+        in = in && (s ? bhi[k] >= nd->center[k] : blo[k] < nd->center[k]);
+      }
+      want |= (in ? 1 : 0) << c;
     }
+    if (!any) {  // a node without children
+      if (nd->trans_idx >= 0) {
+        flag = 1;
+        break;
+      }
+      d--;
+      continue;
+    }
+    want &= ~((1 << first) - 1);
+    if (want == 0 || d + 1 >= F2N_OCT_MAX_DEPTH) {
+      d--;
+      continue;
+    }
+    const int c = __ffs(want) - 1;
+    s_next[d][t] = (uint8_t) (c + 1);
+    d++;
+    s_node[d][t] = nd->childs[c];  // (read from memory by its run-time index: nothing private is indexed)
+    s_next[d][t] = 0;
+  }
+  flags[b] = flag;
+}
+
+// oct_locate_warp_kernel<true> for the corners of listed bricks: row (j, l) = brick j of the list, local corner l (x fastest)
+__global__ void __launch_bounds__(256) oct_locate_warp_bricks_kernel(BrickGrid g, int64_t n_total, int64_t n, const int32_t* __restrict__ brick_ids,
+                                                                     const F2nTreeNode* __restrict__ nodes,
+                                                                     const F2nTransInfo* __restrict__ transes, float* __restrict__ out_pts,
+                                                                     int32_t* __restrict__ out_anchors) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int S = g.B + 1, P = S * S * S;
+  const int64_t b = brick_ids[i / P];
+  const int l = (int) (i % P);
+  const int lc[3] = {l % S, (l / S) % S, l / (S * S)};
+  bool exists = b >= 0 && b < n_total;
+  float p[3] = {0.f, 0.f, 0.f};
+  if (exists) {
+    int bc[3];
+    brick_coords(g, b, bc);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const int ik = bc[k] * g.B + lc[k];
+      exists = exists && ik <= g.n[k] - 1;
+      p[k] = grid_coord(g.lo[k], g.step, ik);
+    }
+  }
+  int trans = -1, leaf = -1;
+  if (exists) leaf = oct_locate(nodes, p, &trans);
+  float w[3] = {0.f, 0.f, 0.f};
+  if (leaf >= 0) f2n_warp(transes + trans, p, w);
+  out_pts[i * 3 + 0] = w[0];
+  out_pts[i * 3 + 1] = w[1];
+  out_pts[i * 3 + 2] = w[2];
+  out_anchors[i * 3 + 0] = leaf >= 0 ? trans : -1;
+  out_anchors[i * 3 + 1] = leaf;
+  out_anchors[i * 3 + 2] = 0;
+}
+
+// One brick of the list per workgroup of 256 threads, its values in LDS.
+template <int B>
+struct BrickTile {
+  static constexpr int S = B + 1, P = S * S * S, CELLS = B * B * B;
+  int x0[3];    // the grid index of the local corner (0, 0, 0)
+  bool last[3]; // the last brick of the axis: it owns the local plane B as well (the grid's border plane when n - 1 is a multiple of B)
+  int n[3];
+
+  __device__ __forceinline__ void init(int nx, int ny, int nz, int64_t b) {
+    n[0] = nx, n[1] = ny, n[2] = nz;
+    const int nb0 = (nx - 1 + B - 1) / B, nb1 = (ny - 1 + B - 1) / B, nb2 = (nz - 1 + B - 1) / B;
+    const int bc[3] = {(int) (b % nb0), (int) ((b / nb0) % nb1), (int) (b / ((int64_t) nb0 * nb1))};
+    const int nb[3] = {nb0, nb1, nb2};
+    if (b < 0 || b >= (int64_t) nb0 * nb1 * nb2) n[0] = n[1] = n[2] = 0;  // (no such brick: it owns nothing)
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      x0[k] = bc[k] * B;
+      last[k] = bc[k] == nb[k] - 1;
+    }
+  }
+  __device__ __forceinline__ void stage(const float* __restrict__ values, float* s_val) const {
+    const float* src = values + (int64_t) blockIdx.x * P;
+    for (int i = threadIdx.x; i < P; i += 256) s_val[i] = src[i];
+    __syncthreads();
+  }
+  static __device__ __forceinline__ int local(int lx, int ly, int lz) { return (lz * S + ly) * S + lx; }
+  // bit t: the edge of type t owned by the local corner l crosses the level; 0 for a corner this brick does not own
+  __device__ __forceinline__ uint32_t corner_edges(const float* s_val, int l, float level) const {
+    if (l >= P) return 0;
+    const int lc[3] = {l % S, (l / S) % S, l / (S * S)};
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+      if ((lc[k] >= B && !last[k]) || x0[k] + lc[k] > n[k] - 1) return 0;
+    const bool in0 = mesh_inside(s_val[l], level);
+    uint32_t m = 0;
+#pragma unroll
+    for (int o = 1; o < 8; o++) {
+      const int dx = o & 1, dy = (o >> 1) & 1, dz = (o >> 2) & 1;
+      if (lc[0] + dx > B || lc[1] + dy > B || lc[2] + dz > B) continue;
+      if (x0[0] + lc[0] + dx > n[0] - 1 || x0[1] + lc[1] + dy > n[1] - 1 || x0[2] + lc[2] + dz > n[2] - 1) continue;
+      if (in0 != mesh_inside(s_val[local(lc[0] + dx, lc[1] + dy, lc[2] + dz)], level)) m |= 1u << c_edge_type[o];
+    }
+    return m;
+  }
+  // the inside mask of the owned cell c (local index in [0, B)^3, x fastest), 0 for a cell outside the grid; lc receives its local corner
+  __device__ __forceinline__ int cell_inside(const float* s_val, int c, float level, int lc[3]) const {
+    lc[0] = c % B, lc[1] = (c / B) % B, lc[2] = c / (B * B);
+    if (c >= CELLS) return 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+      if (x0[k] + lc[k] + 1 > n[k] - 1) return 0;
+    int m = 0;
+#pragma unroll
+    for (int o = 0; o < 8; o++)
+      m |= (mesh_inside(s_val[local(lc[0] + (o & 1), lc[1] + ((o >> 1) & 1), lc[2] + ((o >> 2) & 1))], level) ? 1 : 0) << o;
+    return m;
+  }
+};
+
+// sum of v over the block's 256 threads (s_wave: 4 ints of LDS); every thread calls it
+__device__ __forceinline__ int block_sum_256(int v, int* s_wave) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
+  __syncthreads();  // (an earlier use of s_wave is over)
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
+// exclusive prefix sum of v in thread order over the block's 256 threads, *total = the block's sum; every thread calls it
+__device__ __forceinline__ int block_scan_256(int v, int* s_wave, int* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int up = __shfl_up(inc, d);
+    if (lane >= d) inc += up;
+  }
+  __syncthreads();  // (an earlier use of s_wave is over)
+  if (lane == 63) s_wave[w] = inc;
+  __syncthreads();
+  int base = 0, sum = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int s = s_wave[k];
+    base += k < w ? s : 0;
+    sum += s;
+  }
+  *total = sum;
+  return base + inc - v;
+}
+
+template <int B>
+__global__ void __launch_bounds__(256) brick_mesh_count_kernel(int nx, int ny, int nz, const int32_t* __restrict__ brick_ids,
+                                                              const float* __restrict__ values, float level,
+                                                              int32_t* __restrict__ vert_counts, int32_t* __restrict__ face_counts) {
+  using Tile = BrickTile<B>;
+  __shared__ float s_val[Tile::P];
+  __shared__ int s_wave[4];
+  Tile tile;
+  tile.init(nx, ny, nz, brick_ids[blockIdx.x]);
+  tile.stage(values, s_val);
+  int nv = 0, nf = 0;
+  for (int l = threadIdx.x; l < Tile::P; l += 256) nv += __popc(tile.corner_edges(s_val, l, level));
+  for (int c = threadIdx.x; c < Tile::CELLS; c += 256) {
+    int lc[3];
+    nf += cell_face_count(tile.cell_inside(s_val, c, level, lc));
+  }
+  nv = block_sum_256(nv, s_wave);
+  nf = block_sum_256(nf, s_wave);
+  if (threadIdx.x == 0) {
+    vert_counts[blockIdx.x] = nv;
+    face_counts[blockIdx.x] = nf;
+  }
+}
+
+// vertices: local corners in rounds of 256, a block scan per round; within a corner by edge type
+template <int B>
+__global__ void __launch_bounds__(256) brick_vert_emit_kernel(int nx, int ny, int nz, const int32_t* __restrict__ brick_ids,
+                                                             const float* __restrict__ values, float level, float lo0, float lo1, float lo2,
+                                                             float step, const long long* __restrict__ vert_start,
+                                                             long long* __restrict__ vert_keys, float* __restrict__ verts) {
+  using Tile = BrickTile<B>;
+  __shared__ float s_val[Tile::P];
+  __shared__ int s_wave[4];
+  Tile tile;
+  tile.init(nx, ny, nz, brick_ids[blockIdx.x]);
+  tile.stage(values, s_val);
+  const int S = Tile::S;
+  long long v_base = vert_start[blockIdx.x];
+  for (int l0 = 0; l0 < Tile::P; l0 += 256) {
+    const int l = l0 + threadIdx.x;
+    const uint32_t m = tile.corner_edges(s_val, l, level);
+    int total;
+    const long long v = v_base + block_scan_256(__popc(m), s_wave, &total);
+    v_base += total;
+    if (m == 0) continue;  // (m != 0: l < P and the corner is owned)
+    const int lx = l % S, ly = (l / S) % S, lz = l / (S * S);
+    const int x = tile.x0[0] + lx, y = tile.x0[1] + ly, z = tile.x0[2] + lz;
+    const long long corner = corner_index(x, y, z, nx, ny);
+    const float ga = s_val[l];
+    const float pa[3] = {grid_coord(lo0, step, x), grid_coord(lo1, step, y), grid_coord(lo2, step, z)};
+#pragma unroll
+    for (int o = 1; o < 8; o++) {
+      const int t = c_edge_type[o];
+      if (!((m >> t) & 1)) continue;
+      const long long slot = v + __popc(m & ((1u << t) - 1u));
+      const int dx = o & 1, dy = (o >> 1) & 1, dz = (o >> 2) & 1;
+      const float gb = s_val[Tile::local(lx + dx, ly + dy, lz + dz)];
+      const float pb[3] = {grid_coord(lo0, step, x + dx), grid_coord(lo1, step, y + dy), grid_coord(lo2, step, z + dz)};
+      float p[3];
+      mesh_edge_point(level, ga, gb, pa, pb, p);
+      vert_keys[slot] = 8 * corner + t;
+#pragma unroll
+      for (int k = 0; k < 3; k++) verts[slot * 3 + k] = p[k];
+    }
+  }
+}
+
+// faces: owned cells in rounds of 256, a block scan per round; a face names its vertices by their keys
+template <int B>
+__global__ void __launch_bounds__(256) brick_face_emit_kernel(int nx, int ny, int nz, const int32_t* __restrict__ brick_ids,
+                                                             const float* __restrict__ values, float level,
+                                                             const long long* __restrict__ face_start, long long* __restrict__ face_keys,
+                                                             long long* __restrict__ face_vert_keys) {
+  using Tile = BrickTile<B>;
+  __shared__ float s_val[Tile::P];
+  __shared__ int s_wave[4];
+  Tile tile;
+  tile.init(nx, ny, nz, brick_ids[blockIdx.x]);
+  tile.stage(values, s_val);
+  long long f_base = face_start[blockIdx.x];
+  for (int c0 = 0; c0 < Tile::CELLS; c0 += 256) {
+    int lc[3];
+    const int cm = tile.cell_inside(s_val, c0 + threadIdx.x, level, lc);
+    int total;
+    long long f = f_base + block_scan_256(cell_face_count(cm), s_wave, &total);
+    f_base += total;
+    if (cm == 0 || cm == 255) continue;
+    const int x = tile.x0[0] + lc[0], y = tile.x0[1] + lc[1], z = tile.x0[2] + lc[2];
+    const long long cell = ((long long) z * (ny - 1) + y) * (nx - 1) + x;
+    int ordinal = 0;
+    cell_faces<long long>(
+        cm,
+        [&](int oa, int ob) {
+          const int low = (oa & ob) == oa ? oa : ob;
+          return 8 * (long long) corner_index(x + (low & 1), y + ((low >> 1) & 1), z + ((low >> 2) & 1), nx, ny) + c_edge_type[oa ^ ob];
+        },
+        [&](long long k0, long long k1, long long k2) {
+          face_keys[f] = 16 * cell + ordinal;
+          face_vert_keys[f * 3 + 0] = k0;
+          face_vert_keys[f * 3 + 1] = k1;
+          face_vert_keys[f * 3 + 2] = k2;
+          f++;
+          ordinal++;
+        });
   }
 }
 
@@ -670,6 +1020,98 @@ int f2n_mesh_emit(void* stream, int nx, int ny, int nz, const float* grid, float
   if (e != F2N_OK) return e;
   hipLaunchKernelGGL(mesh_face_emit_kernel, dim3(f2n_div_up(n_cells, 256)), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, grid, level,
                      edge_mask, vert_start_end, face_start_end, faces);
+  return f2n_launch_status();
+}
+
+// the brick grid of (n, B), or the status that refuses it
+static int brick_grid(const float* lo, float step, int nx, int ny, int nz, int B, BrickGrid* g, int64_t* n_total) {
+  if (nx < 2 || ny < 2 || nz < 2 || nx > F2N_BRICK_MAX_POINTS || ny > F2N_BRICK_MAX_POINTS || nz > F2N_BRICK_MAX_POINTS) return F2N_ERR_INVALID_ARG;
+  if (B != 4 && B != 8 && B != 16) return F2N_ERR_INVALID_ARG;
+  const int n[3] = {nx, ny, nz};
+  for (int k = 0; k < 3; k++) {
+    g->lo[k] = lo != nullptr ? lo[k] : 0.f;
+    g->n[k] = n[k];
+    g->nb[k] = (n[k] - 1 + B - 1) / B;
+  }
+  g->step = step;
+  g->B = B;
+  *n_total = (int64_t) g->nb[0] * g->nb[1] * g->nb[2];
+  return *n_total > 0x7fffffff ? F2N_ERR_UNSUPPORTED : F2N_OK;
+}
+
+int f2n_brick_mark(void* stream, const void* tree_nodes, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int B,
+                   uint8_t* flags) {
+  if (tree_nodes == nullptr || lo == nullptr || flags == nullptr) return F2N_ERR_INVALID_ARG;
+  BrickGrid g;
+  int64_t n_total;
+  const int e = brick_grid(lo, step, nx, ny, nz, B, &g, &n_total);
+  if (e != F2N_OK) return e;
+  hipLaunchKernelGGL(brick_mark_kernel, dim3(f2n_div_up(n_total, F2N_BRICK_MARK_THREADS)), dim3(F2N_BRICK_MARK_THREADS), 0,
+                     (hipStream_t) stream, g, n_total, (const F2nTreeNode*) tree_nodes, flags);
+  return f2n_launch_status();
+}
+
+int f2n_oct_locate_warp_bricks(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int B, int n_bricks,
+                               const int32_t* brick_ids, const void* tree_nodes, const void* transes, float* out_pts_warped,
+                               int32_t* out_anchors) {
+  if (lo == nullptr || n_bricks < 0) return F2N_ERR_INVALID_ARG;
+  BrickGrid g;
+  int64_t n_total;
+  const int e = brick_grid(lo, step, nx, ny, nz, B, &g, &n_total);
+  if (e != F2N_OK) return e;
+  const int64_t n = (int64_t) n_bricks * (B + 1) * (B + 1) * (B + 1);
+  if (n > 0x7fffffff) return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  if (brick_ids == nullptr || tree_nodes == nullptr || transes == nullptr || out_pts_warped == nullptr || out_anchors == nullptr)
+    return F2N_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(oct_locate_warp_bricks_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, g, n_total, n, brick_ids,
+                     (const F2nTreeNode*) tree_nodes, (const F2nTransInfo*) transes, out_pts_warped, out_anchors);
+  return f2n_launch_status();
+}
+
+int f2n_brick_mesh_count(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids, const float* values,
+                         float level, int32_t* vert_counts, int32_t* face_counts) {
+  BrickGrid g;
+  int64_t n_total;
+  const int e = brick_grid(nullptr, 1.f, nx, ny, nz, B, &g, &n_total);
+  if (e != F2N_OK) return e;
+  if (n_bricks < 0) return F2N_ERR_INVALID_ARG;
+  if (n_bricks == 0) return F2N_OK;
+  if (brick_ids == nullptr || values == nullptr || vert_counts == nullptr || face_counts == nullptr) return F2N_ERR_INVALID_ARG;
+#define F2N_BRICK_COUNT(BB)                                                                                                          \
+  hipLaunchKernelGGL(brick_mesh_count_kernel<BB>, dim3(n_bricks), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, brick_ids, values, \
+                     level, vert_counts, face_counts)
+  if (B == 4) F2N_BRICK_COUNT(4);
+  else if (B == 8) F2N_BRICK_COUNT(8);
+  else F2N_BRICK_COUNT(16);
+#undef F2N_BRICK_COUNT
+  return f2n_launch_status();
+}
+
+int f2n_brick_mesh_emit(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids, const float* values,
+                        float level, const float* lo /*host [3]*/, float step, const int64_t* vert_start, const int64_t* face_start,
+                        int64_t* vert_keys, float* verts, int64_t* face_keys, int64_t* face_vert_keys) {
+  if (lo == nullptr) return F2N_ERR_INVALID_ARG;
+  BrickGrid g;
+  int64_t n_total;
+  const int e = brick_grid(lo, step, nx, ny, nz, B, &g, &n_total);
+  if (e != F2N_OK) return e;
+  if (n_bricks < 0) return F2N_ERR_INVALID_ARG;
+  if (n_bricks == 0) return F2N_OK;
+  if (brick_ids == nullptr || values == nullptr || vert_start == nullptr || face_start == nullptr || vert_keys == nullptr ||
+      verts == nullptr || face_keys == nullptr || face_vert_keys == nullptr)
+    return F2N_ERR_INVALID_ARG;
+#define F2N_BRICK_EMIT(BB)                                                                                                            \
+  do {                                                                                                                                \
+    hipLaunchKernelGGL(brick_vert_emit_kernel<BB>, dim3(n_bricks), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, brick_ids, values, \
+                       level, lo[0], lo[1], lo[2], step, (const long long*) vert_start, (long long*) vert_keys, verts);              \
+    hipLaunchKernelGGL(brick_face_emit_kernel<BB>, dim3(n_bricks), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, brick_ids, values, \
+                       level, (const long long*) face_start, (long long*) face_keys, (long long*) face_vert_keys);                   \
+  } while (0)
+  if (B == 4) F2N_BRICK_EMIT(4);
+  else if (B == 8) F2N_BRICK_EMIT(8);
+  else F2N_BRICK_EMIT(16);
+#undef F2N_BRICK_EMIT
   return f2n_launch_status();
 }
 

@@ -17,7 +17,8 @@
     reference's rgb_ssim of scripts/eval.py on the device, metrics.py -- and with test.write_images=true the reference's
     test_images/color_<iter>_<idx>.png, depth_... and oct_depth_... are written), render_path (RenderPath over poses_render.npy), extract_mesh (with is_continue:
     <exp>/meshes/<iter>_<res>.ply, the density iso-surface in the data set's world frame, or with mesh.source=tsdf the surface fused from
-    the training views' rendered depth; mesh.py), extract_points (with
+    the training views' rendered depth; with mesh.sparse=true|4|8|16 the same density mesh from the non-empty bricks of the box only,
+    mesh.resolution up to 8192; mesh.py), extract_points (with
     is_continue: <exp>/points/<iter>.ply, the training views' surface points with normals and colours; mesh.py).  Image files are written with
     PIL; everything per-ray runs in the C++/HIP host (there is no Python in the training loop: ExpRunner::Train).
   * data-parallel training (the reference is single-GPU): launched as N ranks -- `python -m torch.distributed.run --nnodes=1

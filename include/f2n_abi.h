@@ -1095,6 +1095,61 @@ int f2n_mesh_count_masked(void* stream, int nx, int ny, int nz, const float* gri
                           int32_t* face_counts /*[C]*/, int32_t* face_start_end /*[C,2]*/, int32_t* totals /*[2]*/);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Sparse mesh extraction on bricks (additive; the ABI version is unchanged): the iso-surface of f2n_mesh_count / f2n_mesh_emit,
+ * bit for bit, from the parts of a grid that can hold something -- the grid itself is never materialised.  No reference
+ * counterpart.  csrc/octree.hip; tests/mesh_sparse_ref.py restates the definitions in numpy.
+ * ------------------------------------------------------------------------------------------------- */
+/* The VIRTUAL GRID is that of f2n_oct_locate_warp_grid: n[k] points per axis (2 <= n[k] <= F2N_BRICK_MAX_POINTS), point i =
+ * p_k(i_k) = lo[k] + step * (float) i_k (rounded twice, never an FMA).  lo is HOST data.
+ * BRICKS of B^3 cells, B in {4, 8, 16} (any other B: F2N_ERR_INVALID_ARG): nb[k] = ceil((n[k] - 1) / B) bricks per axis, linear id
+ *   b = (b_z nb[1] + b_y) nb[0] + b_x (x fastest); nb[0] nb[1] nb[2] must be below 2^31 (F2N_ERR_UNSUPPORTED otherwise).
+ *   Brick b READS the (B + 1)^3 corners b B + l, l in [0, B]^3, as one row of (B + 1)^3 values, local x fastest: (l_z (B + 1) + l_y)
+ *   (B + 1) + l_x.  A corner with i_k > n[k] - 1 DOES NOT EXIST (its value is never read); no edge or cell that uses it exists.
+ *   Brick b OWNS the cells with l in [0, B)^3 and the corners with l in [0, B)^3 -- the last brick of an axis (b_k = nb[k] - 1) also
+ *   those with l_k = B: the grid's border plane when n[k] - 1 is a multiple of B, which no other brick reaches.  Every existing corner
+ *   and cell has exactly one owner, and the owner's row holds both endpoints of every edge the corner owns and all eight corners of
+ *   the cell.
+ * KEYS (int64): corner (i_z n_y + i_y) n_x + i_x;  vertex 8 corner + type (owner corner and edge type 0..6 of f2n_mesh_count);
+ *   cell (i_z (n_y - 1) + i_y) (n_x - 1) + i_x;  face 16 cell + ordinal, ordinal = the position of the triangle among its cell's faces
+ *   in f2n_mesh_emit's order (tet, triangle), 0..11.  Sorted by key, vertices and faces are in f2n_mesh_emit's order. */
+#define F2N_BRICK_MAX_POINTS (1 << 19)
+/* flags [nb_z nb_y nb_x] uint8, a pure function of (tree_nodes, lo, step, n, B): flags[b] = 1 iff the CLOSED box of brick b,
+ *   blo_k = p_k(b_k B) .. bhi_k = p_k(min(b_k B + B, n[k] - 1)), can hold a non-empty point:
+ *   root test -- with h = side_len * .5f of node 0 (f2n_oct_locate_warp's expressions), bhi_k >= center_k - h and blo_k <= center_k + h
+ *   for every axis, else 0;
+ *   descent from node 0 -- a node with a child enters child slot 4 s_x + 2 s_y + s_z when that slot is >= 0 and for every axis
+ *   (s_k = 0 and blo_k < c_k) or (s_k = 1 and bhi_k >= c_k), c = the node's centre; a node WITHOUT children ends its branch, with flag 1
+ *   if its trans_idx >= 0.  Nodes below depth 31 are not entered (f2n_oct_locate_warp reports their points empty).
+ *   The flag is 1 iff some branch ends so.  This is conservative for the point rule p_k >= c_k of f2n_oct_locate_warp: a point of the
+ *   box follows one of the branches its box follows, so every non-empty grid point lies in rows of flagged bricks only. */
+int f2n_brick_mark(void* stream, const void* tree_nodes, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int B,
+                   uint8_t* flags /*[nb_z*nb_y*nb_x]*/);
+/* f2n_oct_locate_warp_grid for the corners of the n_bricks listed bricks: output row j (B + 1)^3 + l = local corner l of brick
+ * brick_ids[j] (n_bricks (B + 1)^3 <= 2^31 - 1).  A corner that does not exist (or a brick id outside the grid) gets anchors
+ * (-1, -1, 0) and warped (0, 0, 0), as an empty point. */
+int f2n_oct_locate_warp_bricks(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int B, int n_bricks,
+                               const int32_t* brick_ids /*[n_bricks]*/, const void* tree_nodes, const void* transes,
+                               float* out_pts_warped /*[n_bricks*(B+1)^3,3]*/, int32_t* out_anchors /*[n_bricks*(B+1)^3,3]*/);
+/* The iso-surface of ANY values [n_bricks, (B + 1)^3] float32 of the listed bricks, count -> scan -> emit as f2n_mesh_count /
+ * f2n_mesh_emit; one workgroup per brick, the brick's row staged in LDS; the inside test, edge types, tetrahedra, winding and vertex
+ * position are f2n_mesh_emit's own device functions.
+ * f2n_brick_mesh_count: vert_counts[j] / face_counts[j] = the vertices of the corners / the faces of the cells that brick j owns.
+ * f2n_brick_mesh_emit: vert_start / face_start [n_bricks] int64 = the exclusive prefix sums of the counts (plus any offset of the
+ *   caller's); brick j writes vert_keys, verts [.,3] from row vert_start[j] and face_keys, face_vert_keys [.,3] (the KEYS of a face's three
+ *   vertices, wound as f2n_mesh_emit winds) from row face_start[j].  The order within a brick is fixed (local corner / cell index,
+ *   then type / ordinal) but carries no meaning: keys are unique across bricks, and a caller sorts by them.
+ * A brick id outside the grid owns nothing.  A face's vertex may be owned by another brick: the surface is complete only over a set
+ * of bricks that holds the owner of every crossing edge of its cells (any set that holds every brick whose row has a value on
+ * either side of the level does). */
+int f2n_brick_mesh_count(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids /*[n_bricks]*/,
+                         const float* values /*[n_bricks,(B+1)^3]*/, float level, int32_t* vert_counts /*[n_bricks]*/,
+                         int32_t* face_counts /*[n_bricks]*/);
+int f2n_brick_mesh_emit(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids /*[n_bricks]*/,
+                        const float* values /*[n_bricks,(B+1)^3]*/, float level, const float* lo /*host [3]*/, float step,
+                        const int64_t* vert_start /*[n_bricks]*/, const int64_t* face_start /*[n_bricks]*/, int64_t* vert_keys /*[nv]*/,
+                        float* verts /*[nv,3]*/, int64_t* face_keys /*[nf]*/, int64_t* face_vert_keys /*[nf,3]*/);
+
+/* ---------------------------------------------------------------------------------------------------
  * Mesh simplification by vertex clustering with quadric-error placement (additive; the ABI version is unchanged).  Lindstrom 2000
  * with Garland-Heckbert plane quadrics.  No reference counterpart.  csrc/octree.hip.
  * ------------------------------------------------------------------------------------------------- */
