@@ -1516,8 +1516,13 @@ def mesh_from_bricks(values, brick_ids, n, lo, step, level, B, batch_bricks=0):
     mesh_from_grid on the dense grid when the list holds every brick with a value on either side of the level.  ValueError: a brick size
     outside {4, 8, 16}, a brick id outside the grid or listed twice, a list that lacks the owner of a face's vertex, more than
     2^31 - 1 vertices or faces."""
+    return _mesh_from_bricks(values, None, brick_ids, n, lo, step, level, B, batch_bricks)
+
+
+def _checked_brick_ids(brick_ids, n, B):
+    """brick_ids as int32 [n_bricks], every id inside the grid and listed once (ValueError otherwise)"""
     nb = _brick_counts(n, B)
-    total, P, dev = nb[0] * nb[1] * nb[2], (B + 1) ** 3, values.device
+    total = nb[0] * nb[1] * nb[2]
     ids = brick_ids.to(torch.int64).reshape(-1)
     nbr = int(ids.numel())
     if nbr:
@@ -1526,10 +1531,22 @@ def mesh_from_bricks(values, brick_ids, n, lo, step, level, B, batch_bricks=0):
             raise ValueError("a brick id lies outside the grid's %d bricks" % total)
         if nbr > 1 and bool((s[1:] == s[:-1]).any()):
             raise ValueError("a brick id is listed twice")
-    ids = ids.to(torch.int32).contiguous()
-    if values.numel() != nbr * P:
-        raise F2nError("values must be [n_bricks, (B+1)^3]")
+    return ids.to(torch.int32).contiguous()
+
+
+def _mesh_from_bricks(values, valid, brick_ids, n, lo, step, level, B, batch_bricks):
+    """valid None: mesh_from_bricks; else mesh_from_bricks_masked"""
+    ids = _checked_brick_ids(brick_ids, n, B)
+    nbr, P, dev = int(ids.numel()), (B + 1) ** 3, values.device
+    if values.numel() != nbr * P or (valid is not None and valid.numel() != nbr * P):
+        raise F2nError("values (and valid) must be [n_bricks, (B+1)^3]")
     values = values.reshape(nbr, P)
+    masked = valid is not None
+    if masked:
+        valid = valid.reshape(nbr, P)
+    L = lib()
+    count = L.f2n_brick_mesh_count_masked if masked else L.f2n_brick_mesh_count
+    emit = L.f2n_brick_mesh_emit_masked if masked else L.f2n_brick_mesh_emit
     per = int(batch_bricks) if batch_bricks > 0 else max(nbr, 1)
     i64 = dict(dtype=torch.int64, device=dev)
     vk, vv, fk, fv = [torch.empty(0, **i64)], [torch.empty((0, 3), dtype=torch.float32, device=dev)], [torch.empty(0, **i64)], [torch.empty((0, 3), **i64)]
@@ -1537,8 +1554,9 @@ def mesh_from_bricks(values, brick_ids, n, lo, step, level, B, batch_bricks=0):
         b, val = ids[j0:j0 + per].contiguous(), values[j0:j0 + per].contiguous()
         c = int(b.numel())
         vc, fc = torch.empty(c, dtype=torch.int32, device=dev), torch.empty(c, dtype=torch.int32, device=dev)
-        _ck(lib().f2n_brick_mesh_count(_stream(), _i(n[0]), _i(n[1]), _i(n[2]), _i(B), _i(c), _p(b, "i32"), _p(val, "f32"), _f(level),
-                                       _p(vc, "i32"), _p(fc, "i32")), "f2n_brick_mesh_count")
+        ok = (_p(valid[j0:j0 + per].contiguous(), "u8"),) if masked else ()  # (the slice of a contiguous [nbr, P] is the memory itself)
+        _ck(count(_stream(), _i(n[0]), _i(n[1]), _i(n[2]), _i(B), _i(c), _p(b, "i32"), _p(val, "f32"), *ok, _f(level),
+                  _p(vc, "i32"), _p(fc, "i32")), "f2n_brick_mesh_count")
         vend, fend = torch.cumsum(vc, 0, dtype=torch.int64), torch.cumsum(fc, 0, dtype=torch.int64)
         nv, nf = int(vend[-1]), int(fend[-1])
         if nv == 0 and nf == 0:
@@ -1547,9 +1565,9 @@ def mesh_from_bricks(values, brick_ids, n, lo, step, level, B, batch_bricks=0):
         bvk, bvv = torch.empty(max(nv, 1), **i64), torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev)
         bfk, bfv = torch.empty(max(nf, 1), **i64), torch.empty((max(nf, 1), 3), **i64)
         vstart, fstart = (vend - vc).contiguous(), (fend - fc).contiguous()  # (named: they must outlive the call's argument list)
-        _ck(lib().f2n_brick_mesh_emit(_stream(), _i(n[0]), _i(n[1]), _i(n[2]), _i(B), _i(c), _p(b, "i32"), _p(val, "f32"), _f(level), _lo3(lo),
-                                      _f(step), _p(vstart, "i64"), _p(fstart, "i64"), _p(bvk, "i64"), _p(bvv, "f32"), _p(bfk, "i64"),
-                                      _p(bfv, "i64")), "f2n_brick_mesh_emit")
+        _ck(emit(_stream(), _i(n[0]), _i(n[1]), _i(n[2]), _i(B), _i(c), _p(b, "i32"), _p(val, "f32"), *ok, _f(level), _lo3(lo),
+                 _f(step), _p(vstart, "i64"), _p(fstart, "i64"), _p(bvk, "i64"), _p(bvv, "f32"), _p(bfk, "i64"),
+                 _p(bfv, "i64")), "f2n_brick_mesh_emit")
         vk.append(bvk[:nv]), vv.append(bvv[:nv]), fk.append(bfk[:nf]), fv.append(bfv[:nf])
     keys, verts, fkeys, fverts = torch.cat(vk), torch.cat(vv), torch.cat(fk), torch.cat(fv)
     if keys.numel() > 0x7fffffff or fkeys.numel() > 0x7fffffff:
@@ -1557,9 +1575,62 @@ def mesh_from_bricks(values, brick_ids, n, lo, step, level, B, batch_bricks=0):
     skeys, perm = torch.sort(keys)
     verts = verts[perm].contiguous()
     if fkeys.numel() == 0:
-        return verts, torch.empty((0, 3), dtype=torch.int32, device=dev)
+        return (verts[:0] if masked else verts), torch.empty((0, 3), dtype=torch.int32, device=dev)
     want = fverts.reshape(-1)
     at = torch.searchsorted(skeys, want).clamp_(max=max(int(skeys.numel()) - 1, 0))
     if skeys.numel() == 0 or not bool((skeys[at] == want).all()):
         raise ValueError("the brick list lacks the owner of a face's vertex")
+    if masked:  # the vertices some face names, in key order; a face's index = the number of kept vertices in front of it
+        used = torch.zeros(skeys.numel(), dtype=torch.int64, device=dev)
+        used[at] = 1
+        verts = verts[used.bool()].contiguous()
+        at = (torch.cumsum(used, 0) - used)[at]
     return verts, at.to(torch.int32).reshape(-1, 3)[torch.argsort(fkeys)].contiguous()
+
+
+def mesh_from_bricks_masked(values, valid, brick_ids, n, lo, step, level, B, batch_bricks=0):
+    """mesh_from_bricks over the corners that carry a value (valid [n_bricks, (B+1)^3] uint8; f2n_brick_mesh_count_masked /
+    f2n_brick_mesh_emit_masked), then without the vertices no face names: the bits of mesh_from_grid_masked on the dense grid when the
+    list holds the owner of every face."""
+    if valid is None:
+        raise F2nError("valid is required")
+    return _mesh_from_bricks(values, valid, brick_ids, n, lo, step, level, B, batch_bricks)
+
+
+# ---------------------------------------------------------------- sparse TSDF fusion on bricks (include/f2n_abi.h)
+def _tsdf_views(poses, intri, dist_params, depth, conf):
+    V, h, w = (int(v) for v in depth.shape)
+    if poses.numel() != 12 * V or intri.numel() != 9 * V or dist_params.numel() != 4 * V or (conf is not None and conf.shape != depth.shape):
+        raise F2nError("poses [V,3,4], intri [V,3,3], dist_params [V,4] and conf must match depth [V,h,w]")
+    none = V == 0
+    return (_i(V), _p(poses, "f32", none), _p(intri, "f32", none), _p(dist_params, "f32", none), _p(depth, "f32", none), _p(conf, "f32", True),
+            _i(h), _i(w))
+
+
+def _check_trunc(trunc):
+    if not 0.0 < float(trunc) < float("inf"):
+        raise ValueError("trunc must be positive and finite, got %r" % (trunc,))
+
+
+def tsdf_brick_mark(lo, step, n, B, poses, intri, dist_params, depth, conf, trunc):
+    """flags [nbz, nby, nbx] uint8: 1 for the bricks of B^3 cells of the virtual grid (lo, step, n = (nx, ny, nz)) whose (B+1)^3 row holds
+    an existing corner that some view sees at most trunc behind its surface (f2n_tsdf_brick_mark; all zero without views)."""
+    nb = _brick_counts(n, B)
+    _check_trunc(trunc)
+    flags = torch.zeros((nb[2], nb[1], nb[0]), dtype=torch.uint8, device=depth.device)
+    _ck(lib().f2n_tsdf_brick_mark(_stream(), _lo3(lo), _f(step), _i(n[0]), _i(n[1]), _i(n[2]), _i(B),
+                                  *_tsdf_views(poses, intri, dist_params, depth, conf), _f(trunc), _p(flags, "u8")), "f2n_tsdf_brick_mark")
+    return flags
+
+
+def tsdf_integrate_bricks(S, W, brick_ids, lo, step, n, B, poses, intri, dist_params, depth, conf, trunc):
+    """tsdf_integrate for the rows S, W [n_bricks, (B+1)^3] of brick_ids (each id once, inside the grid), in place
+    (f2n_tsdf_integrate_bricks): an existing corner gets the bits of the dense grid point; the others are left untouched."""
+    ids = _checked_brick_ids(brick_ids, n, B)
+    _check_trunc(trunc)
+    m = int(ids.numel()) * (B + 1) ** 3
+    if S.numel() != m or W.numel() != m:
+        raise F2nError("S and W must be [n_bricks, (B+1)^3]")
+    _ck(lib().f2n_tsdf_integrate_bricks(_stream(), _lo3(lo), _f(step), _i(n[0]), _i(n[1]), _i(n[2]), _i(B), _i(ids.numel()),
+                                        _p(ids, "i32", m == 0), *_tsdf_views(poses, intri, dist_params, depth, conf), _f(trunc),
+                                        _p(S, "f32", m == 0), _p(W, "f32", m == 0)), "f2n_tsdf_integrate_bricks")

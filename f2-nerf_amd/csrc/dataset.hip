@@ -142,6 +142,50 @@ __global__ void draw_ray_batch_kernel(int n_rays, const float* __restrict__ u01,
 // registers: no atomics, the state is read once and written once, and the sums of a launch over [0, V) are those of launches over
 // [0, k) and [k, V).  A view's 20 constants (pose, fx, fy, cx, cy, distortion) are addressed by the loop variable alone: wave-uniform,
 // fetched by scalar loads into SGPRs, so that the vector registers hold the voxel's own state only.
+// Steps 1-10 of f2n_tsdf_integrate for the point p and the view v: false where the view is skipped, else sdf and wgt of steps 9-10.
+// v is the callers' loop variable: the view's constants stay wave-uniform.
+__device__ __forceinline__ bool tsdf_observe(const float p[3], int v, const float* __restrict__ poses, const float* __restrict__ intri,
+                                             const float* __restrict__ dist, const float* __restrict__ depth,
+                                             const float* __restrict__ conf, int h, int w, float trunc, float& sdf, float& wgt) {
+  const float* P = poses + 12 * (size_t) v;
+  const float* K = intri + 9 * (size_t) v;
+  const float q[3] = {F2N_SUB_RN(p[0], P[3]), F2N_SUB_RN(p[1], P[7]), F2N_SUB_RN(p[2], P[11])};
+  float c[3];  // R^T q: the point in the camera frame (x right, y up, z backwards: OpenGL style)
+#pragma unroll
+  for (int a = 0; a < 3; a++) c[a] = f2n_sum3(F2N_MUL_RN(P[a], q[0]), F2N_MUL_RN(P[4 + a], q[1]), F2N_MUL_RN(P[8 + a], q[2]));
+  const float s = -c[2];
+  if (!(s > 0.f)) return false;  // behind the camera (NaN as well)
+  const float un = F2N_DIV_RN(c[0], s), vn = F2N_DIV_RN(-c[1], s);
+  float du, dv;
+  f2n_distort(dist + 4 * (size_t) v, un, vn, du, dv);
+  const float x = F2N_ADD_RN(F2N_MUL_RN(K[0], F2N_ADD_RN(un, du)), K[2]);
+  const float y = F2N_ADD_RN(F2N_MUL_RN(K[4], F2N_ADD_RN(vn, dv)), K[5]);
+  const float fb = floorf(x), fa = floorf(y);
+  if (!(fa >= 0.f && fa < (float) h && fb >= 0.f && fb < (float) w)) return false;  // outside the image (NaN as well)
+  const size_t px = ((size_t) v * h + (int) fa) * w + (int) fb;
+  const float D = depth[px];
+  if (!(D > 0.f)) return false;  // no surface along this pixel's ray
+  wgt = conf != nullptr ? conf[px] : 1.f;
+  if (!(wgt > 0.f)) return false;
+  sdf = F2N_SUB_RN(D, f2n_norm3(q[0], q[1], q[2]));
+  return !(sdf < -trunc);  // further than trunc behind the surface: not observed
+}
+
+// The views [0, n_views) added to the running sums of the voxel at p, in index order (steps 1-12): what the dense kernel and the
+// brick kernel both do to a voxel.
+__device__ __forceinline__ void tsdf_voxel(const float p[3], int n_views, const float* __restrict__ poses, const float* __restrict__ intri,
+                                           const float* __restrict__ dist, const float* __restrict__ depth, const float* __restrict__ conf,
+                                           int h, int w, float trunc, float& s_sum, float& w_sum) {
+  for (int v = 0; v < n_views; v++) {
+    float sdf, wgt;
+    if (!tsdf_observe(p, v, poses, intri, dist, depth, conf, h, w, trunc, sdf, wgt)) continue;
+    const float ratio = F2N_DIV_RN(sdf, trunc);
+    const float d = ratio < 1.f ? ratio : 1.f;
+    s_sum = F2N_ADD_RN(s_sum, F2N_MUL_RN(wgt, d));
+    w_sum = F2N_ADD_RN(w_sum, wgt);
+  }
+}
+
 __global__ void __launch_bounds__(256) tsdf_integrate_kernel(int64_t n, int nx, int ny, float lo0, float lo1, float lo2, float step, int n_views,
                                                             const float* __restrict__ poses, const float* __restrict__ intri,
                                                             const float* __restrict__ dist, const float* __restrict__ depth,
@@ -154,37 +198,95 @@ __global__ void __launch_bounds__(256) tsdf_integrate_kernel(int64_t n, int nx, 
   const float p[3] = {f2n_grid_coord(lo0, step, (int) (r % nx)), f2n_grid_coord(lo1, step, (int) (r / nx)),
                       f2n_grid_coord(lo2, step, (int) (i / plane))};
   float s_sum = S[i], w_sum = W[i];
-  const float fh = (float) h, fw = (float) w;
-  for (int v = 0; v < n_views; v++) {
-    const float* P = poses + 12 * (size_t) v;
-    const float* K = intri + 9 * (size_t) v;
-    const float q[3] = {F2N_SUB_RN(p[0], P[3]), F2N_SUB_RN(p[1], P[7]), F2N_SUB_RN(p[2], P[11])};
-    float c[3];  // R^T q: the point in the camera frame (x right, y up, z backwards: OpenGL style)
-#pragma unroll
-    for (int a = 0; a < 3; a++) c[a] = f2n_sum3(F2N_MUL_RN(P[a], q[0]), F2N_MUL_RN(P[4 + a], q[1]), F2N_MUL_RN(P[8 + a], q[2]));
-    const float s = -c[2];
-    if (!(s > 0.f)) continue;  // behind the camera (NaN as well)
-    const float un = F2N_DIV_RN(c[0], s), vn = F2N_DIV_RN(-c[1], s);
-    float du, dv;
-    f2n_distort(dist + 4 * (size_t) v, un, vn, du, dv);
-    const float x = F2N_ADD_RN(F2N_MUL_RN(K[0], F2N_ADD_RN(un, du)), K[2]);
-    const float y = F2N_ADD_RN(F2N_MUL_RN(K[4], F2N_ADD_RN(vn, dv)), K[5]);
-    const float fb = floorf(x), fa = floorf(y);
-    if (!(fa >= 0.f && fa < fh && fb >= 0.f && fb < fw)) continue;  // outside the image (NaN as well)
-    const size_t px = ((size_t) v * h + (int) fa) * w + (int) fb;
-    const float D = depth[px];
-    if (!(D > 0.f)) continue;  // no surface along this pixel's ray
-    const float wgt = conf != nullptr ? conf[px] : 1.f;
-    if (!(wgt > 0.f)) continue;
-    const float sdf = F2N_SUB_RN(D, f2n_norm3(q[0], q[1], q[2]));
-    if (sdf < -trunc) continue;  // further than trunc behind the surface: not observed
-    const float ratio = F2N_DIV_RN(sdf, trunc);
-    const float d = ratio < 1.f ? ratio : 1.f;
-    s_sum = F2N_ADD_RN(s_sum, F2N_MUL_RN(wgt, d));
-    w_sum = F2N_ADD_RN(w_sum, wgt);
-  }
+  tsdf_voxel(p, n_views, poses, intri, dist, depth, conf, h, w, trunc, s_sum, w_sum);
   S[i] = s_sum;
   W[i] = w_sum;
+}
+
+// ---- sparse TSDF fusion on bricks (include/f2n_abi.h, "Sparse TSDF fusion on bricks") ---------------------------------------------
+// The virtual grid and its bricks are those of the sparse mesher (csrc/octree.hip): brick b = (b_z nb_y + b_y) nb_x + b_x reads the
+// (B + 1)^3 corners b B + l, local x fastest; a corner with i_k > n_k - 1 does not exist.
+struct TsdfBrickGrid {
+  float lo[3], step;
+  int n[3], nb[3], B;
+};
+
+// x0 = the grid index of the local corner (0, 0, 0) of brick b (0 <= b < 2^31: 32-bit arithmetic)
+__device__ __forceinline__ void tsdf_brick_origin(const TsdfBrickGrid& g, int b, int x0[3]) {
+  const int row = b / g.nb[0];
+  x0[0] = (b - row * g.nb[0]) * g.B;
+  x0[2] = row / g.nb[1];
+  x0[1] = (row - x0[2] * g.nb[1]) * g.B;
+  x0[2] *= g.B;
+}
+
+// local corner l of the brick at x0: false where it does not exist, else its position
+__device__ __forceinline__ bool tsdf_brick_corner(const TsdfBrickGrid& g, int S1, const int x0[3], int l, float p[3]) {
+  const int lc[3] = {l % S1, (l / S1) % S1, l / (S1 * S1)};
+  bool exists = true;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const int ik = x0[k] + lc[k];
+    exists = exists && ik <= g.n[k] - 1;
+    p[k] = f2n_grid_coord(g.lo[k], g.step, ik);
+  }
+  return exists;
+}
+
+// tsdf_integrate_kernel for the corners of listed bricks: row (j, l) = brick j of the list, local corner l.  One thread per row entry;
+// a corner that does not exist and a brick id outside the grid keep their state.
+__global__ void __launch_bounds__(256) tsdf_integrate_bricks_kernel(TsdfBrickGrid g, int64_t n_total, int64_t n,
+                                                                   const int32_t* __restrict__ brick_ids, int n_views,
+                                                                   const float* __restrict__ poses, const float* __restrict__ intri,
+                                                                   const float* __restrict__ dist, const float* __restrict__ depth,
+                                                                   const float* __restrict__ conf, int h, int w, float trunc,
+                                                                   float* __restrict__ S, float* __restrict__ W) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int P = (g.B + 1) * (g.B + 1) * (g.B + 1);
+  const int64_t b = brick_ids[i / P];
+  if (b < 0 || b >= n_total) return;
+  int x0[3];
+  tsdf_brick_origin(g, (int) b, x0);
+  float p[3];
+  if (!tsdf_brick_corner(g, g.B + 1, x0, (int) (i % P), p)) return;
+  float s_sum = S[i], w_sum = W[i];
+  tsdf_voxel(p, n_views, poses, intri, dist, depth, conf, h, w, trunc, s_sum, w_sum);
+  S[i] = s_sum;
+  W[i] = w_sum;
+}
+
+// flags[b] = some existing corner of brick b's row has a hit in some view: tsdf_observe and sdf < 0.  One workgroup per brick (the
+// bricks strided over the launch's blocks), the views in the outer loop and one corner per lane and round in the inner one (a view's
+// constants are loaded once per brick); after every group of F2N_TSDF_MARK_VOTE views the block votes, and a brick with a hit leaves.
+// No atomics: a flag is written once, by its own block.
+#define F2N_TSDF_MARK_VOTE 4
+#define F2N_TSDF_MARK_MAX_BLOCKS (1 << 20)
+template <int B>
+__global__ void __launch_bounds__(256) tsdf_brick_mark_kernel(TsdfBrickGrid g, unsigned n_total, int n_views, const float* __restrict__ poses,
+                                                             const float* __restrict__ intri, const float* __restrict__ dist,
+                                                             const float* __restrict__ depth, const float* __restrict__ conf, int h, int w,
+                                                             float trunc, uint8_t* __restrict__ flags) {
+  constexpr int S1 = B + 1, P = S1 * S1 * S1;
+  for (unsigned b = blockIdx.x; b < n_total; b += gridDim.x) {  // (n_total < 2^31 and at most 2^20 blocks: b does not wrap)
+    int x0[3];
+    tsdf_brick_origin(g, (int) b, x0);
+    bool hit = false;
+    int any = 0;
+    for (int v0 = 0; v0 < n_views && any == 0; v0 += F2N_TSDF_MARK_VOTE) {
+      const int v1 = min(v0 + F2N_TSDF_MARK_VOTE, n_views);
+#pragma unroll 1  // (one view's constants in SGPRs at a time)
+      for (int v = v0; v < v1; v++) {
+        for (int l = threadIdx.x; l < P && !hit; l += 256) {
+          float p[3], sdf, wgt;
+          if (!tsdf_brick_corner(g, S1, x0, l, p)) continue;
+          if (tsdf_observe(p, v, poses, intri, dist, depth, conf, h, w, trunc, sdf, wgt) && sdf < 0.f) hit = true;
+        }
+      }
+      any = __syncthreads_or(hit ? 1 : 0);
+    }
+    if (threadIdx.x == 0) flags[b] = any != 0 ? 1 : 0;
+  }
 }
 
 // SSIM of two images (include/f2n_abi.h, f2n_image_ssim; scripts/eval.py:29-75, the mip-NeRF definition): fp64 throughout, one rounding per
@@ -323,6 +425,64 @@ int f2n_tsdf_integrate(void* stream, const float* lo /*host [3]*/, float step, i
     return F2N_ERR_INVALID_ARG;
   hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, nx, ny, lo[0], lo[1], lo[2],
                      step, n_views, poses, intri, dist_params, depth, conf, h, w, trunc, S, W);
+  return f2n_launch_status();
+}
+
+// the brick grid of (n, B), or the status that refuses it (as csrc/octree.hip's)
+static int tsdf_brick_grid(const float* lo, float step, int nx, int ny, int nz, int B, TsdfBrickGrid* g, int64_t* n_total) {
+  if (nx < 2 || ny < 2 || nz < 2 || nx > F2N_BRICK_MAX_POINTS || ny > F2N_BRICK_MAX_POINTS || nz > F2N_BRICK_MAX_POINTS) return F2N_ERR_INVALID_ARG;
+  if (B != 4 && B != 8 && B != 16) return F2N_ERR_INVALID_ARG;
+  const int n[3] = {nx, ny, nz};
+  for (int k = 0; k < 3; k++) {
+    g->lo[k] = lo[k];
+    g->n[k] = n[k];
+    g->nb[k] = (n[k] - 1 + B - 1) / B;
+  }
+  g->step = step;
+  g->B = B;
+  *n_total = (int64_t) g->nb[0] * g->nb[1] * g->nb[2];
+  return *n_total > 0x7fffffff ? F2N_ERR_UNSUPPORTED : F2N_OK;
+}
+
+int f2n_tsdf_brick_mark(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int B, int n_views, const float* poses,
+                        const float* intri, const float* dist_params, const float* depth, const float* conf, int h, int w, float trunc,
+                        uint8_t* flags) {
+  if (lo == nullptr || n_views < 0 || h < 0 || w < 0 || !(trunc > 0.f) || !(trunc < __builtin_huge_valf())) return F2N_ERR_INVALID_ARG;
+  TsdfBrickGrid g;
+  int64_t n_total;
+  const int e = tsdf_brick_grid(lo, step, nx, ny, nz, B, &g, &n_total);
+  if (e != F2N_OK) return e;
+  if (n_views == 0) return F2N_OK;
+  if (h < 1 || w < 1 || h > (1 << 24) || w > (1 << 24)) return F2N_ERR_INVALID_ARG;
+  if (poses == nullptr || intri == nullptr || dist_params == nullptr || depth == nullptr || flags == nullptr) return F2N_ERR_INVALID_ARG;
+  const unsigned blocks = (unsigned) (n_total < F2N_TSDF_MARK_MAX_BLOCKS ? n_total : F2N_TSDF_MARK_MAX_BLOCKS);
+#define F2N_TSDF_MARK(BB)                                                                                                              \
+  hipLaunchKernelGGL(tsdf_brick_mark_kernel<BB>, dim3(blocks), dim3(256), 0, (hipStream_t) stream, g, (unsigned) n_total, n_views, poses, \
+                     intri, dist_params, depth, conf, h, w, trunc, flags)
+  if (B == 4) F2N_TSDF_MARK(4);
+  else if (B == 8) F2N_TSDF_MARK(8);
+  else F2N_TSDF_MARK(16);
+#undef F2N_TSDF_MARK
+  return f2n_launch_status();
+}
+
+int f2n_tsdf_integrate_bricks(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int B, int n_bricks,
+                              const int32_t* brick_ids, int n_views, const float* poses, const float* intri, const float* dist_params,
+                              const float* depth, const float* conf, int h, int w, float trunc, float* S, float* W) {
+  if (lo == nullptr || n_bricks < 0 || n_views < 0 || h < 0 || w < 0 || !(trunc > 0.f) || !(trunc < __builtin_huge_valf()))
+    return F2N_ERR_INVALID_ARG;
+  TsdfBrickGrid g;
+  int64_t n_total;
+  const int e = tsdf_brick_grid(lo, step, nx, ny, nz, B, &g, &n_total);
+  if (e != F2N_OK) return e;
+  const int64_t n = (int64_t) n_bricks * (B + 1) * (B + 1) * (B + 1);
+  if (n > 0x7fffffff) return F2N_ERR_INVALID_ARG;
+  if (n_views == 0 || n == 0) return F2N_OK;
+  if (h < 1 || w < 1 || h > (1 << 24) || w > (1 << 24)) return F2N_ERR_INVALID_ARG;
+  if (brick_ids == nullptr || poses == nullptr || intri == nullptr || dist_params == nullptr || depth == nullptr || S == nullptr || W == nullptr)
+    return F2N_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(tsdf_integrate_bricks_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, g, n_total, n, brick_ids,
+                     n_views, poses, intri, dist_params, depth, conf, h, w, trunc, S, W);
   return f2n_launch_status();
 }
 

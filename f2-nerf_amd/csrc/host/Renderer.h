@@ -95,10 +95,12 @@ struct BrickMeshPart {
   Tensor vert_keys, verts, face_keys, face_vert_keys;  // [nv] int64, [nv,3] f32, [nf] int64, [nf,3] int64
   int64_t meshed_bricks = 0;                           // bricks of the batch that own a vertex or a face
 };
-BrickMeshPart BrickMeshBatch(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step, float level, int B);
+// valid: undefined = f2n_brick_mesh_count / _emit, else the device uint8 rows [n_bricks, (B+1)^3] of the masked entry points
+BrickMeshPart BrickMeshBatch(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step, float level, int B,
+                             const Tensor& valid = Tensor());
 // The parts as one mesh in f2n_mesh_emit's order: vertices sorted by key, faces = searchsorted(sorted keys, face_vert_keys) as int32,
-// sorted by face key
-std::tuple<Tensor, Tensor> BrickMeshAssemble(const std::vector<BrickMeshPart>& parts);
+// sorted by face key.  drop_unreferenced (the masked mesher): the vertices no face names are compacted away, order kept, faces remapped
+std::tuple<Tensor, Tensor> BrickMeshAssemble(const std::vector<BrickMeshPart>& parts, bool drop_unreferenced = false);
 // (verts, faces) of values [n_bricks, (B+1)^3] for brick_ids [n_bricks] (any order, each id once); batch_bricks > 0: in batches of
 // that many bricks (the same mesh)
 std::tuple<Tensor, Tensor> MeshFromBricks(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step,
@@ -108,6 +110,26 @@ std::tuple<Tensor, Tensor> MeshFromBricks(const Tensor& values, const Tensor& br
 void TsdfIntegrate(const Tensor& S, const Tensor& W, const float lo[3], float step, const Tensor& poses, const Tensor& intri,
                    const Tensor& dist, const Tensor& depth, const Tensor& conf, float trunc);
 std::tuple<Tensor, Tensor> TsdfFinalize(const Tensor& S, const Tensor& W, float min_weight);
+// Sparse TSDF fusion on bricks (include/f2n_abi.h, "Sparse TSDF fusion on bricks"); the views as TsdfIntegrate takes them.
+// TsdfBrickMark: flags [nbz, nby, nbx] uint8 of f2n_tsdf_brick_mark (all zero without views).  TsdfIntegrateBricks: the device rows S, W
+// [n_bricks, (B+1)^3] of brick_ids (checked as MeshFromBricks checks them) IN PLACE.  MeshFromBricksMasked: MeshFromBricks through the
+// masked entry points, then without the vertices no face names -- MeshFromGridMasked's mesh when the list holds the owner of every face.
+Tensor TsdfBrickMark(const float lo[3], float step, const int n[3], int B, const Tensor& poses, const Tensor& intri, const Tensor& dist,
+                     const Tensor& depth, const Tensor& conf, float trunc);
+void TsdfIntegrateBricks(const Tensor& S, const Tensor& W, const Tensor& brick_ids, const float lo[3], float step, const int n[3], int B,
+                         const Tensor& poses, const Tensor& intri, const Tensor& dist, const Tensor& depth, const Tensor& conf, float trunc);
+std::tuple<Tensor, Tensor> MeshFromBricksMasked(const Tensor& values, const Tensor& valid, const Tensor& brick_ids, const int n[3],
+                                                const float lo[3], float step, float level, int B, int64_t batch_bricks = 0);
+// mark -> the flagged bricks in ascending order in batches of batch_bricks -> zeroed rows, TsdfIntegrateBricks over all views,
+// TsdfFinalize, one masked mesh batch -> assemble: the mesh of TsdfIntegrate -> TsdfFinalize -> MeshFromGridMasked at level 0, bit for
+// bit, with one batch of rows alive at a time
+struct SparseTsdfStats {
+  int64_t bricks = 0, active_bricks = 0, meshed_bricks = 0, points_evaluated = 0, points_known = 0, batches = 0;
+  int grid[3] = {0, 0, 0};
+};
+std::tuple<Tensor, Tensor> TsdfMeshSparse(const float lo[3], float step, const int n[3], int B, const Tensor& poses, const Tensor& intri,
+                                          const Tensor& dist, const Tensor& depth, const Tensor& conf, float trunc, float min_weight,
+                                          int64_t batch_bricks, SparseTsdfStats* stats = nullptr);
 // Unit normals [n,3] at pts [n,3] from the gradient of any float32 grid [nz, ny, nx] (f2n_grid_normals): -grad / |grad|, 0 where flat
 Tensor GridNormals(const Tensor& grid, const Tensor& pts, const float lo[3], float step);
 // labels [V] int32: the smallest vertex index of every vertex's connected component (f2n_mesh_components); *rounds: labelling rounds

@@ -431,12 +431,15 @@ Tensor BrickMark(const Tensor& tree_nodes, const float lo[3], float step, const 
   return flags;
 }
 
-BrickMeshPart BrickMeshBatch(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step, float level, int B) {
+BrickMeshPart BrickMeshBatch(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step, float level, int B,
+                             const Tensor& valid) {
   torch::NoGradGuard g;
   const int64_t nbr = brick_ids.numel(), P = (int64_t) (B + 1) * (B + 1) * (B + 1);
   TORCH_CHECK(brick_ids.is_cuda() && brick_ids.scalar_type() == torch::kInt32 && brick_ids.is_contiguous(), "brick_ids must be device int32");
   TORCH_CHECK(values.is_cuda() && values.scalar_type() == torch::kFloat32 && values.is_contiguous() && values.numel() == nbr * P,
               "values must be device float32 [n_bricks, (B+1)^3]");
+  TORCH_CHECK(!valid.defined() || (valid.is_cuda() && valid.scalar_type() == torch::kUInt8 && valid.is_contiguous() && valid.numel() == nbr * P),
+              "valid must be device uint8 [n_bricks, (B+1)^3]");
   TORCH_CHECK(nbr <= INT32_MAX, "too many bricks in one batch");
   BrickMeshPart part;
   part.vert_keys = torch::empty({0}, DevI64());
@@ -445,7 +448,11 @@ BrickMeshPart BrickMeshBatch(const Tensor& values, const Tensor& brick_ids, cons
   part.face_vert_keys = torch::empty({0, 3}, DevI64());
   if (nbr == 0) return part;
   Tensor vc = torch::empty({nbr}, DevI32()), fc = torch::empty({nbr}, DevI32());
-  F2N_CALL(f2n_brick_mesh_count(CurStream(), n[0], n[1], n[2], B, (int) nbr, I32P(brick_ids), F32P(values), level, I32P(vc), I32P(fc)));
+  if (valid.defined())
+    F2N_CALL(f2n_brick_mesh_count_masked(CurStream(), n[0], n[1], n[2], B, (int) nbr, I32P(brick_ids), F32P(values), valid.data_ptr<uint8_t>(),
+                                         level, I32P(vc), I32P(fc)));
+  else
+    F2N_CALL(f2n_brick_mesh_count(CurStream(), n[0], n[1], n[2], B, (int) nbr, I32P(brick_ids), F32P(values), level, I32P(vc), I32P(fc)));
   Tensor vend = torch::cumsum(vc, 0, torch::kInt64), fend = torch::cumsum(fc, 0, torch::kInt64);
   Tensor tot = torch::stack({vend[-1], fend[-1], ((vc > 0) | (fc > 0)).sum()}).cpu();  // the one read-back: the totals size the outputs
   const int64_t nv = tot.data_ptr<int64_t>()[0], nf = tot.data_ptr<int64_t>()[1];
@@ -455,9 +462,14 @@ BrickMeshPart BrickMeshBatch(const Tensor& values, const Tensor& brick_ids, cons
   // (at least one row each: the emit wants its four outputs, and a batch may own vertices but no face or the other way round)
   Tensor vk = torch::empty({std::max<int64_t>(nv, 1)}, DevI64()), v = torch::empty({std::max<int64_t>(nv, 1), 3}, DevF32());
   Tensor fk = torch::empty({std::max<int64_t>(nf, 1)}, DevI64()), fvk = torch::empty({std::max<int64_t>(nf, 1), 3}, DevI64());
-  F2N_CALL(f2n_brick_mesh_emit(CurStream(), n[0], n[1], n[2], B, (int) nbr, I32P(brick_ids), F32P(values), level, lo, step,
-                               vstart.data_ptr<int64_t>(), fstart.data_ptr<int64_t>(), vk.data_ptr<int64_t>(), F32P(v), fk.data_ptr<int64_t>(),
-                               fvk.data_ptr<int64_t>()));
+  if (valid.defined())
+    F2N_CALL(f2n_brick_mesh_emit_masked(CurStream(), n[0], n[1], n[2], B, (int) nbr, I32P(brick_ids), F32P(values), valid.data_ptr<uint8_t>(),
+                                        level, lo, step, vstart.data_ptr<int64_t>(), fstart.data_ptr<int64_t>(), vk.data_ptr<int64_t>(), F32P(v),
+                                        fk.data_ptr<int64_t>(), fvk.data_ptr<int64_t>()));
+  else
+    F2N_CALL(f2n_brick_mesh_emit(CurStream(), n[0], n[1], n[2], B, (int) nbr, I32P(brick_ids), F32P(values), level, lo, step,
+                                 vstart.data_ptr<int64_t>(), fstart.data_ptr<int64_t>(), vk.data_ptr<int64_t>(), F32P(v), fk.data_ptr<int64_t>(),
+                                 fvk.data_ptr<int64_t>()));
   part.vert_keys = vk.narrow(0, 0, nv);
   part.verts = v.narrow(0, 0, nv);
   part.face_keys = fk.narrow(0, 0, nf);
@@ -465,7 +477,7 @@ BrickMeshPart BrickMeshBatch(const Tensor& values, const Tensor& brick_ids, cons
   return part;
 }
 
-std::tuple<Tensor, Tensor> BrickMeshAssemble(const std::vector<BrickMeshPart>& parts) {
+std::tuple<Tensor, Tensor> BrickMeshAssemble(const std::vector<BrickMeshPart>& parts, bool drop_unreferenced) {
   torch::NoGradGuard g;
   std::vector<Tensor> vk, v, fk, fvk;
   for (const auto& p : parts) {
@@ -482,17 +494,26 @@ std::tuple<Tensor, Tensor> BrickMeshAssemble(const std::vector<BrickMeshPart>& p
   auto sorted = torch::sort(keys);
   const Tensor& skeys = std::get<0>(sorted);
   verts = verts.index_select(0, std::get<1>(sorted)).contiguous();
-  if (nf == 0) return {verts, torch::empty({0, 3}, DevI32())};
+  if (nf == 0) return {drop_unreferenced ? torch::empty({0, 3}, DevF32()) : verts, torch::empty({0, 3}, DevI32())};
   if (nv == 0) throw std::invalid_argument("the brick list lacks the owner of a face's vertex");
   Tensor want = fverts.view({-1});
   Tensor at = torch::searchsorted(skeys, want).clamp_max(nv - 1);
   if (!(skeys.index_select(0, at) == want).all().item<bool>()) throw std::invalid_argument("the brick list lacks the owner of a face's vertex");
+  if (drop_unreferenced) {  // the vertices some face names, in key order; a face's index = the number of kept vertices in front of it
+    Tensor used = torch::zeros({nv}, DevI64());
+    used.index_fill_(0, at, 1);
+    Tensor rank = torch::cumsum(used, 0) - used;
+    verts = verts.index_select(0, torch::nonzero(used).view({-1})).contiguous();
+    at = rank.index_select(0, at);
+  }
   Tensor faces = at.to(torch::kInt32).view({-1, 3}).index_select(0, torch::argsort(fkeys)).contiguous();
   return {verts, faces};
 }
 
-std::tuple<Tensor, Tensor> MeshFromBricks(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step,
-                                          float level, int B, int64_t batch_bricks) {
+namespace {
+// valid: undefined = MeshFromBricks, else MeshFromBricksMasked
+std::tuple<Tensor, Tensor> MeshFromBricksImpl(const Tensor& values, const Tensor& valid, const Tensor& brick_ids, const int n[3],
+                                              const float lo[3], float step, float level, int B, int64_t batch_bricks) {
   torch::NoGradGuard g;
   int nb[3];
   const int64_t total = BrickCounts(n, B, nb);
@@ -501,13 +522,32 @@ std::tuple<Tensor, Tensor> MeshFromBricks(const Tensor& values, const Tensor& br
   Tensor vals = values.to(torch::kCUDA, torch::kFloat32).contiguous();
   TORCH_CHECK(vals.numel() == nbr * P, "values must be [n_bricks, (B+1)^3]");
   vals = vals.view({nbr, P});
+  Tensor ok;
+  if (valid.defined()) {
+    ok = valid.to(torch::kCUDA, torch::kUInt8).contiguous();
+    TORCH_CHECK(ok.numel() == nbr * P, "valid must be [n_bricks, (B+1)^3]");
+    ok = ok.view({nbr, P});
+  }
   const int64_t per = batch_bricks > 0 ? batch_bricks : std::max<int64_t>(nbr, 1);
   std::vector<BrickMeshPart> parts;
   for (int64_t j0 = 0; j0 < nbr; j0 += per) {
     const int64_t c = std::min(per, nbr - j0);
-    parts.push_back(BrickMeshBatch(vals.narrow(0, j0, c), ids.narrow(0, j0, c), n, lo, step, level, B));
+    parts.push_back(BrickMeshBatch(vals.narrow(0, j0, c), ids.narrow(0, j0, c), n, lo, step, level, B,
+                                   ok.defined() ? ok.narrow(0, j0, c) : Tensor()));
   }
-  return BrickMeshAssemble(parts);
+  return BrickMeshAssemble(parts, ok.defined());
+}
+}  // namespace
+
+std::tuple<Tensor, Tensor> MeshFromBricks(const Tensor& values, const Tensor& brick_ids, const int n[3], const float lo[3], float step,
+                                          float level, int B, int64_t batch_bricks) {
+  return MeshFromBricksImpl(values, Tensor(), brick_ids, n, lo, step, level, B, batch_bricks);
+}
+
+std::tuple<Tensor, Tensor> MeshFromBricksMasked(const Tensor& values, const Tensor& valid, const Tensor& brick_ids, const int n[3],
+                                                const float lo[3], float step, float level, int B, int64_t batch_bricks) {
+  TORCH_CHECK(valid.defined(), "valid is required");
+  return MeshFromBricksImpl(values, valid, brick_ids, n, lo, step, level, B, batch_bricks);
 }
 
 std::tuple<Tensor, Tensor> Renderer::ExtractMeshSparse(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level,
@@ -590,6 +630,109 @@ std::tuple<Tensor, Tensor> TsdfFinalize(const Tensor& S, const Tensor& W, float 
   Tensor out = torch::empty_like(S), valid = torch::empty(S.sizes(), torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA));
   F2N_CALL(f2n_tsdf_finalize(CurStream(), S.numel(), F32P(S), F32P(W), min_weight, F32P(out), valid.data_ptr<uint8_t>()));
   return {out, valid};
+}
+
+// ---- sparse TSDF fusion on bricks (include/f2n_abi.h, "Sparse TSDF fusion on bricks") -----------------------------------------
+namespace {
+// the views of TsdfIntegrate as contiguous device float32 tensors: {poses, intri, dist, depth, conf or undefined}
+struct TsdfViews {
+  Tensor po, in, di, de, co;
+  int V = 0, h = 0, w = 0;
+};
+TsdfViews CheckedViews(const Tensor& poses, const Tensor& intri, const Tensor& dist, const Tensor& depth, const Tensor& conf) {
+  TsdfViews v;
+  v.po = poses.to(torch::kCUDA, torch::kFloat32).contiguous(), v.in = intri.to(torch::kCUDA, torch::kFloat32).contiguous();
+  v.di = dist.to(torch::kCUDA, torch::kFloat32).contiguous(), v.de = depth.to(torch::kCUDA, torch::kFloat32).contiguous();
+  TORCH_CHECK(v.de.dim() == 3, "depth must be [V, h, w]");
+  const int64_t V = v.de.size(0);
+  TORCH_CHECK(V <= INT32_MAX && v.po.numel() == V * 12 && v.in.numel() == V * 9 && v.di.numel() == V * 4,
+              "poses [V,3,4], intri [V,3,3] and dist_params [V,4] must match depth [V,h,w]");
+  if (conf.defined()) {
+    v.co = conf.to(torch::kCUDA, torch::kFloat32).contiguous();
+    TORCH_CHECK(v.co.sizes() == v.de.sizes(), "conf must have the shape of depth");
+  }
+  v.V = (int) V, v.h = (int) v.de.size(1), v.w = (int) v.de.size(2);
+  return v;
+}
+void CheckTrunc(float trunc) {
+  if (!(trunc > 0.f) || !std::isfinite(trunc)) throw std::invalid_argument("trunc must be positive and finite");
+}
+
+Tensor TsdfBrickMarkViews(const float lo[3], float step, const int n[3], int B, const TsdfViews& v, float trunc) {
+  int nb[3];
+  BrickCounts(n, B, nb);
+  CheckTrunc(trunc);
+  Tensor flags = torch::zeros({nb[2], nb[1], nb[0]}, torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA));
+  F2N_CALL(f2n_tsdf_brick_mark(CurStream(), lo, step, n[0], n[1], n[2], B, v.V, F32P(v.po), F32P(v.in), F32P(v.di), F32P(v.de),
+                               v.co.defined() ? F32P(v.co) : nullptr, v.h, v.w, trunc, flags.data_ptr<uint8_t>()));
+  return flags;
+}
+
+// ids: device int32, checked
+void TsdfIntegrateBrickRows(const Tensor& S, const Tensor& W, const Tensor& ids, const float lo[3], float step, const int n[3], int B,
+                            const TsdfViews& v, float trunc) {
+  const int64_t P = (int64_t) (B + 1) * (B + 1) * (B + 1);
+  DevArg(S, torch::kFloat32, "S");
+  DevArg(W, torch::kFloat32, "W");
+  TORCH_CHECK(S.numel() == ids.numel() * P && W.numel() == S.numel(), "S and W must be [n_bricks, (B+1)^3]");
+  TORCH_CHECK(S.numel() <= INT32_MAX, "too many bricks in one batch");
+  F2N_CALL(f2n_tsdf_integrate_bricks(CurStream(), lo, step, n[0], n[1], n[2], B, (int) ids.numel(), I32P(ids), v.V, F32P(v.po), F32P(v.in),
+                                     F32P(v.di), F32P(v.de), v.co.defined() ? F32P(v.co) : nullptr, v.h, v.w, trunc, F32P(S), F32P(W)));
+}
+}  // namespace
+
+Tensor TsdfBrickMark(const float lo[3], float step, const int n[3], int B, const Tensor& poses, const Tensor& intri, const Tensor& dist,
+                     const Tensor& depth, const Tensor& conf, float trunc) {
+  torch::NoGradGuard g;
+  return TsdfBrickMarkViews(lo, step, n, B, CheckedViews(poses, intri, dist, depth, conf), trunc);
+}
+
+void TsdfIntegrateBricks(const Tensor& S, const Tensor& W, const Tensor& brick_ids, const float lo[3], float step, const int n[3], int B,
+                         const Tensor& poses, const Tensor& intri, const Tensor& dist, const Tensor& depth, const Tensor& conf, float trunc) {
+  torch::NoGradGuard g;
+  int nb[3];
+  const int64_t total = BrickCounts(n, B, nb);
+  CheckTrunc(trunc);
+  TsdfIntegrateBrickRows(S, W, CheckedBrickIds(brick_ids, total), lo, step, n, B, CheckedViews(poses, intri, dist, depth, conf), trunc);
+}
+
+std::tuple<Tensor, Tensor> TsdfMeshSparse(const float lo[3], float step, const int n[3], int B, const Tensor& poses, const Tensor& intri,
+                                          const Tensor& dist, const Tensor& depth, const Tensor& conf, float trunc, float min_weight,
+                                          int64_t batch_bricks, SparseTsdfStats* stats) {
+  torch::NoGradGuard g;
+  int nb[3];
+  const int64_t total = BrickCounts(n, B, nb);
+  const TsdfViews v = CheckedViews(poses, intri, dist, depth, conf);
+  Tensor flags = TsdfBrickMarkViews(lo, step, n, B, v, trunc);
+  Tensor ids = torch::nonzero(flags.view({-1})).view({-1}).to(torch::kInt32).contiguous();  // ascending
+  const int64_t n_active = ids.numel(), S1 = B + 1, P = S1 * S1 * S1;
+  const int64_t per = std::max<int64_t>(1, batch_bricks);
+  SparseTsdfStats st;
+  st.bricks = total;
+  st.active_bricks = n_active;
+  for (int k = 0; k < 3; k++) st.grid[k] = n[k];
+  if (n_active > 0) {  // the corners of the listed bricks that exist: per axis min(B + 1, n - b B)
+    Tensor b = ids.to(torch::kInt64), cnt = torch::ones_like(b);
+    Tensor bc[3] = {b % nb[0], torch::floor_divide(b, nb[0]) % nb[1], torch::floor_divide(b, (int64_t) nb[0] * nb[1])};
+    for (int k = 0; k < 3; k++) cnt = cnt * torch::clamp_max(n[k] - bc[k] * B, S1);
+    st.points_evaluated = cnt.sum().item<int64_t>();
+  }
+  std::vector<BrickMeshPart> parts;
+  Tensor known = torch::zeros({1}, DevI64());
+  for (int64_t j0 = 0; j0 < n_active; j0 += per) {  // one batch of rows alive at a time
+    const int64_t c = std::min(per, n_active - j0);
+    Tensor batch = ids.narrow(0, j0, c);
+    Tensor S = torch::zeros({c, P}, DevF32()), W = torch::zeros({c, P}, DevF32());
+    TsdfIntegrateBrickRows(S, W, batch, lo, step, n, B, v, trunc);
+    auto [gv, valid] = TsdfFinalize(S, W, min_weight);
+    known += (valid != 0).sum();  // (a corner that does not exist keeps W = 0: never valid)
+    parts.push_back(BrickMeshBatch(gv, batch, n, lo, step, 0.f, B, valid));
+    st.meshed_bricks += parts.back().meshed_bricks;
+    st.batches++;
+  }
+  st.points_known = known.item<int64_t>();
+  if (stats != nullptr) *stats = st;
+  return BrickMeshAssemble(parts, true);
 }
 
 std::tuple<Tensor, Tensor> Renderer::ExtractMesh(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level) {

@@ -174,6 +174,57 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
         },
         py::arg("S"), py::arg("W"), py::arg("min_weight"));
+  // sparse TSDF fusion on bricks of B^3 cells of the virtual grid (lo, step, n = (nx, ny, nz)); the views as tsdf_integrate takes them:
+  // flags [nbz, nby, nbx] uint8 of the bricks whose row holds a corner seen at most trunc behind a view's surface (f2n_tsdf_brick_mark) ...
+  m.def("tsdf_brick_mark",
+        [](const std::vector<float>& lo, float step, const std::vector<int>& n, int B, const Tensor& poses, const Tensor& intri,
+           const Tensor& dist, const Tensor& depth, const c10::optional<Tensor>& conf, float trunc) {
+          if (lo.size() != 3 || n.size() != 3) throw std::invalid_argument("lo and n must have three entries");
+          return TsdfBrickMark(lo.data(), step, n.data(), B, poses, intri, dist, depth, conf.has_value() ? *conf : Tensor(), trunc);
+        },
+        py::arg("lo"), py::arg("step"), py::arg("n"), py::arg("B"), py::arg("poses"), py::arg("intri"), py::arg("dist"), py::arg("depth"),
+        py::arg("conf"), py::arg("trunc"));
+  // ... the views added to the rows S, W [n_bricks, (B+1)^3] of brick_ids, in place (f2n_tsdf_integrate_bricks) ...
+  m.def("tsdf_integrate_bricks",
+        [](const Tensor& S, const Tensor& W, const Tensor& brick_ids, const std::vector<float>& lo, float step, const std::vector<int>& n, int B,
+           const Tensor& poses, const Tensor& intri, const Tensor& dist, const Tensor& depth, const c10::optional<Tensor>& conf, float trunc) {
+          if (lo.size() != 3 || n.size() != 3) throw std::invalid_argument("lo and n must have three entries");
+          TsdfIntegrateBricks(S, W, brick_ids, lo.data(), step, n.data(), B, poses, intri, dist, depth, conf.has_value() ? *conf : Tensor(),
+                              trunc);
+        },
+        py::arg("S"), py::arg("W"), py::arg("brick_ids"), py::arg("lo"), py::arg("step"), py::arg("n"), py::arg("B"), py::arg("poses"),
+        py::arg("intri"), py::arg("dist"), py::arg("depth"), py::arg("conf"), py::arg("trunc"));
+  // ... (verts, faces) of values / valid [n_bricks, (B+1)^3] (f2n_brick_mesh_count_masked / _emit_masked, sorted by key, without the
+  // vertices no face names): the bits of mesh_from_grid_masked when the list holds the owner of every face ...
+  m.def("mesh_from_bricks_masked",
+        [](const Tensor& values, const Tensor& valid, const Tensor& brick_ids, const std::vector<int>& n, const std::vector<float>& lo,
+           float step, float level, int B, int64_t batch_bricks) {
+          if (lo.size() != 3 || n.size() != 3) throw std::invalid_argument("lo and n must have three entries");
+          auto t = MeshFromBricksMasked(values, valid, brick_ids, n.data(), lo.data(), step, level, B, batch_bricks);
+          return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
+        },
+        py::arg("values"), py::arg("valid"), py::arg("brick_ids"), py::arg("n"), py::arg("lo"), py::arg("step"), py::arg("level"), py::arg("B"),
+        py::arg("batch_bricks") = 0);
+  // ... and the whole chain with one batch of batch_bricks rows alive at a time: (verts, faces, stats)
+  m.def("tsdf_mesh_sparse",
+        [](const std::vector<float>& lo, float step, const std::vector<int>& n, int B, const Tensor& poses, const Tensor& intri,
+           const Tensor& dist, const Tensor& depth, const c10::optional<Tensor>& conf, float trunc, float min_weight, int64_t batch_bricks) {
+          if (lo.size() != 3 || n.size() != 3) throw std::invalid_argument("lo and n must have three entries");
+          SparseTsdfStats st;
+          auto t = TsdfMeshSparse(lo.data(), step, n.data(), B, poses, intri, dist, depth, conf.has_value() ? *conf : Tensor(), trunc,
+                                  min_weight, batch_bricks, &st);
+          py::dict stats;
+          stats["bricks"] = st.bricks;
+          stats["active_bricks"] = st.active_bricks;
+          stats["meshed_bricks"] = st.meshed_bricks;
+          stats["points_evaluated"] = st.points_evaluated;
+          stats["points_known"] = st.points_known;
+          stats["batches"] = st.batches;
+          stats["grid"] = py::make_tuple(st.grid[0], st.grid[1], st.grid[2]);
+          return py::make_tuple(std::get<0>(t), std::get<1>(t), stats);
+        },
+        py::arg("lo"), py::arg("step"), py::arg("n"), py::arg("B"), py::arg("poses"), py::arg("intri"), py::arg("dist"), py::arg("depth"),
+        py::arg("conf"), py::arg("trunc"), py::arg("min_weight"), py::arg("batch_bricks"));
   // unit normals [n,3] at pts [n,3] from the gradient of any float32 grid [nz, ny, nx] (f2n_grid_normals)
   m.def("grid_normals",
         [](const Tensor& grid, const Tensor& pts, const std::vector<float>& lo, float step) {

@@ -705,7 +705,8 @@ __global__ void __launch_bounds__(256) oct_locate_warp_bricks_kernel(BrickGrid g
   out_anchors[i * 3 + 2] = 0;
 }
 
-// One brick of the list per workgroup of 256 threads, its values in LDS.
+// One brick of the list per workgroup of 256 threads, its values in LDS.  MASKED (f2n_brick_mesh_count_masked / _emit_masked): the row
+// of `valid` bytes is staged next to the values (s_ok); an edge needs both endpoints valid, a cell all eight corners.
 template <int B>
 struct BrickTile {
   static constexpr int S = B + 1, P = S * S * S, CELLS = B * B * B;
@@ -725,19 +726,26 @@ struct BrickTile {
       last[k] = bc[k] == nb[k] - 1;
     }
   }
-  __device__ __forceinline__ void stage(const float* __restrict__ values, float* s_val) const {
+  template <bool MASKED>
+  __device__ __forceinline__ void stage(const float* __restrict__ values, const uint8_t* __restrict__ valid, float* s_val, uint8_t* s_ok) const {
     const float* src = values + (int64_t) blockIdx.x * P;
     for (int i = threadIdx.x; i < P; i += 256) s_val[i] = src[i];
+    if (MASKED) {
+      const uint8_t* ok = valid + (int64_t) blockIdx.x * P;
+      for (int i = threadIdx.x; i < P; i += 256) s_ok[i] = ok[i];
+    }
     __syncthreads();
   }
   static __device__ __forceinline__ int local(int lx, int ly, int lz) { return (lz * S + ly) * S + lx; }
   // bit t: the edge of type t owned by the local corner l crosses the level; 0 for a corner this brick does not own
-  __device__ __forceinline__ uint32_t corner_edges(const float* s_val, int l, float level) const {
+  template <bool MASKED>
+  __device__ __forceinline__ uint32_t corner_edges(const float* s_val, const uint8_t* s_ok, int l, float level) const {
     if (l >= P) return 0;
     const int lc[3] = {l % S, (l / S) % S, l / (S * S)};
 #pragma unroll
     for (int k = 0; k < 3; k++)
       if ((lc[k] >= B && !last[k]) || x0[k] + lc[k] > n[k] - 1) return 0;
+    if (MASKED && s_ok[l] == 0) return 0;
     const bool in0 = mesh_inside(s_val[l], level);
     uint32_t m = 0;
 #pragma unroll
@@ -745,17 +753,26 @@ struct BrickTile {
       const int dx = o & 1, dy = (o >> 1) & 1, dz = (o >> 2) & 1;
       if (lc[0] + dx > B || lc[1] + dy > B || lc[2] + dz > B) continue;
       if (x0[0] + lc[0] + dx > n[0] - 1 || x0[1] + lc[1] + dy > n[1] - 1 || x0[2] + lc[2] + dz > n[2] - 1) continue;
+      if (MASKED && s_ok[local(lc[0] + dx, lc[1] + dy, lc[2] + dz)] == 0) continue;
       if (in0 != mesh_inside(s_val[local(lc[0] + dx, lc[1] + dy, lc[2] + dz)], level)) m |= 1u << c_edge_type[o];
     }
     return m;
   }
-  // the inside mask of the owned cell c (local index in [0, B)^3, x fastest), 0 for a cell outside the grid; lc receives its local corner
-  __device__ __forceinline__ int cell_inside(const float* s_val, int c, float level, int lc[3]) const {
+  // the inside mask of the owned cell c (local index in [0, B)^3, x fastest), 0 for a cell outside the grid (MASKED: and for a cell with
+  // a corner that is not valid); lc receives its local corner
+  template <bool MASKED>
+  __device__ __forceinline__ int cell_inside(const float* s_val, const uint8_t* s_ok, int c, float level, int lc[3]) const {
     lc[0] = c % B, lc[1] = (c / B) % B, lc[2] = c / (B * B);
     if (c >= CELLS) return 0;
 #pragma unroll
     for (int k = 0; k < 3; k++)
       if (x0[k] + lc[k] + 1 > n[k] - 1) return 0;
+    if (MASKED) {
+      bool all = true;
+#pragma unroll
+      for (int o = 0; o < 8; o++) all = all && s_ok[local(lc[0] + (o & 1), lc[1] + ((o >> 1) & 1), lc[2] + ((o >> 2) & 1))] != 0;
+      if (!all) return 0;
+    }
     int m = 0;
 #pragma unroll
     for (int o = 0; o < 8; o++)
@@ -797,21 +814,22 @@ __device__ __forceinline__ int block_scan_256(int v, int* s_wave, int* total) {
   return base + inc - v;
 }
 
-template <int B>
+template <int B, bool MASKED>
 __global__ void __launch_bounds__(256) brick_mesh_count_kernel(int nx, int ny, int nz, const int32_t* __restrict__ brick_ids,
-                                                              const float* __restrict__ values, float level,
+                                                              const float* __restrict__ values, const uint8_t* __restrict__ valid, float level,
                                                               int32_t* __restrict__ vert_counts, int32_t* __restrict__ face_counts) {
   using Tile = BrickTile<B>;
   __shared__ float s_val[Tile::P];
+  __shared__ uint8_t s_ok[MASKED ? Tile::P : 1];
   __shared__ int s_wave[4];
   Tile tile;
   tile.init(nx, ny, nz, brick_ids[blockIdx.x]);
-  tile.stage(values, s_val);
+  tile.template stage<MASKED>(values, valid, s_val, s_ok);
   int nv = 0, nf = 0;
-  for (int l = threadIdx.x; l < Tile::P; l += 256) nv += __popc(tile.corner_edges(s_val, l, level));
+  for (int l = threadIdx.x; l < Tile::P; l += 256) nv += __popc(tile.template corner_edges<MASKED>(s_val, s_ok, l, level));
   for (int c = threadIdx.x; c < Tile::CELLS; c += 256) {
     int lc[3];
-    nf += cell_face_count(tile.cell_inside(s_val, c, level, lc));
+    nf += cell_face_count(tile.template cell_inside<MASKED>(s_val, s_ok, c, level, lc));
   }
   nv = block_sum_256(nv, s_wave);
   nf = block_sum_256(nf, s_wave);
@@ -822,22 +840,23 @@ __global__ void __launch_bounds__(256) brick_mesh_count_kernel(int nx, int ny, i
 }
 
 // vertices: local corners in rounds of 256, a block scan per round; within a corner by edge type
-template <int B>
+template <int B, bool MASKED>
 __global__ void __launch_bounds__(256) brick_vert_emit_kernel(int nx, int ny, int nz, const int32_t* __restrict__ brick_ids,
-                                                             const float* __restrict__ values, float level, float lo0, float lo1, float lo2,
+                                                             const float* __restrict__ values, const uint8_t* __restrict__ valid, float level, float lo0, float lo1, float lo2,
                                                              float step, const long long* __restrict__ vert_start,
                                                              long long* __restrict__ vert_keys, float* __restrict__ verts) {
   using Tile = BrickTile<B>;
   __shared__ float s_val[Tile::P];
+  __shared__ uint8_t s_ok[MASKED ? Tile::P : 1];
   __shared__ int s_wave[4];
   Tile tile;
   tile.init(nx, ny, nz, brick_ids[blockIdx.x]);
-  tile.stage(values, s_val);
+  tile.template stage<MASKED>(values, valid, s_val, s_ok);
   const int S = Tile::S;
   long long v_base = vert_start[blockIdx.x];
   for (int l0 = 0; l0 < Tile::P; l0 += 256) {
     const int l = l0 + threadIdx.x;
-    const uint32_t m = tile.corner_edges(s_val, l, level);
+    const uint32_t m = tile.template corner_edges<MASKED>(s_val, s_ok, l, level);
     int total;
     const long long v = v_base + block_scan_256(__popc(m), s_wave, &total);
     v_base += total;
@@ -865,21 +884,22 @@ __global__ void __launch_bounds__(256) brick_vert_emit_kernel(int nx, int ny, in
 }
 
 // faces: owned cells in rounds of 256, a block scan per round; a face names its vertices by their keys
-template <int B>
+template <int B, bool MASKED>
 __global__ void __launch_bounds__(256) brick_face_emit_kernel(int nx, int ny, int nz, const int32_t* __restrict__ brick_ids,
-                                                             const float* __restrict__ values, float level,
+                                                             const float* __restrict__ values, const uint8_t* __restrict__ valid, float level,
                                                              const long long* __restrict__ face_start, long long* __restrict__ face_keys,
                                                              long long* __restrict__ face_vert_keys) {
   using Tile = BrickTile<B>;
   __shared__ float s_val[Tile::P];
+  __shared__ uint8_t s_ok[MASKED ? Tile::P : 1];
   __shared__ int s_wave[4];
   Tile tile;
   tile.init(nx, ny, nz, brick_ids[blockIdx.x]);
-  tile.stage(values, s_val);
+  tile.template stage<MASKED>(values, valid, s_val, s_ok);
   long long f_base = face_start[blockIdx.x];
   for (int c0 = 0; c0 < Tile::CELLS; c0 += 256) {
     int lc[3];
-    const int cm = tile.cell_inside(s_val, c0 + threadIdx.x, level, lc);
+    const int cm = tile.template cell_inside<MASKED>(s_val, s_ok, c0 + threadIdx.x, level, lc);
     int total;
     long long f = f_base + block_scan_256(cell_face_count(cm), s_wave, &total);
     f_base += total;
@@ -1069,28 +1089,37 @@ int f2n_oct_locate_warp_bricks(void* stream, const float* lo /*host [3]*/, float
   return f2n_launch_status();
 }
 
-int f2n_brick_mesh_count(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids, const float* values,
-                         float level, int32_t* vert_counts, int32_t* face_counts) {
+// valid == nullptr: the unmasked kernels (f2n_brick_mesh_count / _emit), else the masked ones
+static int brick_mesh_count(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids, const float* values,
+                            const uint8_t* valid, bool masked, float level, int32_t* vert_counts, int32_t* face_counts) {
   BrickGrid g;
   int64_t n_total;
   const int e = brick_grid(nullptr, 1.f, nx, ny, nz, B, &g, &n_total);
   if (e != F2N_OK) return e;
   if (n_bricks < 0) return F2N_ERR_INVALID_ARG;
   if (n_bricks == 0) return F2N_OK;
-  if (brick_ids == nullptr || values == nullptr || vert_counts == nullptr || face_counts == nullptr) return F2N_ERR_INVALID_ARG;
-#define F2N_BRICK_COUNT(BB)                                                                                                          \
-  hipLaunchKernelGGL(brick_mesh_count_kernel<BB>, dim3(n_bricks), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, brick_ids, values, \
-                     level, vert_counts, face_counts)
-  if (B == 4) F2N_BRICK_COUNT(4);
-  else if (B == 8) F2N_BRICK_COUNT(8);
-  else F2N_BRICK_COUNT(16);
+  if (brick_ids == nullptr || values == nullptr || vert_counts == nullptr || face_counts == nullptr || (masked && valid == nullptr))
+    return F2N_ERR_INVALID_ARG;
+#define F2N_BRICK_COUNT(BB, MM)                                                                                                          \
+  hipLaunchKernelGGL((brick_mesh_count_kernel<BB, MM>), dim3(n_bricks), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, brick_ids, values, \
+                     valid, level, vert_counts, face_counts)
+  if (masked) {
+    if (B == 4) F2N_BRICK_COUNT(4, true);
+    else if (B == 8) F2N_BRICK_COUNT(8, true);
+    else F2N_BRICK_COUNT(16, true);
+  } else {
+    if (B == 4) F2N_BRICK_COUNT(4, false);
+    else if (B == 8) F2N_BRICK_COUNT(8, false);
+    else F2N_BRICK_COUNT(16, false);
+  }
 #undef F2N_BRICK_COUNT
   return f2n_launch_status();
 }
 
-int f2n_brick_mesh_emit(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids, const float* values,
-                        float level, const float* lo /*host [3]*/, float step, const int64_t* vert_start, const int64_t* face_start,
-                        int64_t* vert_keys, float* verts, int64_t* face_keys, int64_t* face_vert_keys) {
+static int brick_mesh_emit(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids, const float* values,
+                           const uint8_t* valid, bool masked, float level, const float* lo /*host [3]*/, float step,
+                           const int64_t* vert_start, const int64_t* face_start, int64_t* vert_keys, float* verts, int64_t* face_keys,
+                           int64_t* face_vert_keys) {
   if (lo == nullptr) return F2N_ERR_INVALID_ARG;
   BrickGrid g;
   int64_t n_total;
@@ -1099,20 +1128,50 @@ int f2n_brick_mesh_emit(void* stream, int nx, int ny, int nz, int B, int n_brick
   if (n_bricks < 0) return F2N_ERR_INVALID_ARG;
   if (n_bricks == 0) return F2N_OK;
   if (brick_ids == nullptr || values == nullptr || vert_start == nullptr || face_start == nullptr || vert_keys == nullptr ||
-      verts == nullptr || face_keys == nullptr || face_vert_keys == nullptr)
+      verts == nullptr || face_keys == nullptr || face_vert_keys == nullptr || (masked && valid == nullptr))
     return F2N_ERR_INVALID_ARG;
-#define F2N_BRICK_EMIT(BB)                                                                                                            \
-  do {                                                                                                                                \
-    hipLaunchKernelGGL(brick_vert_emit_kernel<BB>, dim3(n_bricks), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, brick_ids, values, \
-                       level, lo[0], lo[1], lo[2], step, (const long long*) vert_start, (long long*) vert_keys, verts);              \
-    hipLaunchKernelGGL(brick_face_emit_kernel<BB>, dim3(n_bricks), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, brick_ids, values, \
-                       level, (const long long*) face_start, (long long*) face_keys, (long long*) face_vert_keys);                   \
+#define F2N_BRICK_EMIT(BB, MM)                                                                                                             \
+  do {                                                                                                                                     \
+    hipLaunchKernelGGL((brick_vert_emit_kernel<BB, MM>), dim3(n_bricks), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, brick_ids, values, \
+                       valid, level, lo[0], lo[1], lo[2], step, (const long long*) vert_start, (long long*) vert_keys, verts);            \
+    hipLaunchKernelGGL((brick_face_emit_kernel<BB, MM>), dim3(n_bricks), dim3(256), 0, (hipStream_t) stream, nx, ny, nz, brick_ids, values, \
+                       valid, level, (const long long*) face_start, (long long*) face_keys, (long long*) face_vert_keys);                 \
   } while (0)
-  if (B == 4) F2N_BRICK_EMIT(4);
-  else if (B == 8) F2N_BRICK_EMIT(8);
-  else F2N_BRICK_EMIT(16);
+  if (masked) {
+    if (B == 4) F2N_BRICK_EMIT(4, true);
+    else if (B == 8) F2N_BRICK_EMIT(8, true);
+    else F2N_BRICK_EMIT(16, true);
+  } else {
+    if (B == 4) F2N_BRICK_EMIT(4, false);
+    else if (B == 8) F2N_BRICK_EMIT(8, false);
+    else F2N_BRICK_EMIT(16, false);
+  }
 #undef F2N_BRICK_EMIT
   return f2n_launch_status();
+}
+
+int f2n_brick_mesh_count(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids, const float* values,
+                         float level, int32_t* vert_counts, int32_t* face_counts) {
+  return brick_mesh_count(stream, nx, ny, nz, B, n_bricks, brick_ids, values, nullptr, false, level, vert_counts, face_counts);
+}
+
+int f2n_brick_mesh_emit(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids, const float* values,
+                        float level, const float* lo /*host [3]*/, float step, const int64_t* vert_start, const int64_t* face_start,
+                        int64_t* vert_keys, float* verts, int64_t* face_keys, int64_t* face_vert_keys) {
+  return brick_mesh_emit(stream, nx, ny, nz, B, n_bricks, brick_ids, values, nullptr, false, level, lo, step, vert_start, face_start, vert_keys,
+                         verts, face_keys, face_vert_keys);
+}
+
+int f2n_brick_mesh_count_masked(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids, const float* values,
+                                const uint8_t* valid, float level, int32_t* vert_counts, int32_t* face_counts) {
+  return brick_mesh_count(stream, nx, ny, nz, B, n_bricks, brick_ids, values, valid, true, level, vert_counts, face_counts);
+}
+
+int f2n_brick_mesh_emit_masked(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids, const float* values,
+                               const uint8_t* valid, float level, const float* lo /*host [3]*/, float step, const int64_t* vert_start,
+                               const int64_t* face_start, int64_t* vert_keys, float* verts, int64_t* face_keys, int64_t* face_vert_keys) {
+  return brick_mesh_emit(stream, nx, ny, nz, B, n_bricks, brick_ids, values, valid, true, level, lo, step, vert_start, face_start, vert_keys,
+                         verts, face_keys, face_vert_keys);
 }
 
 // =====================================================================================================================

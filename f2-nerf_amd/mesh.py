@@ -5,7 +5,7 @@ forward -> f2n_mesh_count / f2n_mesh_emit); this module only picks the options, 
 frame and writes the PLY file.
 
 Options (hydra-style overrides, no `mesh` group in the configs):
-  mesh.resolution  cells along the longest side of the box (default 256; at most 1024, with mesh.sparse at most 8192)
+  mesh.resolution  cells along the longest side of the box (default 256; at most 1024, with mesh.sparse or tsdf.sparse at most 8192)
   mesh.level       density iso-level (default DEFAULT_LEVEL)
   mesh.bbox_min / mesh.bbox_max  the box in the NORMALISED scene frame (default: pts_sampler.bbox_min / bbox_max, [-1, 1]^3,
                    which holds the normalised cameras; the octree's root cube is 512 wide and mostly empty)
@@ -74,7 +74,7 @@ Options (hydra-style overrides, no `mesh` group in the configs):
                    the printed line gains the active and total brick counts.  It composes with mesh.simplify, mesh.refine,
                    mesh.texture, mesh.check and mesh.distance* as the dense path does.  No dense grid exists, so normals and colours
                    (mesh.normals, mesh.colors, mesh.texture) need mesh.normal_source=field -- a vertex where the field's gradient
-                   vanishes then keeps the normal (0, 0, 0) -- and mesh.source=tsdf is refused (the fusion keeps its dense sums):
+                   vanishes then keeps the normal (0, 0, 0) -- and mesh.source=tsdf is refused (its sparse path is tsdf.sparse):
                    both are a ValueError before anything is extracted.  mesh.level must be >= 0 (the cull is exact only then).
                    B = 8 is a choice, not a measurement: a brick evaluates (B + 1)^3 corners for B^3 cells, (9/8)^3 = 1.42x
                    duplicated corners against 1.20x at 16, and culls at a finer grain
@@ -89,6 +89,16 @@ and the masked mesher leaves the surface open where no camera looked (f2n_mesh_c
   tsdf.min_weight    a grid point is known where its summed weight reaches this (default 1.0)
   tsdf.views_per_batch  cameras rendered per integration launch (default 8); the result does not depend on it
   tsdf.max_views     only the first N training cameras are fused (default 0: all)
+  tsdf.sparse        true | 4 | 8 | 16 (true = 8; default false): the same mesh, bit for bit, without the dense sums (fuse_tsdf_sparse):
+                     the views' depth maps are kept on the device, the bricks of B^3 cells whose corners some view sees at most the
+                     truncation behind its surface are marked (f2n_tsdf_brick_mark), and only those are integrated, finalized and
+                     meshed, a batch of rows at a time; memory follows the batch, the mesh and the depth maps (8 B per depth pixel
+                     and view), not the box, and mesh.resolution may go up to 8192.  The mark costs what a dense integration costs in
+                     arithmetic (grid points x views): the option saves memory, not time.  The file name is unchanged and the printed
+                     line names the brick counts in the place of the known grid points.  No dense TSDF exists, so mesh.normals,
+                     mesh.colors and mesh.texture need mesh.normal_source=field (a vertex where the field's gradient vanishes keeps
+                     the normal (0, 0, 0)): anything else is a ValueError before a view is rendered.  B = 8 is inherited from
+                     mesh.sparse, not measured for this path.  (mesh.sparse itself stays refused with mesh.source=tsdf.)
 
 Point-cloud export: `mode=extract_points is_continue=true` renders every training camera with runner.render_geometry and writes the
 rays' surface points, oriented and coloured, to <exp>/points/<iter>.ply in the data set's world frame (the usual input of a Poisson
@@ -215,6 +225,11 @@ def tsdf_options(cfg):
     o = {"res_level": int(t.get("res_level", 4)), "trunc_voxels": float(t.get("trunc_voxels", 4.0)), "tau": float(t.get("tau", 0.5)),
          "min_opacity": float(t.get("min_opacity", 0.5)), "min_weight": float(t.get("min_weight", 1.0)),
          "views_per_batch": int(t.get("views_per_batch", 8)), "max_views": int(t.get("max_views", 0))}
+    if "sparse" in t:  # (absent without the key: the dense export's options are what they were)
+        try:
+            o["sparse"] = _sparse(t["sparse"])
+        except ValueError:
+            raise ValueError("tsdf.sparse must be true, false, 4, 8 or 16, got %r" % (t["sparse"],)) from None
     if (o["res_level"] < 1 or o["views_per_batch"] < 1 or o["max_views"] < 0 or not 0.0 < o["tau"] <= 1.0 or
             not 0.0 < o["trunc_voxels"] < float("inf") or not o["min_weight"] >= 0.0 or not o["min_opacity"] >= 0.0):
         raise ValueError("tsdf.res_level and tsdf.views_per_batch must be >= 1, tsdf.max_views >= 0, tsdf.tau in (0, 1], tsdf.trunc_voxels "
@@ -395,6 +410,16 @@ def tsdf_intrinsics(intri, s):
     return k
 
 
+def _tsdf_view_maps(runner, dataset, scene, o, idx):
+    """(depth, conf) [h, w] of training camera idx as the TSDF takes them: the rays' surface distance where the ray has a surface and
+    its opacity reaches o["min_opacity"] (0 elsewhere), and the opacity."""
+    import torch
+    ro, rd, b, h, w = tsdf_camera_rays(dataset, scene["bounds"], idx, int(o["res_level"]))
+    g = runner.render_geometry(ro, rd, b, tau=o["tau"])
+    hit = (g["surf_idx"] >= 0) & (g["opacity"] >= o["min_opacity"])
+    return torch.where(hit, g["surf_t"], torch.zeros_like(g["surf_t"])).reshape(h, w), g["opacity"].reshape(h, w)
+
+
 def fuse_tsdf(runner, dataset, scene, o):
     """The training views' rendered depth fused into a TSDF on the grid of o["bbox_min"] / o["bbox_max"] / o["resolution"] (the grid of
     runner.density_grid).  o: options() and tsdf_options() in one dict.  Returns dict(g [nz, ny, nx] positive inside, valid uint8, S, W,
@@ -416,17 +441,53 @@ def fuse_tsdf(runner, dataset, scene, o):
         batch = views[k:k + o["views_per_batch"]]
         depth, conf = [], []
         for idx in batch:
-            ro, rd, b, h, w = tsdf_camera_rays(dataset, scene["bounds"], idx, s)
-            g = runner.render_geometry(ro, rd, b, tau=o["tau"])
-            hit = (g["surf_idx"] >= 0) & (g["opacity"] >= o["min_opacity"])
-            depth.append(torch.where(hit, g["surf_t"], torch.zeros_like(g["surf_t"])).reshape(h, w))
-            conf.append(g["opacity"].reshape(h, w))
+            d, c = _tsdf_view_maps(runner, dataset, scene, o, idx)
+            depth.append(d)
+            conf.append(c)
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()  # noqa: E731
         host.tsdf_integrate(S, W, lo, step, dev(np.asarray(scene["poses"], np.float32)[batch]), dev(tsdf_intrinsics(np.asarray(scene["intri"])[batch], s)),
                             dev(np.asarray(scene["dist_params"], np.float32)[batch]), torch.stack(depth).contiguous(),
                             torch.stack(conf).contiguous(), trunc)
     g, valid = host.tsdf_finalize(S, W, float(o["min_weight"]))
     return {"g": g, "valid": valid, "S": S, "W": W, "lo": lo, "step": step, "n_views": len(views), "trunc": trunc}
+
+
+SPARSE_MAX_RES = 8192  # (the virtual grid of the sparse exports)
+
+
+def fuse_tsdf_sparse(runner, dataset, scene, o, brick=8):
+    """fuse_tsdf followed by the masked mesher at level 0, bit for bit, without the dense sums: every selected view is rendered exactly as
+    fuse_tsdf renders it and its depth and conf maps are KEPT on the device as [V, h, w] (8 B per depth pixel and view: the mark needs
+    every view before any brick is integrated); host.tsdf_mesh_sparse then marks the bricks of brick^3 cells whose row holds a corner some
+    view sees at most trunc behind its surface, and takes the flagged bricks in ascending order in batches of
+    max(1, runner.density_slab_points // (brick + 1)^3): zeroed S / W rows -> f2n_tsdf_integrate_bricks over all views -> f2n_tsdf_finalize
+    -> one masked mesh batch; only one batch of rows is alive at a time.  The mark costs what a dense integration costs (grid points x
+    views): memory is saved, not arithmetic.  Returns dict(verts, faces, lo, step, n_views, trunc, stats) with stats = {bricks,
+    active_bricks, meshed_bricks, points_evaluated, points_known, batches, grid}.  No side effect on training, as fuse_tsdf."""
+    import torch
+    from . import runtime
+    host = runtime.host()
+    runner.flush()
+    B = int(brick)
+    lo = [float(v) for v in o["bbox_min"]]
+    step, nx, ny, nz = host.grid_spec(lo, [float(v) for v in o["bbox_max"]], int(o["resolution"]), SPARSE_MAX_RES)
+    views = [int(v) for v in scene["train_set"]]
+    if o["max_views"] > 0:
+        views = views[:o["max_views"]]
+    s = int(o["res_level"])
+    trunc = float(np.float32(o["trunc_voxels"]) * np.float32(step))
+    maps = [_tsdf_view_maps(runner, dataset, scene, o, idx) for idx in views]
+    h, w = int(dataset.height) // s, int(dataset.width) // s
+    depth = torch.stack([m[0] for m in maps]).contiguous() if maps else torch.zeros((0, h, w), device="cuda")
+    conf = torch.stack([m[1] for m in maps]).contiguous() if maps else torch.zeros((0, h, w), device="cuda")
+    del maps
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()  # noqa: E731
+    per = max(1, int(runner.density_slab_points) // (B + 1) ** 3)
+    verts, faces, stats = host.tsdf_mesh_sparse(lo, step, [nx, ny, nz], B, dev(np.asarray(scene["poses"], np.float32)[views]),
+                                                dev(tsdf_intrinsics(np.asarray(scene["intri"])[views], s)),
+                                                dev(np.asarray(scene["dist_params"], np.float32)[views]), depth, conf, trunc,
+                                                float(o["min_weight"]), per)
+    return {"verts": verts, "faces": faces, "lo": lo, "step": step, "n_views": len(views), "trunc": trunc, "stats": dict(stats)}
 
 
 def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
@@ -436,27 +497,37 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
         raise ValueError("mesh.source=tsdf renders the training cameras: it needs the data set")
     import torch
     from . import runtime
-    host = runtime.host()
     o = options(cfg)
     o.update(tsdf_options(cfg))
     dist = distance_options(cfg)
-    t = fuse_tsdf(runner, dataset, scene, o)
-    verts, faces = host.mesh_from_grid_masked(t["g"], t["valid"], t["lo"], t["step"], 0.0)
+    tex_on = texture_options(cfg)["texture"]
+    sp = o.get("sparse", 0)
+    if sp and o["normal_source"] == "grid" and (o["normals"] or o["colors"] or tex_on):
+        raise ValueError("tsdf.sparse builds no dense TSDF: mesh.normals, mesh.colors and mesh.texture need mesh.normal_source=field")
+    host = runtime.host()
+    if sp:
+        t = fuse_tsdf_sparse(runner, dataset, scene, o, sp)
+        verts, faces = t["verts"], t["faces"]
+    else:
+        t = fuse_tsdf(runner, dataset, scene, o)
+        verts, faces = host.mesh_from_grid_masked(t["g"], t["valid"], t["lo"], t["step"], 0.0)
     if o["min_component_faces"] > 1:
         verts, faces, _ = host.mesh_filter_components(verts, faces, o["min_component_faces"])
     k, faces_in = o["simplify"], len(faces)
     full_verts, full_faces = verts, faces  # (mesh.distance compares with the mesh before the simplification)
     if k >= 2:  # (cell = k * step as ONE float32 product: what extract_mesh_attrs uses)
         verts, faces, _ = host.mesh_simplify(verts, faces, float(np.float32(k) * np.float32(t["step"])), t["lo"])
-    tex_on = texture_options(cfg)["texture"]
 
     def attributes(verts):
         normals = colors = nrm = None
-        if (o["normals"] or o["colors"] or tex_on) and len(verts) > 0:
+        if (o["normals"] or o["colors"] or tex_on) and len(verts) > 0 and sp:
+            nrm = runner.field_normals(verts).contiguous()  # ((0, 0, 0) where the field's gradient vanishes: there is no grid to fall back on)
+        elif (o["normals"] or o["colors"] or tex_on) and len(verts) > 0:
             nrm = host.grid_normals(t["g"], verts, t["lo"], t["step"])  # (g is positive inside, as a density is: the same sign)
             if o["normal_source"] == "field":  # the field's own gradient at the vertex; the grid's where that vanishes
                 fn = runner.field_normals(verts)
                 nrm = torch.where((fn == 0).all(1, keepdim=True), nrm, fn).contiguous()
+        if nrm is not None:
             if o["normals"]:
                 normals = nrm.cpu().numpy()
             if o["colors"]:  # the radiance AT the vertex seen along the inward normal, as in the density export
@@ -472,8 +543,12 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
     path = os.path.join(exp_dir, "meshes", "%d_%d_tsdf%s.ply" % (runner.iter_step, o["resolution"], "_s%d" % k if k >= 2 else ""))
     v = to_world(verts.cpu().numpy(), scene["center"], scene["radius"])
     write_ply(path, v, faces.cpu().numpy(), normals, colors)
-    print("Mesh: %d vertices, %d faces%s from the TSDF of %d views (%d of %d grid points known, truncation %g) -> %s" % (
-        len(v), len(faces), _simplified(k, faces_in), t["n_views"], int(t["valid"].sum()), t["valid"].numel(), t["trunc"], path))
+    if sp:
+        print("Mesh: %d vertices, %d faces%s from the TSDF of %d views (sparse: %d of %d bricks of %d^3 cells active, truncation %g) -> %s" % (
+            len(v), len(faces), _simplified(k, faces_in), t["n_views"], t["stats"]["active_bricks"], t["stats"]["bricks"], sp, t["trunc"], path))
+    else:
+        print("Mesh: %d vertices, %d faces%s from the TSDF of %d views (%d of %d grid points known, truncation %g) -> %s" % (
+            len(v), len(faces), _simplified(k, faces_in), t["n_views"], int(t["valid"].sum()), t["valid"].numel(), t["trunc"], path))
     if o["refine"] is not None:  # the smoothing alone: the TSDF surface is no level set of the density
         rf = o["refine"]
         max_move = float(np.float32(rf["max_move_steps"]) * np.float32(t["step"]) * np.float32(k if k >= 2 else 1))
@@ -998,7 +1073,7 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
     dist = distance_options(cfg)
     sp = o["sparse"]
     if sp and o["source"] == "tsdf":
-        raise ValueError("mesh.sparse with mesh.source=tsdf: the TSDF fusion keeps its dense sums (a sparse TSDF is not implemented)")
+        raise ValueError("mesh.sparse with mesh.source=tsdf: mesh.sparse culls by the octree; the sparse TSDF fusion is tsdf.sparse")
     if sp and o["normal_source"] == "grid" and (o["normals"] or o["colors"] or texture_options(cfg)["texture"]):
         raise ValueError("mesh.sparse builds no dense grid: mesh.normals, mesh.colors and mesh.texture need mesh.normal_source=field")
     if o["source"] == "tsdf":

@@ -1150,6 +1150,57 @@ int f2n_brick_mesh_emit(void* stream, int nx, int ny, int nz, int B, int n_brick
                         float* verts /*[nv,3]*/, int64_t* face_keys /*[nf]*/, int64_t* face_vert_keys /*[nf,3]*/);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Sparse TSDF fusion on bricks (additive; the ABI version is unchanged): the mesh of f2n_tsdf_integrate -> f2n_tsdf_finalize ->
+ * f2n_mesh_count_masked -> f2n_mesh_emit, bit for bit, from the bricks that saw a surface -- S, W, g and valid exist for one batch of
+ * brick rows at a time.  No reference counterpart.  csrc/dataset.hip (mark, integrate), csrc/octree.hip (masked brick mesher);
+ * tests/tsdf_sparse_ref.py restates the definitions in numpy.
+ * The VIRTUAL GRID, the BRICKS (B in {4, 8, 16}, nb, linear ids, rows of (B + 1)^3 corners local x fastest, corners that DO NOT EXIST,
+ * ownership) and the KEYS are those of "Sparse mesh extraction on bricks" above; views, depth, conf, trunc and the twelve steps are
+ * those of f2n_tsdf_integrate.
+ * A (grid point, view) pair is a HIT when the view passes steps 1-9 for the point, !(sdf < -trunc) (step 10) and sdf < 0: the point is
+ * seen, and lies at most trunc behind that view's surface.  g > 0 at a valid point needs S < 0, which needs a hit; so every cell of the
+ * masked mesh with a face, and every crossing edge with a vertex, has a corner with a hit, and its owner brick holds that corner in its
+ * row: the bricks flagged by f2n_tsdf_brick_mark hold the owner of every face and every vertex of the dense TSDF mesh (level 0).
+ * ------------------------------------------------------------------------------------------------- */
+/* flags [nb_z nb_y nb_x] uint8: flags[b] = 1 iff some EXISTING corner of brick b's row has a hit in some view, else 0 -- exactly, not
+ * a superset: steps 1-10 with the roundings, comparisons and NaN behaviour of f2n_tsdf_integrate (the same device function), then
+ * sdf < 0 (false for NaN).  One workgroup per brick, views in groups in the outer loop with a block-wide vote after each group; no
+ * atomics, a flag is written once.  The work is that of a dense integration, O(grid points x views): the pass saves memory, not
+ * arithmetic.  n_views == 0: F2N_OK, nothing is touched.  F2N_ERR_INVALID_ARG: B outside {4, 8, 16}, n[k] outside
+ * [2, F2N_BRICK_MAX_POINTS], a negative size, h or w outside [1, 2^24], trunc not positive and finite, a NULL pointer other than conf;
+ * F2N_ERR_UNSUPPORTED: 2^31 bricks or more. */
+int f2n_tsdf_brick_mark(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int B, int n_views,
+                        const float* poses /*[V,3,4]*/, const float* intri /*[V,3,3]*/, const float* dist_params /*[V,4]*/,
+                        const float* depth /*[V,h,w]*/, const float* conf /*[V,h,w] or NULL*/, int h, int w, float trunc,
+                        uint8_t* flags /*[nb_z*nb_y*nb_x]*/);
+/* f2n_tsdf_integrate for the corners of the n_bricks listed bricks: S, W [n_bricks, (B + 1)^3] rows (n_bricks (B + 1)^3 <= 2^31 - 1),
+ * row j (B + 1)^3 + l = local corner l of brick brick_ids[j], updated IN PLACE by the twelve steps, views in index order, one thread
+ * per row entry, no atomics: the entry of an existing corner gets the bits the dense entry point gives that grid point from the same
+ * state, and the views [0, k) then [k, V) give the bits of one call.  A corner that does not exist, and every corner of a brick id
+ * outside the grid, is left untouched.  n_views == 0 or n_bricks == 0: F2N_OK, nothing is touched.  Error codes as
+ * f2n_tsdf_brick_mark.  f2n_tsdf_finalize is flat over n and serves the rows unchanged. */
+int f2n_tsdf_integrate_bricks(void* stream, const float* lo /*host [3]*/, float step, int nx, int ny, int nz, int B, int n_bricks,
+                              const int32_t* brick_ids /*[n_bricks]*/, int n_views, const float* poses /*[V,3,4]*/,
+                              const float* intri /*[V,3,3]*/, const float* dist_params /*[V,4]*/, const float* depth /*[V,h,w]*/,
+                              const float* conf /*[V,h,w] or NULL*/, int h, int w, float trunc, float* S /*[n_bricks,(B+1)^3]*/,
+                              float* W /*[n_bricks,(B+1)^3]*/);
+/* f2n_brick_mesh_count / f2n_brick_mesh_emit with valid [n_bricks, (B + 1)^3] uint8 rows (non-zero = the corner carries a value; the
+ * entry of a corner that does not exist is never read); the same device functions.  A cell has faces only if its eight corners are
+ * valid.  A corner's owned edge yields a vertex iff it crosses the level AND both endpoints are valid -- a SUPERSET of
+ * f2n_mesh_count_masked's rule, which also asks for an observed cell around the edge (cells on the low side, which a row does not
+ * hold): every vertex a face names is emitted, and a caller that drops the vertices no face names after the key sort is left with
+ * f2n_mesh_count_masked's set.  With valid all non-zero every output equals the unmasked entry point's bit for bit.  Error codes as the
+ * unmasked entry points, plus F2N_ERR_INVALID_ARG for valid == NULL. */
+int f2n_brick_mesh_count_masked(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids /*[n_bricks]*/,
+                                const float* values /*[n_bricks,(B+1)^3]*/, const uint8_t* valid /*[n_bricks,(B+1)^3]*/, float level,
+                                int32_t* vert_counts /*[n_bricks]*/, int32_t* face_counts /*[n_bricks]*/);
+int f2n_brick_mesh_emit_masked(void* stream, int nx, int ny, int nz, int B, int n_bricks, const int32_t* brick_ids /*[n_bricks]*/,
+                               const float* values /*[n_bricks,(B+1)^3]*/, const uint8_t* valid /*[n_bricks,(B+1)^3]*/, float level,
+                               const float* lo /*host [3]*/, float step, const int64_t* vert_start /*[n_bricks]*/,
+                               const int64_t* face_start /*[n_bricks]*/, int64_t* vert_keys /*[nv]*/, float* verts /*[nv,3]*/,
+                               int64_t* face_keys /*[nf]*/, int64_t* face_vert_keys /*[nf,3]*/);
+
+/* ---------------------------------------------------------------------------------------------------
  * Mesh simplification by vertex clustering with quadric-error placement (additive; the ABI version is unchanged).  Lindstrom 2000
  * with Garland-Heckbert plane quadrics.  No reference counterpart.  csrc/octree.hip.
  * ------------------------------------------------------------------------------------------------- */
