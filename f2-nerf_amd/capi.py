@@ -1450,6 +1450,40 @@ def tsdf_finalize(S, W, min_weight):
     return g, valid
 
 
+# ---------------------------------------------------------------- view-colour fusion
+def view_colors_accumulate(acc, wsum, count, points, normals, poses, intri, dist_params, depth, conf, image, tol, cos_min):
+    """Adds what the views (poses [V,3,4] / intri [V,3,3] / dist_params [V,4], depth [V,h,w], conf [V,h,w] or None: 1, image [V,h,w,C])
+    observe of points [n,3] (outward normals [n,3] or None) to the running sums acc [n,C], wsum [n], count [n] int32, in place
+    (f2n_view_colors_accumulate)."""
+    n = int(points.shape[0])
+    if acc.dim() != 2 or int(acc.shape[0]) != n or tuple(points.shape) != (n, 3) or wsum.numel() != n or count.numel() != n or (
+            normals is not None and normals.shape != points.shape):
+        raise F2nError("points [n,3], normals [n,3] or None, acc [n,C], wsum [n] and count [n] must match")
+    C = int(acc.shape[1])
+    V, h, w = (int(v) for v in depth.shape)
+    if (poses.numel() != 12 * V or intri.numel() != 9 * V or dist_params.numel() != 4 * V or (conf is not None and conf.shape != depth.shape) or
+            tuple(image.shape) != (V, h, w, C)):
+        raise F2nError("poses [V,3,4], intri [V,3,3], dist_params [V,4], conf and image [V,h,w,C] must match depth [V,h,w]")
+    none = V == 0 or n == 0
+    _ck(lib().f2n_view_colors_accumulate(_stream(), ctypes.c_int64(n), _p(points, "f32", none), _p(normals, "f32", True), _i(V),
+                                         _p(poses, "f32", none), _p(intri, "f32", none), _p(dist_params, "f32", none), _p(depth, "f32", none),
+                                         _p(conf, "f32", True), _p(image, "f32", none), _i(C), _i(h), _i(w), _f(tol), _f(cos_min),
+                                         _p(acc, "f32", none), _p(wsum, "f32", none), _p(count, "i32", none)), "f2n_view_colors_accumulate")
+
+
+def view_colors_finalize(acc, wsum, count, min_views):
+    """(rgb [n,C], known [n] uint8) of the running sums: known = (count >= min_views and wsum > 0), rgb = acc / wsum, 0 where not known."""
+    n = int(acc.shape[0])
+    if acc.dim() != 2 or wsum.numel() != n or count.numel() != n:
+        raise F2nError("acc [n,C], wsum [n] and count [n] must match")
+    rgb = torch.empty_like(acc)
+    known = torch.empty((n,), dtype=torch.uint8, device=acc.device)
+    _ck(lib().f2n_view_colors_finalize(_stream(), ctypes.c_int64(n), _i(int(acc.shape[1])), _p(acc, "f32", n == 0), _p(wsum, "f32", n == 0),
+                                       _p(count, "i32", n == 0), _i(int(min_views)), _p(rgb, "f32", n == 0), _p(known, "u8", n == 0)),
+        "f2n_view_colors_finalize")
+    return rgb, known
+
+
 def mesh_from_grid_masked(grid, valid, lo=(0.0, 0.0, 0.0), step=1.0, level=0.0):
     """mesh_from_grid over the grid points that carry a value (valid [nz, ny, nx] uint8; f2n_mesh_count_masked -> f2n_mesh_emit): faces
     only from cells whose eight corners are valid, vertices only where a face uses them."""

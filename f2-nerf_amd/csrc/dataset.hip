@@ -142,14 +142,15 @@ __global__ void draw_ray_batch_kernel(int n_rays, const float* __restrict__ u01,
 // registers: no atomics, the state is read once and written once, and the sums of a launch over [0, V) are those of launches over
 // [0, k) and [k, V).  A view's 20 constants (pose, fx, fy, cx, cy, distortion) are addressed by the loop variable alone: wave-uniform,
 // fetched by scalar loads into SGPRs, so that the vector registers hold the voxel's own state only.
-// Steps 1-10 of f2n_tsdf_integrate for the point p and the view v: false where the view is skipped, else sdf and wgt of steps 9-10.
-// v is the callers' loop variable: the view's constants stay wave-uniform.
-__device__ __forceinline__ bool tsdf_observe(const float p[3], int v, const float* __restrict__ poses, const float* __restrict__ intri,
-                                             const float* __restrict__ dist, const float* __restrict__ depth,
-                                             const float* __restrict__ conf, int h, int w, float trunc, float& sdf, float& wgt) {
+// Steps 1-6 of f2n_tsdf_integrate for the point p and the view v: false behind the camera, else q = p - o_v and the point's map
+// coordinates (x, y).  v is the callers' loop variable: the view's constants stay wave-uniform.
+__device__ __forceinline__ bool tsdf_project(const float p[3], int v, const float* __restrict__ poses, const float* __restrict__ intri,
+                                             const float* __restrict__ dist, float q[3], float& x, float& y) {
   const float* P = poses + 12 * (size_t) v;
   const float* K = intri + 9 * (size_t) v;
-  const float q[3] = {F2N_SUB_RN(p[0], P[3]), F2N_SUB_RN(p[1], P[7]), F2N_SUB_RN(p[2], P[11])};
+  q[0] = F2N_SUB_RN(p[0], P[3]);
+  q[1] = F2N_SUB_RN(p[1], P[7]);
+  q[2] = F2N_SUB_RN(p[2], P[11]);
   float c[3];  // R^T q: the point in the camera frame (x right, y up, z backwards: OpenGL style)
 #pragma unroll
   for (int a = 0; a < 3; a++) c[a] = f2n_sum3(F2N_MUL_RN(P[a], q[0]), F2N_MUL_RN(P[4 + a], q[1]), F2N_MUL_RN(P[8 + a], q[2]));
@@ -158,8 +159,17 @@ __device__ __forceinline__ bool tsdf_observe(const float p[3], int v, const floa
   const float un = F2N_DIV_RN(c[0], s), vn = F2N_DIV_RN(-c[1], s);
   float du, dv;
   f2n_distort(dist + 4 * (size_t) v, un, vn, du, dv);
-  const float x = F2N_ADD_RN(F2N_MUL_RN(K[0], F2N_ADD_RN(un, du)), K[2]);
-  const float y = F2N_ADD_RN(F2N_MUL_RN(K[4], F2N_ADD_RN(vn, dv)), K[5]);
+  x = F2N_ADD_RN(F2N_MUL_RN(K[0], F2N_ADD_RN(un, du)), K[2]);
+  y = F2N_ADD_RN(F2N_MUL_RN(K[4], F2N_ADD_RN(vn, dv)), K[5]);
+  return true;
+}
+
+// Steps 1-10 of f2n_tsdf_integrate for the point p and the view v: false where the view is skipped, else sdf and wgt of steps 9-10.
+__device__ __forceinline__ bool tsdf_observe(const float p[3], int v, const float* __restrict__ poses, const float* __restrict__ intri,
+                                             const float* __restrict__ dist, const float* __restrict__ depth,
+                                             const float* __restrict__ conf, int h, int w, float trunc, float& sdf, float& wgt) {
+  float q[3], x, y;
+  if (!tsdf_project(p, v, poses, intri, dist, q, x, y)) return false;
   const float fb = floorf(x), fa = floorf(y);
   if (!(fa >= 0.f && fa < (float) h && fb >= 0.f && fb < (float) w)) return false;  // outside the image (NaN as well)
   const size_t px = ((size_t) v * h + (int) fa) * w + (int) fb;
@@ -287,6 +297,92 @@ __global__ void __launch_bounds__(256) tsdf_brick_mark_kernel(TsdfBrickGrid g, u
     }
     if (threadIdx.x == 0) flags[b] = any != 0 ? 1 : 0;
   }
+}
+
+// ---- view-colour fusion (include/f2n_abi.h, "View-colour fusion") -------------------------------------------------------------------
+// The TSDF kernel's projection turned round: a surface point is taken into every view (tsdf_project), tested for occlusion against
+// that view's depth at the four pixels around it, and takes the bilinear blend of the image at the pixels that see it.  One thread
+// owns one point and walks the views in index order with its C + 2 running sums in registers (C is a template parameter: no private
+// array is indexed dynamically); a view's 20 constants are addressed by the loop variable alone, wave-uniform scalar loads as in
+// tsdf_observe.  The rejections that need no map (behind the camera, facing away, no tap in the image) come first; image is read
+// for valid taps only.  No atomics: the state is read once and written once.
+template <int C>
+__global__ void __launch_bounds__(256) view_colors_kernel(int64_t n, const float* __restrict__ points, const float* __restrict__ normals,
+                                                         int n_views, const float* __restrict__ poses, const float* __restrict__ intri,
+                                                         const float* __restrict__ dist, const float* __restrict__ depth,
+                                                         const float* __restrict__ conf, const float* __restrict__ image, int h, int w,
+                                                         float tol, float cos_min, float* __restrict__ acc, float* __restrict__ wsum,
+                                                         int32_t* __restrict__ count) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float p[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
+  float nr[3] = {0.f, 0.f, 0.f};
+  bool has_normal = false;
+  if (normals != nullptr) {
+    nr[0] = normals[3 * i]; nr[1] = normals[3 * i + 1]; nr[2] = normals[3 * i + 2];
+    const float inf = __builtin_huge_valf();
+    has_normal = fabsf(nr[0]) < inf && fabsf(nr[1]) < inf && fabsf(nr[2]) < inf && (nr[0] != 0.f || nr[1] != 0.f || nr[2] != 0.f);
+  }
+  float a_sum[C];
+#pragma unroll
+  for (int c = 0; c < C; c++) a_sum[c] = acc[C * i + c];
+  float w_sum = wsum[i];
+  int cnt = count[i];
+  const float fh = (float) h, fw = (float) w;
+  for (int v = 0; v < n_views; v++) {
+    float q[3], x, y;
+    if (!tsdf_project(p, v, poses, intri, dist, q, x, y)) continue;
+    const float r = f2n_norm3(q[0], q[1], q[2]);
+    float facing = 1.f;
+    if (has_normal) {
+      facing = F2N_DIV_RN(f2n_sum3(F2N_MUL_RN(nr[0], -q[0]), F2N_MUL_RN(nr[1], -q[1]), F2N_MUL_RN(nr[2], -q[2])), r);
+      if (!(facing > cos_min)) continue;  // seen from behind or at a grazing angle (NaN as well)
+    }
+    const float xs = F2N_SUB_RN(x, .5f), ys = F2N_SUB_RN(y, .5f);
+    const float b0 = floorf(xs), a0 = floorf(ys);
+    if (!(a0 >= -1.f && a0 < fh && b0 >= -1.f && b0 < fw)) continue;  // no tap exists (NaN as well)
+    const float fx = F2N_SUB_RN(xs, b0), fy = F2N_SUB_RN(ys, a0);
+    const float wy[2] = {F2N_SUB_RN(1.f, fy), fy}, wx[2] = {F2N_SUB_RN(1.f, fx), fx};
+    float om = 0.f, col[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) col[c] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const float ta = F2N_ADD_RN(a0, (float) (k >> 1)), tb = F2N_ADD_RN(b0, (float) (k & 1));
+      if (!(ta >= 0.f && ta < fh && tb >= 0.f && tb < fw)) continue;  // beyond the border: no observation
+      const size_t px = ((size_t) v * h + (int) ta) * w + (int) tb;
+      const float D = depth[px];
+      if (!(D > 0.f)) continue;
+      const float cf = conf != nullptr ? conf[px] : 1.f;
+      if (!(cf > 0.f)) continue;
+      const float d = F2N_SUB_RN(D, r);
+      if (d < -tol || d > tol) continue;  // occluded in this view, or in front of what it sees
+      const float ok = F2N_MUL_RN(F2N_MUL_RN(wy[k >> 1], wx[k & 1]), cf);
+      om = F2N_ADD_RN(om, ok);
+#pragma unroll
+      for (int c = 0; c < C; c++) col[c] = F2N_ADD_RN(col[c], F2N_MUL_RN(ok, image[C * px + c]));
+    }
+    if (!(om > 0.f)) continue;
+#pragma unroll
+    for (int c = 0; c < C; c++) a_sum[c] = F2N_ADD_RN(a_sum[c], F2N_MUL_RN(facing, col[c]));
+    w_sum = F2N_ADD_RN(w_sum, F2N_MUL_RN(facing, om));
+    cnt += 1;
+  }
+#pragma unroll
+  for (int c = 0; c < C; c++) acc[C * i + c] = a_sum[c];
+  wsum[i] = w_sum;
+  count[i] = cnt;
+}
+
+__global__ void __launch_bounds__(256) view_colors_finalize_kernel(int64_t n, int C, const float* __restrict__ acc,
+                                                                  const float* __restrict__ wsum, const int32_t* __restrict__ count,
+                                                                  int min_views, float* __restrict__ rgb, uint8_t* __restrict__ known) {
+  const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float ws = wsum[i];
+  const bool ok = count[i] >= min_views && ws > 0.f;
+  for (int c = 0; c < C; c++) rgb[C * i + c] = ok ? F2N_DIV_RN(acc[C * i + c], ws) : 0.f;
+  known[i] = ok ? 1 : 0;
 }
 
 // SSIM of two images (include/f2n_abi.h, f2n_image_ssim; scripts/eval.py:29-75, the mip-NeRF definition): fp64 throughout, one rounding per
@@ -483,6 +579,37 @@ int f2n_tsdf_integrate_bricks(void* stream, const float* lo /*host [3]*/, float 
     return F2N_ERR_INVALID_ARG;
   hipLaunchKernelGGL(tsdf_integrate_bricks_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, g, n_total, n, brick_ids,
                      n_views, poses, intri, dist_params, depth, conf, h, w, trunc, S, W);
+  return f2n_launch_status();
+}
+
+int f2n_view_colors_accumulate(void* stream, int64_t n, const float* points, const float* normals, int n_views, const float* poses,
+                               const float* intri, const float* dist_params, const float* depth, const float* conf, const float* image, int C,
+                               int h, int w, float tol, float cos_min, float* acc, float* wsum, int32_t* count) {
+  if (n < 0 || n_views < 0 || h < 0 || w < 0 || C < 1 || C > 4 || !(tol > 0.f) || !(tol < __builtin_huge_valf()) || cos_min != cos_min)
+    return F2N_ERR_INVALID_ARG;
+  if (n_views == 0 || n == 0) return F2N_OK;
+  if (h < 1 || w < 1 || h > (1 << 24) || w > (1 << 24) || n > (int64_t) 0x7fffffff * 256) return F2N_ERR_INVALID_ARG;
+  if (points == nullptr || poses == nullptr || intri == nullptr || dist_params == nullptr || depth == nullptr || image == nullptr ||
+      acc == nullptr || wsum == nullptr || count == nullptr)
+    return F2N_ERR_INVALID_ARG;
+#define F2N_VIEW_COLORS(CC)                                                                                                            \
+  hipLaunchKernelGGL(view_colors_kernel<CC>, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, points, normals, n_views, \
+                     poses, intri, dist_params, depth, conf, image, h, w, tol, cos_min, acc, wsum, count)
+  if (C == 1) F2N_VIEW_COLORS(1);
+  else if (C == 2) F2N_VIEW_COLORS(2);
+  else if (C == 3) F2N_VIEW_COLORS(3);
+  else F2N_VIEW_COLORS(4);
+#undef F2N_VIEW_COLORS
+  return f2n_launch_status();
+}
+
+int f2n_view_colors_finalize(void* stream, int64_t n, int C, const float* acc, const float* wsum, const int32_t* count, int min_views,
+                             float* rgb, uint8_t* known) {
+  if (n < 0 || C < 1 || C > 4 || n > (int64_t) 0x7fffffff * 256) return F2N_ERR_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  if (acc == nullptr || wsum == nullptr || count == nullptr || rgb == nullptr || known == nullptr) return F2N_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(view_colors_finalize_kernel, dim3(f2n_div_up(n, 256)), dim3(256), 0, (hipStream_t) stream, n, C, acc, wsum, count,
+                     min_views, rgb, known);
   return f2n_launch_status();
 }
 

@@ -120,6 +120,13 @@ void TsdfIntegrateBricks(const Tensor& S, const Tensor& W, const Tensor& brick_i
                          const Tensor& poses, const Tensor& intri, const Tensor& dist, const Tensor& depth, const Tensor& conf, float trunc);
 std::tuple<Tensor, Tensor> MeshFromBricksMasked(const Tensor& values, const Tensor& valid, const Tensor& brick_ids, const int n[3],
                                                 const float lo[3], float step, float level, int B, int64_t batch_bricks = 0);
+// View-colour fusion (f2n_view_colors_accumulate / f2n_view_colors_finalize); the views as TsdfIntegrate takes them, image [V,h,w,C] on
+// the pixel grid of depth.  ViewColorsAccumulate adds the views' observations of points [n,3] (normals [n,3] or undefined) to the device
+// tensors acc [n,C], wsum [n], count [n] int32 IN PLACE; ViewColorsFinalize: (rgb [n,C], known [n] uint8).
+void ViewColorsAccumulate(const Tensor& acc, const Tensor& wsum, const Tensor& count, const Tensor& points, const Tensor& normals,
+                          const Tensor& poses, const Tensor& intri, const Tensor& dist, const Tensor& depth, const Tensor& conf,
+                          const Tensor& image, float tol, float cos_min);
+std::tuple<Tensor, Tensor> ViewColorsFinalize(const Tensor& acc, const Tensor& wsum, const Tensor& count, int min_views);
 // mark -> the flagged bricks in ascending order in batches of batch_bricks -> zeroed rows, TsdfIntegrateBricks over all views,
 // TsdfFinalize, one masked mesh batch -> assemble: the mesh of TsdfIntegrate -> TsdfFinalize -> MeshFromGridMasked at level 0, bit for
 // bit, with one batch of rows alive at a time

@@ -735,6 +735,48 @@ std::tuple<Tensor, Tensor> TsdfMeshSparse(const float lo[3], float step, const i
   return BrickMeshAssemble(parts, true);
 }
 
+// ---- view-colour fusion (include/f2n_abi.h, "View-colour fusion") -------------------------------------------------------------
+void ViewColorsAccumulate(const Tensor& acc, const Tensor& wsum, const Tensor& count, const Tensor& points, const Tensor& normals,
+                          const Tensor& poses, const Tensor& intri, const Tensor& dist, const Tensor& depth, const Tensor& conf,
+                          const Tensor& image, float tol, float cos_min) {
+  torch::NoGradGuard g;
+  // (the sums are updated in place: no copy may stand in for them)
+  DevArg(acc, torch::kFloat32, "acc");
+  DevArg(wsum, torch::kFloat32, "wsum");
+  DevArg(count, torch::kInt32, "count");
+  Tensor p = Points3(points);
+  const int64_t n = p.size(0);
+  TORCH_CHECK(acc.dim() == 2 && acc.size(0) == n && acc.size(1) >= 1 && acc.size(1) <= 4 && wsum.numel() == n && count.numel() == n,
+              "acc must be [n, C] with C in [1, 4], wsum and count [n] for points [n, 3]");
+  const int C = (int) acc.size(1);
+  Tensor nr;
+  if (normals.defined()) {
+    nr = Points3(normals);
+    TORCH_CHECK(nr.size(0) == n, "normals must have the shape of points");
+  }
+  const TsdfViews v = CheckedViews(poses, intri, dist, depth, conf);
+  Tensor im = image.to(torch::kCUDA, torch::kFloat32).contiguous();
+  TORCH_CHECK(im.dim() == 4 && im.size(0) == v.V && im.size(1) == v.h && im.size(2) == v.w && im.size(3) == C,
+              "image must be [V, h, w, C] on the pixel grid of depth");
+  F2N_CALL(f2n_view_colors_accumulate(CurStream(), n, F32P(p), nr.defined() ? F32P(nr) : nullptr, v.V, F32P(v.po), F32P(v.in), F32P(v.di),
+                                      F32P(v.de), v.co.defined() ? F32P(v.co) : nullptr, F32P(im), C, v.h, v.w, tol, cos_min, F32P(acc),
+                                      F32P(wsum), I32P(count)));
+}
+
+std::tuple<Tensor, Tensor> ViewColorsFinalize(const Tensor& acc, const Tensor& wsum, const Tensor& count, int min_views) {
+  torch::NoGradGuard g;
+  DevArg(acc, torch::kFloat32, "acc");
+  DevArg(wsum, torch::kFloat32, "wsum");
+  DevArg(count, torch::kInt32, "count");
+  TORCH_CHECK(acc.dim() == 2 && acc.size(1) >= 1 && acc.size(1) <= 4 && wsum.numel() == acc.size(0) && count.numel() == acc.size(0),
+              "acc must be [n, C] with C in [1, 4], wsum and count [n]");
+  const int64_t n = acc.size(0);
+  Tensor rgb = torch::empty_like(acc), known = torch::empty({n}, torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA));
+  F2N_CALL(f2n_view_colors_finalize(CurStream(), n, (int) acc.size(1), F32P(acc), F32P(wsum), I32P(count), min_views, F32P(rgb),
+                                    known.data_ptr<uint8_t>()));
+  return {rgb, known};
+}
+
 std::tuple<Tensor, Tensor> Renderer::ExtractMesh(const std::vector<float>& lo, const std::vector<float>& hi, int res, float level) {
   const GridSpec s = MakeGridSpec(lo, hi, res);
   Tensor grid = DensityGrid(lo, hi, res);

@@ -174,6 +174,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
         },
         py::arg("S"), py::arg("W"), py::arg("min_weight"));
+  // view-colour fusion: the views' observations (depth, conf or None, image [V,h,w,C]) of points [n,3] (normals [n,3] or None) added to
+  // the running sums acc [n,C], wsum [n], count [n] int32, in place (f2n_view_colors_accumulate); then (rgb, known) of the sums
+  // (f2n_view_colors_finalize)
+  m.def("view_colors_accumulate",
+        [](const Tensor& acc, const Tensor& wsum, const Tensor& count, const Tensor& points, const c10::optional<Tensor>& normals,
+           const Tensor& poses, const Tensor& intri, const Tensor& dist, const Tensor& depth, const c10::optional<Tensor>& conf,
+           const Tensor& image, float tol, float cos_min) {
+          ViewColorsAccumulate(acc, wsum, count, points, normals.has_value() ? *normals : Tensor(), poses, intri, dist, depth,
+                               conf.has_value() ? *conf : Tensor(), image, tol, cos_min);
+        },
+        py::arg("acc"), py::arg("wsum"), py::arg("count"), py::arg("points"), py::arg("normals"), py::arg("poses"), py::arg("intri"),
+        py::arg("dist"), py::arg("depth"), py::arg("conf"), py::arg("image"), py::arg("tol"), py::arg("cos_min"));
+  m.def("view_colors_finalize",
+        [](const Tensor& acc, const Tensor& wsum, const Tensor& count, int min_views) {
+          auto t = ViewColorsFinalize(acc, wsum, count, min_views);
+          return std::vector<Tensor>{std::get<0>(t), std::get<1>(t)};
+        },
+        py::arg("acc"), py::arg("wsum"), py::arg("count"), py::arg("min_views"));
   // sparse TSDF fusion on bricks of B^3 cells of the virtual grid (lo, step, n = (nx, ny, nz)); the views as tsdf_integrate takes them:
   // flags [nbz, nby, nbx] uint8 of the bricks whose row holds a corner seen at most trunc behind a view's surface (f2n_tsdf_brick_mark) ...
   m.def("tsdf_brick_mark",

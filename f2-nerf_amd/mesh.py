@@ -15,6 +15,12 @@ Options (hydra-style overrides, no `mesh` group in the configs):
                    (runner.query_density_grad; a vertex where that vanishes keeps its grid normal)
   mesh.colors      true: per-vertex colours (uchar red, green, blue; default false): the radiance AT the vertex seen along the
                    inward normal -- a single-point query, not a volume-rendered pixel
+  mesh.color_source  radiance | views (default radiance: nothing changes): with views the colours of mesh.colors are the colours the
+                   training views OBSERVED at the vertex, blended (fuse_view_colors, below); a vertex no view sees keeps its
+                   radiance colour, so the file is fully coloured, and one line is printed: Colors: <known> of <n> vertices from
+                   <V> views (1/<res_level>, tol <t>).  It works with either mesh.source, with mesh.sparse / tsdf.sparse,
+                   mesh.simplify and mesh.refine (the final vertices, and the refined ones for _r.ply); mesh.colors raises when it
+                   raised before
   mesh.min_component_faces  N > 1: connected components of fewer than N faces ("floaters") are dropped (default 0: none)
   mesh.simplify    k >= 2: the mesh is simplified by vertex clustering on cells of k grid steps with quadric-error placement
                    (host.mesh_simplify; default 0: off) after the floater removal and before normals and colours, which are computed
@@ -30,8 +36,10 @@ Options (hydra-style overrides, no `mesh` group in the configs):
                    with or without mesh.simplify, and computes the per-vertex normals whether or not mesh.normals writes them to the
                    .ply.  Options: texture.texels_per_step (2.0: texels per grid step of mesh.resolution; not measured on a scene),
                    texture.max_size (8192, a power of two: the density is halved until the atlas fits), texture.max_block_log2 (7),
-                   texture.source (point | ray: the radiance AT the texel's point seen along the inward normal, as mesh.colors, or
-                   the volume-rendered colour of a short ray through it), texture.ray_steps (4.0 grid steps, the TSDF truncation's
+                   texture.source (point | ray | views: the radiance AT the texel's point seen along the inward normal, as
+                   mesh.colors, the volume-rendered colour of a short ray through it, or the colours the training views observed
+                   there -- fuse_view_colors with the colors.* options; a texel no view sees takes the point colour and the
+                   Texture: line names the texels that came from views), texture.ray_steps (4.0 grid steps, the TSDF truncation's
                    default; not measured on a scene).  With mesh.check the check JSON gains texture_psnr and n_texture_rays.
                    Known limits: no mip-safe padding between blocks (nearest and bilinear filtering are clean, mipmaps bleed); charts
                    are per face, so filtering is not seam-free across edges beyond the replicated gutter; a chart's anisotropy is
@@ -99,6 +107,21 @@ and the masked mesher leaves the surface open where no camera looked (f2n_mesh_c
                      mesh.colors and mesh.texture need mesh.normal_source=field (a vertex where the field's gradient vanishes keeps
                      the normal (0, 0, 0)): anything else is a ValueError before a view is rendered.  B = 8 is inherited from
                      mesh.sparse, not measured for this path.  (mesh.sparse itself stays refused with mesh.source=tsdf.)
+
+View colours (mesh.color_source=views, texture.source=views): every surface point is projected into the training views that see it
+(f2n_view_colors_accumulate: the camera model of the TSDF, a bilinear lookup whose four taps are each tested for occlusion against the
+view's rendered depth) and the observed colours are blended, weighted by the rendered opacity times the cosine between the normal
+and the viewing direction -- a weighted mean over all views, no best-view pick: a choice, not a measurement.  Options, every default
+a choice (the thresholds are those of tsdf.* and points.*), none measured on a converged scene:
+  colors.res_level   the views are rendered at 1/res_level of the cameras' resolution (default 2)
+  colors.tol_steps   a tap sees the point when its depth is within this many grid steps of the point's distance (default 2.0)
+  colors.cos_min     views that meet the surface at a cosine at or below this are skipped (default 0.1; a point without a normal
+                     skips none)
+  colors.min_views   a point is known when at least this many views contributed (default 1)
+  colors.max_views   only the first N training cameras are used (default 0: all)
+  colors.views_per_batch  cameras rendered per launch (default 8); the result does not depend on it
+  colors.tau, colors.min_opacity  as tsdf.tau and tsdf.min_opacity (default 0.5 both)
+  colors.image       render | photo (default render): the colours the field renders from the view, or the photograph's pixels
 
 Point-cloud export: `mode=extract_points is_continue=true` renders every training camera with runner.render_geometry and writes the
 rays' surface points, oriented and coloured, to <exp>/points/<iter>.ply in the data set's world frame (the usual input of a Poisson
@@ -389,6 +412,16 @@ def tsdf_camera_rays(dataset, bounds, idx, s):
     (a s + s // 2, b s + s // 2) -- inside pixel (a, b) of an image s times smaller, whose intrinsics are fx, fy, cx, cy divided by s.
     Returns (rays_o, rays_d, bounds, h, w)."""
     import torch
+    ij, h, w = tsdf_pixels(dataset, s)
+    ro, rd = dataset.img2world_ray_flex(torch.full((h * w,), int(idx), dtype=torch.int32, device="cuda"), ij)
+    b = torch.as_tensor(np.asarray(bounds, np.float32)[idx], device="cuda").reshape(1, 2).repeat(h * w, 1).contiguous()
+    return ro, rd, b, h, w
+
+
+def tsdf_pixels(dataset, s):
+    """(ij [h w, 2] int32, h, w): the full-resolution pixels (a s + s // 2, b s + s // 2) the map entries (a, b) of tsdf_camera_rays look
+    through, row-major."""
+    import torch
     s = int(s)
     h, w = int(dataset.height) // s, int(dataset.width) // s
     if h < 1 or w < 1:
@@ -396,10 +429,7 @@ def tsdf_camera_rays(dataset, bounds, idx, s):
     ii = torch.arange(h, dtype=torch.int32, device="cuda") * s + s // 2
     jj = torch.arange(w, dtype=torch.int32, device="cuda") * s + s // 2
     gi, gj = torch.meshgrid(ii, jj, indexing="ij")
-    ij = torch.stack([gi.reshape(-1), gj.reshape(-1)], -1).contiguous()
-    ro, rd = dataset.img2world_ray_flex(torch.full((h * w,), int(idx), dtype=torch.int32, device="cuda"), ij)
-    b = torch.as_tensor(np.asarray(bounds, np.float32)[idx], device="cuda").reshape(1, 2).repeat(h * w, 1).contiguous()
-    return ro, rd, b, h, w
+    return torch.stack([gi.reshape(-1), gj.reshape(-1)], -1).contiguous(), h, w
 
 
 def tsdf_intrinsics(intri, s):
@@ -410,14 +440,127 @@ def tsdf_intrinsics(intri, s):
     return k
 
 
-def _tsdf_view_maps(runner, dataset, scene, o, idx):
+def _tsdf_view_maps(runner, dataset, scene, o, idx, with_colors=False):
     """(depth, conf) [h, w] of training camera idx as the TSDF takes them: the rays' surface distance where the ray has a surface and
-    its opacity reaches o["min_opacity"] (0 elsewhere), and the opacity."""
+    its opacity reaches o["min_opacity"] (0 elsewhere), and the opacity.  with_colors: the rays' rendered colours [h, w, 3] as a third."""
     import torch
     ro, rd, b, h, w = tsdf_camera_rays(dataset, scene["bounds"], idx, int(o["res_level"]))
     g = runner.render_geometry(ro, rd, b, tau=o["tau"])
     hit = (g["surf_idx"] >= 0) & (g["opacity"] >= o["min_opacity"])
-    return torch.where(hit, g["surf_t"], torch.zeros_like(g["surf_t"])).reshape(h, w), g["opacity"].reshape(h, w)
+    maps = torch.where(hit, g["surf_t"], torch.zeros_like(g["surf_t"])).reshape(h, w), g["opacity"].reshape(h, w)
+    return maps + (g["colors"].reshape(h, w, 3),) if with_colors else maps
+
+
+def view_intrinsics(intri, s):
+    """intri [V,3,3] in units of the maps' pixels WITH the pixel centres in place (float32): entry (a, b) of the maps of
+    tsdf_camera_rays looks through the centre (b s + s // 2 + 0.5, a s + s // 2 + 0.5) of a full-resolution pixel (the + 0.5 of
+    f2n_img2world_rays), and these intrinsics put that ray at the entry's centre (b + 0.5, a + 0.5): fx / s, fy / s,
+    cx' = (cx - s // 2 - 0.5) / s + 0.5, cy' likewise.  What a bilinear lookup needs; tsdf_intrinsics (cx / s) is right to within the
+    pixel, which is all a nearest lookup asks for."""
+    k = np.array(intri, np.float32, copy=True).reshape(-1, 3, 3)
+    s32, off = np.float32(s), np.float32(int(s) // 2) + np.float32(0.5)
+    for r in (0, 1):
+        k[:, r, r] = k[:, r, r] / s32
+        k[:, r, 2] = (k[:, r, 2] - off) / s32 + np.float32(0.5)
+    return k
+
+
+COLOR_SOURCES = ("radiance", "views")
+COLOR_IMAGES = ("render", "photo")
+
+
+def view_color_options(cfg):
+    """mesh.color_source and the colors.* options (a dict of its own: options() keeps its keys).  Every default is a choice: the
+    thresholds are those of tsdf.* and points.*, res_level 2 is one step finer than the TSDF's depth maps, tol_steps 2 half of the TSDF's
+    truncation, cos_min 0.1 drops views within 6 degrees of grazing; none of them is measured on a converged scene."""
+    m = cfg.get("mesh") or {}
+    c = cfg.get("colors") or {}
+    src = str(m.get("color_source", "radiance")).strip().lower()
+    if src not in COLOR_SOURCES:
+        raise ValueError("mesh.color_source must be one of %s, got %r" % (" | ".join(COLOR_SOURCES), m.get("color_source")))
+    img = str(c.get("image", "render")).strip().lower()
+    if img not in COLOR_IMAGES:
+        raise ValueError("colors.image must be one of %s, got %r" % (" | ".join(COLOR_IMAGES), c.get("image")))
+    o = {"color_source": src, "res_level": int(c.get("res_level", 2)), "tol_steps": float(c.get("tol_steps", 2.0)),
+         "cos_min": float(c.get("cos_min", 0.1)), "min_views": int(c.get("min_views", 1)), "max_views": int(c.get("max_views", 0)),
+         "views_per_batch": int(c.get("views_per_batch", 8)), "tau": float(c.get("tau", 0.5)), "min_opacity": float(c.get("min_opacity", 0.5)),
+         "image": img}
+    if (o["res_level"] < 1 or o["views_per_batch"] < 1 or o["max_views"] < 0 or o["min_views"] < 1 or not 0.0 < o["tau"] <= 1.0 or
+            not 0.0 < o["tol_steps"] < float("inf") or not -1.0 <= o["cos_min"] < 1.0 or not o["min_opacity"] >= 0.0):
+        raise ValueError("colors.res_level, colors.views_per_batch and colors.min_views must be >= 1, colors.max_views >= 0, colors.tau in "
+                         "(0, 1], colors.tol_steps > 0 and finite, colors.cos_min in [-1, 1), colors.min_opacity >= 0, got %r" % (o,))
+    return o
+
+
+def fuse_view_colors(runner, dataset, scene, points, normals, o):
+    """The colours the training views observed at points [n,3] (NORMALISED frame; outward normals [n,3] or None), blended
+    (f2n_view_colors_accumulate / _finalize).  o: view_color_options() plus "step", the grid step the tolerance is counted in
+    (tol = tol_steps * step as ONE float32 product).  The selected training cameras are rendered in batches of o["views_per_batch"]
+    exactly as fuse_tsdf renders them (depth and conf of _tsdf_view_maps at o["res_level"]); the image is the render's colours, or with
+    o["image"] == "photo" the photographs at the same pixels (dataset.gather_colors); the intrinsics are view_intrinsics.  The sums of
+    all points stay resident, one batch of maps is alive at a time, and the batch size does not show in the result's bits.  Returns
+    dict(colors [n,3], known [n] bool, weight [n], count [n] int32, n_views, tol), tensors on the device.  No side effect on training:
+    nothing is drawn, no vote is cast, a pending step is flushed first."""
+    import torch
+    from . import runtime
+    host = runtime.host()
+    runner.flush()
+    pts = points.to("cuda", torch.float32).reshape(-1, 3).contiguous()
+    nrm = None if normals is None else normals.to("cuda", torch.float32).reshape(-1, 3).contiguous()
+    n = int(pts.shape[0])
+    acc = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+    wsum = torch.zeros((n,), dtype=torch.float32, device="cuda")
+    count = torch.zeros((n,), dtype=torch.int32, device="cuda")
+    views = [int(v) for v in scene["train_set"]]
+    if o["max_views"] > 0:
+        views = views[:o["max_views"]]
+    s = int(o["res_level"])
+    tol = float(np.float32(o["tol_steps"]) * np.float32(o["step"]))
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()  # noqa: E731
+    ij, h, w = tsdf_pixels(dataset, s)
+    for k in range(0, len(views), o["views_per_batch"]):
+        batch = views[k:k + o["views_per_batch"]]
+        depth, conf, image = [], [], []
+        for idx in batch:
+            d, c, im = _tsdf_view_maps(runner, dataset, scene, o, idx, True)
+            if o["image"] == "photo":
+                im = dataset.gather_colors(torch.full((h * w,), idx, dtype=torch.int32, device="cuda"), ij).reshape(h, w, 3)
+            depth.append(d)
+            conf.append(c)
+            image.append(im)
+        host.view_colors_accumulate(acc, wsum, count, pts, nrm, dev(np.asarray(scene["poses"], np.float32)[batch]),
+                                    dev(view_intrinsics(np.asarray(scene["intri"])[batch], s)),
+                                    dev(np.asarray(scene["dist_params"], np.float32)[batch]), torch.stack(depth).contiguous(),
+                                    torch.stack(conf).contiguous(), torch.stack(image).contiguous(), tol, float(o["cos_min"]))
+    rgb, known = host.view_colors_finalize(acc, wsum, count, int(o["min_views"]))
+    return {"colors": rgb, "known": known != 0, "weight": wsum, "count": count, "n_views": len(views), "tol": tol}
+
+
+def _view_colors_fn(runner, cfg, scene, dataset, step, totals=None):
+    """fn(points, normals) -> (rgb, known) of fuse_view_colors with the options of cfg, as bake_texture's view_colors takes it; totals (a
+    dict, optional) receives n_views and tol of the last call."""
+    if dataset is None:
+        raise ValueError("mesh.color_source=views and texture.source=views render the training cameras: they need the data set")
+    o = view_color_options(cfg)
+    o["step"] = float(step)
+
+    def fn(points, normals):
+        r = fuse_view_colors(runner, dataset, scene, points, normals, o)
+        if totals is not None:
+            totals.update(n_views=r["n_views"], tol=r["tol"], res_level=o["res_level"])
+        return r["colors"], r["known"]
+    return fn
+
+
+def _colors_from_views(fn, totals, verts, normals, colors):
+    """mesh.color_source=views: the radiance colours [n,3] (numpy) of the vertices with the fused view colour where that is known, and the
+    Colors: line."""
+    import torch
+    rgb, known = fn(verts, normals)
+    out = torch.where(known[:, None], rgb, torch.as_tensor(np.asarray(colors, np.float32), device=rgb.device).reshape(-1, 3))
+    print("Colors: %d of %d vertices from %d views (1/%d, tol %g)" % (int(known.sum()), int(known.numel()), totals["n_views"],
+                                                                     totals["res_level"], totals["tol"]))
+    return out.cpu().numpy()
 
 
 def fuse_tsdf(runner, dataset, scene, o):
@@ -501,6 +644,7 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
     o.update(tsdf_options(cfg))
     dist = distance_options(cfg)
     tex_on = texture_options(cfg)["texture"]
+    cviews = o["colors"] and view_color_options(cfg)["color_source"] == "views"
     sp = o.get("sparse", 0)
     if sp and o["normal_source"] == "grid" and (o["normals"] or o["colors"] or tex_on):
         raise ValueError("tsdf.sparse builds no dense TSDF: mesh.normals, mesh.colors and mesh.texture need mesh.normal_source=field")
@@ -537,6 +681,9 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
         elif o["normals"] or o["colors"]:
             normals = np.zeros((0, 3), np.float32) if o["normals"] else None
             colors = np.zeros((0, 3), np.float32) if o["colors"] else None
+        if cviews and nrm is not None:  # the colours the views observed; a vertex none of them sees keeps the radiance colour
+            totals = {}
+            colors = _colors_from_views(_view_colors_fn(runner, cfg, scene, dataset, t["step"], totals), totals, verts, nrm, colors)
         return nrm, normals, colors
 
     nrm, normals, colors = attributes(verts)
@@ -568,7 +715,7 @@ def extract_tsdf(runner, cfg, scene, dataset, exp_dir):
                  "nonmanifold_edges": int(edges[1])}
         nrm, normals, colors = attributes(verts)
         path = _write_refined(path, scene, verts, faces, normals, colors, stats)
-    tex = _run_texture(runner, cfg, scene, verts, faces, nrm, t["step"], path) if tex_on else None
+    tex = _run_texture(runner, cfg, scene, verts, faces, nrm, t["step"], path, dataset) if tex_on else None
     if check_options(cfg)["check"]:
         _run_check(runner, cfg, scene, dataset, verts, faces, t["step"], path, tex)
     if dist["distance"] or dist["distance_to"] is not None:
@@ -722,7 +869,7 @@ def _run_check(runner, cfg, scene, dataset, verts, faces, step, path, tex=None):
     return out
 
 
-TEXTURE_SOURCES = ("point", "ray")
+TEXTURE_SOURCES = ("point", "ray", "views")
 
 
 def texture_options(cfg):
@@ -745,7 +892,7 @@ def texture_options(cfg):
 BAKE_CHUNK = 1 << 20  # texels per radiance query / rays per render of bake_texture
 
 
-def bake_texture(runner, verts, faces, normals, density, max_size=8192, max_log=7, source="point", ray_steps=4.0, step=None):
+def bake_texture(runner, verts, faces, normals, density, max_size=8192, max_log=7, source="point", ray_steps=4.0, step=None, view_colors=None):
     """runner.bake_texture: a texture atlas of the mesh (verts, faces, per-vertex normals [V,3] in the NORMALISED frame; density in texels
     per length unit) filled from the field.  host.mesh_atlas lays one right-triangle chart per face into an atlas of at most max_size
     (the density is halved until it fits) and host.mesh_atlas_texels (clamp on) gives every owned texel its point of the surface and
@@ -754,9 +901,13 @@ def bake_texture(runner, verts, faces, normals, density, max_size=8192, max_log=
     runner.query_radiance(point, dir)[1], the definition of mesh.colors, so a texel on a vertex carries that vertex's colour;
     source "ray": the volume-rendered colour of runner.render_geometry along the ray from point - h dir in direction dir over (0, 2 h)
     with h = ray_steps * step (step: the grid step of the mesh, required) -- it starts h outside the surface and ends h inside it.
-    ray_steps = 4 grid steps is the TSDF truncation's default, not measured on a scene.  Returns dict of uv [F,3,2], size, texture
-    [S,S,3] (0 where no face owns the texel), tex_face [S,S] int32, density_used, texels_used.  No side effect on training: a pending
-    step is flushed first, nothing is drawn, no vote is cast."""
+    ray_steps = 4 grid steps is the TSDF truncation's default, not measured on a scene.
+    source "views": view_colors(points [T,3], normals [T,3]) -> (rgb [T,3], known [T] bool) (fuse_view_colors through the launcher: the
+    colours the training views observed) is called ONCE on the owned texels' points and their blended corner normals (minus the
+    direction above); a texel that is not known takes the "point" colour.  Without view_colors it is a ValueError.
+    Returns dict of uv [F,3,2], size, texture [S,S,3] (0 where no face owns the texel), tex_face [S,S] int32, density_used, texels_used
+    and, for source "views", texels_from_views.  No side effect on training: a pending step is flushed first, nothing is drawn, no vote
+    is cast."""
     import torch
     from . import runtime
     host = runtime.host()
@@ -764,12 +915,15 @@ def bake_texture(runner, verts, faces, normals, density, max_size=8192, max_log=
         raise ValueError("bake_texture: source must be one of %s, got %r" % (" | ".join(TEXTURE_SOURCES), source))
     if source == "ray" and not (step is not None and float(step) > 0.0 and float(ray_steps) > 0.0):
         raise ValueError("bake_texture: source='ray' needs the grid step of the mesh (step > 0) and ray_steps > 0")
+    if source == "views" and view_colors is None:
+        raise ValueError("bake_texture: source='views' needs view_colors, a function (points, normals) -> (rgb, known)")
     runner.flush()
     uv, size, blocks, used = host.mesh_atlas(verts, faces, float(density), int(max_size), int(max_log))
     tex_face, bary, pos = host.mesh_atlas_texels(verts, faces, blocks, size, True)
     texture = torch.zeros((size, size, 3), dtype=torch.float32, device=pos.device)
     own = tex_face.reshape(-1) >= 0
     at = own.nonzero().reshape(-1)
+    from_views = 0
     if at.numel():
         corners = faces.reshape(-1, 3).long()[tex_face.reshape(-1)[at].long()]  # [T,3]
         w, p = bary.reshape(-1, 3)[at], pos.reshape(-1, 3)[at].contiguous()
@@ -783,14 +937,22 @@ def bake_texture(runner, verts, faces, normals, density, max_size=8192, max_log=
         cols = []
         for k in range(0, int(at.numel()), BAKE_CHUNK):
             pk, dk = p[k:k + BAKE_CHUNK].contiguous(), dirs[k:k + BAKE_CHUNK].contiguous()
-            if source == "point":
+            if source != "ray":
                 cols.append(runner.query_radiance(pk, dk)[1])
             else:
                 h = float(np.float32(ray_steps) * np.float32(step))
                 b = torch.tensor([[0.0, 2.0 * h]], dtype=torch.float32, device=p.device).repeat(len(pk), 1).contiguous()
                 cols.append(runner.render_geometry((pk - h * dk).contiguous(), dk, b)["colors"])
-        texture.reshape(-1, 3)[at] = torch.cat(cols)
-    return {"uv": uv, "size": int(size), "texture": texture, "tex_face": tex_face, "density_used": float(used), "texels_used": int(at.numel())}
+        cols = torch.cat(cols)
+        if source == "views":
+            rgb, known = view_colors(p, (-dirs).contiguous())
+            cols = torch.where(known.bool()[:, None], rgb, cols)
+            from_views = int(known.sum())
+        texture.reshape(-1, 3)[at] = cols
+    out = {"uv": uv, "size": int(size), "texture": texture, "tex_face": tex_face, "density_used": float(used), "texels_used": int(at.numel())}
+    if source == "views":
+        out["texels_from_views"] = from_views
+    return out
 
 
 def write_png(path, rgb_uint8):
@@ -845,7 +1007,7 @@ def write_obj(path, verts, faces, uv, normals=None, texture_name="texture.png"):
     return path
 
 
-def _run_texture(runner, cfg, scene, verts, faces, normals, step, path):
+def _run_texture(runner, cfg, scene, verts, faces, normals, step, path, dataset=None):
     """mesh.texture=true: runner.bake_texture of the mesh just written -> <path without .ply>_tex.obj / .mtl / .png and one printed line.
     Returns bake_texture's dict (mesh.check reads uv and texture from it)."""
     import torch
@@ -854,13 +1016,15 @@ def _run_texture(runner, cfg, scene, verts, faces, normals, step, path):
     density = float(np.float32(t["texels_per_step"]) / np.float32(step))
     if normals is None:
         normals = torch.zeros((int(verts.shape[0]), 3), dtype=torch.float32, device=verts.device)
-    r = runner.bake_texture(verts, faces, normals, density, t["max_size"], t["max_block_log2"], t["source"], t["ray_steps"], step)
+    views = {"view_colors": _view_colors_fn(runner, cfg, scene, dataset, step)} if t["source"] == "views" else {}
+    r = runner.bake_texture(verts, faces, normals, density, t["max_size"], t["max_block_log2"], t["source"], t["ray_steps"], step, **views)
     write_png(base + ".png", quantize_colors(r["texture"].cpu().numpy()))
     write_obj(base + ".obj", to_world(verts.cpu().numpy(), scene["center"], scene["radius"]), faces.cpu().numpy(), r["uv"].cpu().numpy(),
               normals.cpu().numpy(), os.path.basename(base + ".png"))
     halved = "" if r["density_used"] == density else " (halved from %g to fit texture.max_size=%d)" % (density, t["max_size"])
     print("Texture: atlas %d x %d, %d texels used, %g texels per unit%s, source %s -> %s" % (
-        r["size"], r["size"], r["texels_used"], r["density_used"], halved, t["source"], base + ".obj"))
+        r["size"], r["size"], r["texels_used"], r["density_used"], halved,
+        t["source"] + (" (%d texels from views)" % r["texels_from_views"] if t["source"] == "views" else ""), base + ".obj"))
     return r
 
 
@@ -1079,6 +1243,19 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
     if o["source"] == "tsdf":
         return extract_tsdf(runner, cfg, scene, dataset, exp_dir)
     sparse = {"sparse": sp} if sp else {}  # (what every extract_mesh_attrs call below passes on)
+    cviews = o["colors"] and view_color_options(cfg)["color_source"] == "views"
+    totals = {}
+    if cviews:  # (the facing test wants the normals whether or not the .ply carries them)
+        from . import runtime
+        vstep = runtime.host().grid_spec([float(x) for x in o["bbox_min"]], [float(x) for x in o["bbox_max"]], int(o["resolution"]),
+                                         8192 if sp else 1024)[0]
+        vfn = _view_colors_fn(runner, cfg, scene, dataset, vstep, totals)
+
+    def vertex_colors(m):
+        if not o["colors"]:
+            return None
+        colors = m["colors"].cpu().numpy()
+        return _colors_from_views(vfn, totals, m["verts"], m["normals"], colors) if cviews and len(colors) else colors
     bricks = ""
     k, faces_in = o["simplify"], 0
     path = os.path.join(exp_dir, "meshes", "%d_%d%s.ply" % (runner.iter_step, o["resolution"], "_s%d" % k if k >= 2 else ""))
@@ -1091,22 +1268,21 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
         v = to_world(verts.cpu().numpy(), scene["center"], scene["radius"])
         write_ply(path, v, faces.cpu().numpy())
     else:
-        m = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"], o["normals"],
-                                      o["colors"], o["normal_source"], *((k,) if k >= 2 else ()), **sparse)
+        m = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"],
+                                      o["normals"] or cviews, o["colors"], o["normal_source"], *((k,) if k >= 2 else ()), **sparse)
         verts, faces, faces_in = m["verts"], m["faces"], m.get("faces_in", 0)
         bricks = _bricks(sp, m["sparse"]) if sp else ""
         v = to_world(verts.cpu().numpy(), scene["center"], scene["radius"])
         # (the world frame is a uniform scale and a shift of the normalised one: normals are the same in both)
-        write_ply(path, v, faces.cpu().numpy(), m["normals"].cpu().numpy() if o["normals"] else None,
-                  m["colors"].cpu().numpy() if o["colors"] else None)
+        write_ply(path, v, faces.cpu().numpy(), m["normals"].cpu().numpy() if o["normals"] else None, vertex_colors(m))
     print("Mesh: %d vertices, %d faces%s at level %g%s -> %s" % (len(v), len(faces), _simplified(k, faces_in), o["level"], bricks, path))
     refine = {} if o["refine"] is None else {"refine": o["refine"]}  # (what every later extract_mesh_attrs call passes on)
     if refine:  # the unrefined file stands as it is; everything below works on the refined mesh
-        m = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"], o["normals"],
-                                      o["colors"], o["normal_source"], k if k >= 2 else 0, **refine, **sparse)
+        m = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"],
+                                      o["normals"] or cviews, o["colors"], o["normal_source"], k if k >= 2 else 0, **refine, **sparse)
         verts, faces = m["verts"], m["faces"]
-        path = _write_refined(path, scene, verts, faces, m["normals"].cpu().numpy() if o["normals"] else None,
-                              m["colors"].cpu().numpy() if o["colors"] else None, dict(m["refine"]))
+        path = _write_refined(path, scene, verts, faces, m["normals"].cpu().numpy() if o["normals"] else None, vertex_colors(m),
+                              dict(m["refine"]))
     tex = None
     if texture_options(cfg)["texture"] or check_options(cfg)["check"] or dist["distance"] or dist["distance_to"] is not None:
         from . import runtime
@@ -1116,7 +1292,7 @@ def extract(runner, cfg, scene, exp_dir, dataset=None):
         m = runner.extract_mesh_attrs(o["bbox_min"], o["bbox_max"], o["resolution"], o["level"], o["min_component_faces"], True, False,
                                       o["normal_source"], *((k,) if k >= 2 or refine else ()), **refine, **sparse)
         verts, faces = m["verts"], m["faces"]
-        tex = _run_texture(runner, cfg, scene, verts, faces, m["normals"], step, path)
+        tex = _run_texture(runner, cfg, scene, verts, faces, m["normals"], step, path, dataset)
     if check_options(cfg)["check"]:
         _run_check(runner, cfg, scene, dataset, verts, faces, step, path, tex)
     if dist["distance"]:  # the same floater filter, extracted once more without the simplification (as the texture path re-extracts)

@@ -240,8 +240,10 @@ def main(argv=None):
         elif mode == "extract_mesh":  # no reference counterpart: <exp>/meshes/<iter>_<res>.ply (mesh.py; options mesh.*)
             from . import mesh
             mesh.texture_options(cfg)  # (mesh.texture / texture.*: a bad value raises before anything is extracted or written)
-            # (the TSDF is fused from renders of the training cameras, and mesh.check casts their rays at the mesh: both need them)
-            if mesh.options(cfg)["source"] == "tsdf" or mesh.check_options(cfg)["check"]:
+            # (the TSDF is fused from renders of the training cameras, mesh.check casts their rays at the mesh, and the views colour
+            # sources project into them: all need them)
+            views = mesh.view_color_options(cfg)["color_source"] == "views" or mesh.texture_options(cfg)["source"] == "views"
+            if mesh.options(cfg)["source"] == "tsdf" or mesh.check_options(cfg)["check"] or views:
                 mesh.extract(runner, cfg, sc, exp_dir, dataset=ds)
             else:
                 mesh.extract(runner, cfg, sc, exp_dir)

@@ -1201,6 +1201,47 @@ int f2n_brick_mesh_emit_masked(void* stream, int nx, int ny, int nz, int B, int 
                                int64_t* face_keys /*[nf]*/, int64_t* face_vert_keys /*[nf,3]*/);
 
 /* ---------------------------------------------------------------------------------------------------
+ * View-colour fusion: the colours the views observed, blended onto surface points (additive; the ABI version is unchanged).  No
+ * reference counterpart.  csrc/dataset.hip; tests/view_colors_ref.py restates the definitions in numpy.
+ * ------------------------------------------------------------------------------------------------- */
+/* Adds the observations of n_views views to the running sums acc [n,C] (sum of weight x colour), wsum [n] (sum of weight) and count [n]
+ * (int32: the views that contributed) of n surface points.  points [n,3]; normals [n,3] or NULL: OUTWARD, as the exporters produce
+ * them; a row that is all zero or has a component that is not finite means "no normal", and so does NULL.
+ * The views are those of f2n_tsdf_integrate: poses [V,3,4], intri [V,3,3] in units of map pixels, dist_params [V,4], depth [V,h,w] (the
+ * Euclidean distance to the surface; no surface where the value is not > 0), conf [V,h,w] or NULL (= 1); image [V,h,w,C] float32 on
+ * the pixel grid of depth, C in [1, 4].
+ * One thread owns one point p and walks the views in index order; every operation below is ONE fp32 rounding, never an FMA:
+ *    1. steps 1-6 of f2n_tsdf_integrate unchanged (the same device function): q = p - o_v, c = R^T q, s = -c_2 (skip the view unless
+ *       s > 0), u, v, the distortion, x, y;  r = f2n_norm3(q) = sqrt(q_0 q_0 + (q_1 q_1 + q_2 q_2))
+ *    2. facing: with a normal n, cosv = (n_0 (-q_0) + (n_1 (-q_1) + n_2 (-q_2))) / r; skip unless cosv > cos_min (NaN skips);
+ *       facing = cosv.  Without a normal, facing = 1 and no view is skipped here.
+ *    3. taps: xs = x - 0.5, ys = y - 0.5, b0 = floor(xs), a0 = floor(ys), fx = xs - b0, fy = ys - a0; the four taps (a0 + i, b0 + j) in
+ *       the order (i, j) = (0,0), (0,1), (1,0), (1,1) with the bilinear weights b = (i ? fy : 1 - fy) (j ? fx : 1 - fx) (a subtraction each,
+ *       then the product).  A tap with a0 + i outside [0, h) or b0 + j outside [0, w) (compared as floats; NaN is outside) DOES NOT
+ *       EXIST -- there is no observation beyond the image border, nothing is clamped.  An existing tap with D = its depth and cf = its
+ *       conf (or 1) is VALID iff D > 0, cf > 0, !(D - r < -tol) and !(D - r > tol): the point lies on that pixel's visible surface
+ *       within tol -- a point the view sees occluded is not valid, nor is one floating in front of what the view sees.  A tap's
+ *       validity depends on its own depth only: colours do not bleed across a silhouette.
+ *    4. weight: om_k = b_k cf_k of the valid taps; om = ((0 + om_k) + ...) over the valid taps in tap order; skip the view unless om > 0
+ *    5. col_c = ((0 + om_k image_k,c) + ...) over the valid taps in tap order (image is read for valid taps only);
+ *       acc_c += facing col_c;  wsum += facing om;  count += 1
+ * acc, wsum and count are read once and written once per launch; there are no atomics, so the outputs are a function of the inputs
+ * alone, and the views [0, k) followed by [k, V) into the same state give the bits of one call over [0, V).
+ * The weighting is a CHOICE, not a measurement: confidence (the rendered opacity, where the maps are rendered) times the cosine of the
+ * viewing angle, and a weighted mean over all views that see the point rather than the pick of a best view.
+ * n == 0 or n_views == 0: F2N_OK, nothing is touched.  F2N_ERR_INVALID_ARG: a negative size, C outside [1, 4], h or w outside
+ * [1, 2^24], tol not positive and finite, cos_min NaN, a NULL pointer other than normals and conf. */
+int f2n_view_colors_accumulate(void* stream, int64_t n, const float* points /*[n,3]*/, const float* normals /*[n,3] or NULL*/,
+                               int n_views, const float* poses /*[V,3,4]*/, const float* intri /*[V,3,3]*/,
+                               const float* dist_params /*[V,4]*/, const float* depth /*[V,h,w]*/, const float* conf /*[V,h,w] or NULL*/,
+                               const float* image /*[V,h,w,C]*/, int C, int h, int w, float tol, float cos_min, float* acc /*[n,C]*/,
+                               float* wsum /*[n]*/, int32_t* count /*[n]*/);
+/* The blended colour of the sums and where it is known: known[i] = (count[i] >= min_views && wsum[i] > 0);
+ *   rgb[i,c] = known[i] ? acc[i,c] / wsum[i] : 0.   F2N_ERR_INVALID_ARG: n < 0, C outside [1, 4], a NULL pointer (n > 0). */
+int f2n_view_colors_finalize(void* stream, int64_t n, int C, const float* acc /*[n,C]*/, const float* wsum /*[n]*/,
+                             const int32_t* count /*[n]*/, int min_views, float* rgb /*[n,C]*/, uint8_t* known /*[n]*/);
+
+/* ---------------------------------------------------------------------------------------------------
  * Mesh simplification by vertex clustering with quadric-error placement (additive; the ABI version is unchanged).  Lindstrom 2000
  * with Garland-Heckbert plane quadrics.  No reference counterpart.  csrc/octree.hip.
  * ------------------------------------------------------------------------------------------------- */
