@@ -319,6 +319,9 @@ __global__ __launch_bounds__(256) void oct_intersect_coop_kernel(
 // ---------------------------------------------------------------------------------------------------
 #define F2N_SCAN_THREADS 1024
 #define F2N_SCAN_ITEMS 4
+// IDX is the type of the element index, the chunk counter and the start_end offset: int for every n <= 2^29 (the code of
+// the training step's queue), int64_t above, where 2 * i passes 2^31 from element 2^30 on and chunk + 4096 can pass it too.
+template <typename IDX = int>
 __device__ __forceinline__ void f2n_segment_scan_block(int n, const int32_t* __restrict__ counts, int32_t* __restrict__ start_end,
                                                        int32_t* __restrict__ total, int32_t* __restrict__ mirror,
                                                        const int32_t* __restrict__ also, int n_also) {
@@ -327,8 +330,8 @@ __device__ __forceinline__ void f2n_segment_scan_block(int n, const int32_t* __r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) s_carry = 0;
   __syncthreads();
-  for (int chunk = 0; chunk < n; chunk += F2N_SCAN_THREADS * F2N_SCAN_ITEMS) {
-    const int i0 = chunk + tid * F2N_SCAN_ITEMS;
+  for (IDX chunk = 0; chunk < n; chunk += F2N_SCAN_THREADS * F2N_SCAN_ITEMS) {
+    const IDX i0 = chunk + tid * F2N_SCAN_ITEMS;
     int v[F2N_SCAN_ITEMS];
     int local = 0;
 #pragma unroll
@@ -370,11 +373,12 @@ __device__ __forceinline__ void f2n_segment_scan_block(int n, const int32_t* __r
   }
 }
 
+template <typename IDX>
 __global__ __launch_bounds__(F2N_SCAN_THREADS) void segment_scan_kernel(int n, const int32_t* __restrict__ counts,
                                                                         int32_t* __restrict__ start_end,
                                                                         int32_t* __restrict__ total, int32_t* __restrict__ mirror,
                                                                         const int32_t* __restrict__ also, int n_also) {
-  f2n_segment_scan_block(n, counts, start_end, total, mirror, also, n_also);
+  f2n_segment_scan_block<IDX>(n, counts, start_end, total, mirror, also, n_also);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1507,8 +1511,12 @@ int f2n_oct_intersect_repair(void* stream, int n_rays, int max_hits, const uint8
 int f2n_segment_scan_ex(void* stream, int n, const int32_t* counts, int32_t* start_end, int32_t* total, int32_t* mirror,
                         const int32_t* also, int n_also) {
   if (n < 0 || n_also < 0 || n_also > 4 || (n_also > 0 && (also == nullptr || mirror == nullptr))) return F2N_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(segment_scan_kernel, dim3(1), dim3(F2N_SCAN_THREADS), 0, (hipStream_t) stream, n, counts,
-                     start_end, total, mirror, also, n_also);
+  if (n > (1 << 29))  // 64-bit indices only where 32-bit ones could overflow: every n of the training step keeps its code
+    hipLaunchKernelGGL(segment_scan_kernel<int64_t>, dim3(1), dim3(F2N_SCAN_THREADS), 0, (hipStream_t) stream, n, counts,
+                       start_end, total, mirror, also, n_also);
+  else
+    hipLaunchKernelGGL(segment_scan_kernel<int>, dim3(1), dim3(F2N_SCAN_THREADS), 0, (hipStream_t) stream, n, counts,
+                       start_end, total, mirror, also, n_also);
   return f2n_launch_status();
 }
 

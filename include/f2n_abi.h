@@ -114,7 +114,10 @@ int f2n_oct_intersect_count(void* stream, int n_rays, int max_hits, const uint8_
 
 /* Ray-ordered segment allocation: start_end[i] = (sum_{j<i} counts[j], sum_{j<=i} counts[j]);
  * total[0] = sum.  Replaces the racing atomicAdd allocator (PersSampler.cu:144) and the
- * torch::cumsum + .item() host sync (:395-397); also FilterIdxBounds' cumsum (Renderer/Renderer.cu:44-48). */
+ * torch::cumsum + .item() host sync (:395-397); also FilterIdxBounds' cumsum (Renderer/Renderer.cu:44-48).
+ * Any n in [0, 2^31 - 1] is accepted (n < 0: F2N_ERR_INVALID_ARG): the element index, the chunk counter and the start_end offset 2 i
+ * are 64-bit for n > 2^29 and 32-bit below, where nothing can overflow (one instantiation of the kernel each; the results are the
+ * same).  The sums themselves are int32: the caller keeps the total below 2^31. */
 int f2n_segment_scan(void* stream, int n, const int32_t* counts, int32_t* start_end /*[n,2]*/, int32_t* total /*[1]*/);
 /* The same, and the host's copy of the result from the same launch: `mirror` (or NULL) is a DEVICE pointer to MAPPED HOST
  * memory (hipHostMallocMapped + hipHostGetDevicePointer) that receives also[0..n_also) followed by the total -- e.g. the hit
@@ -958,7 +961,9 @@ int f2n_density_scatter(void* stream, int n, const int32_t* anchors /*[n,3]*/, c
  *   Position p_a + t (p_b - p_a), t = (level - g_a) / (g_b - g_a), a = the lower endpoint, p = lo + step * index as above.
  * f2n_mesh_count: edge_mask [N] (bit t: the edge of type t crosses), the per-corner vertex counts and per-cell face counts and their
  *   scans (N = nx*ny*nz corners, C = (nx-1)(ny-1)(nz-1) cells); totals[0] = vertices, totals[1] = faces -- the only values a caller
- *   needs on the host (to size the outputs).
+ *   needs on the host (to size the outputs).  Any grid with N <= 2^31 - 1 is accepted (F2N_ERR_INVALID_ARG above, e.g. 1291^3; a cubic
+ *   box at resolution 1024 has N = 1025^3 > 2^30): corner and cell indices and the offsets into the [N,2] / [C,2] scans are 64-bit,
+ *   f2n_segment_scan's as stated there.
  * f2n_mesh_emit: verts [totals[0],3] f32, faces [totals[1],3] int32.  lo is HOST data. */
 int f2n_mesh_count(void* stream, int nx, int ny, int nz, const float* grid, float level, uint8_t* edge_mask /*[N]*/,
                    int32_t* vert_counts /*[N]*/, int32_t* vert_start_end /*[N,2]*/, int32_t* face_counts /*[C]*/,

@@ -99,18 +99,20 @@ def box_meets_live_leaf(nodes, blo, bhi):
     return False
 
 
-def brick_mark(nodes, lo, step, n, B):
-    """flags [nbz, nby, nbx] uint8."""
+def brick_mark(nodes, lo, step, n, B, b0=(0, 0, 0), b1=None):
+    """flags [nbz, nby, nbx] uint8 -- of the bricks b0 <= (bx, by, bz) <= b1 only when a box of bricks is given (shape b1 - b0 + 1,
+    reversed): a virtual grid is never walked whole."""
     nb = n_bricks(n, B)
+    b1 = tuple(v - 1 for v in nb) if b1 is None else b1
     ax = mr.grid_points(lo, step, n)
-    flags = np.zeros((nb[2], nb[1], nb[0]), np.uint8)
-    for bz in range(nb[2]):
-        for by in range(nb[1]):
-            for bx in range(nb[0]):
+    flags = np.zeros((b1[2] - b0[2] + 1, b1[1] - b0[1] + 1, b1[0] - b0[0] + 1), np.uint8)
+    for bz in range(b0[2], b1[2] + 1):
+        for by in range(b0[1], b1[1] + 1):
+            for bx in range(b0[0], b1[0] + 1):
                 bc = (bx, by, bz)
                 blo = [ax[k][bc[k] * B] for k in range(3)]
                 bhi = [ax[k][min(bc[k] * B + B, n[k] - 1)] for k in range(3)]
-                flags[bz, by, bx] = 1 if box_meets_live_leaf(nodes, blo, bhi) else 0
+                flags[bz - b0[2], by - b0[1], bx - b0[0]] = 1 if box_meets_live_leaf(nodes, blo, bhi) else 0
     return flags
 
 
@@ -153,3 +155,77 @@ def mesh_keys(grid, level):
                 cell = (z * (ny - 1) + y) * (nx - 1) + x
                 fk.extend(16 * cell + q for q in range(k))
     return vk, np.array(fk, np.int64)
+
+
+# ---- virtual grids whose indices need more than 32 bits --------------------------------------------------------------------------
+# Only a WINDOW of at most 64 bricks of such a grid is ever touched: its dense sub-grid, with lo translated by whole steps, is an
+# ordinary small grid.  step is a power of two and lo a multiple of it, small enough for every coordinate lo + step i to be exact in
+# float32 -- the sub-grid's points are then the same floats as the big grid's, and every result can be compared bit for bit.
+HUGE_STEP = 2.0 ** -6
+# n, B, lo, the window's size in bricks, the first brick of the inner window (the far window ends at the last brick of every axis)
+HUGE_GRIDS = {
+    "wide16": dict(n=(65537, 65537, 33), B=16, lo=(-512.0, -600.25, 3.5), wb=(2, 2, 1), inner=(2049, 1365, 1)),
+    "wide8": dict(n=(65537, 65537, 33), B=8, lo=(-512.0, -600.25, 3.5), wb=(3, 3, 2), inner=(4097, 2731, 1)),
+    "full": dict(n=(524288, 32765, 9), B=4, lo=(-4096.0, -250.5, -0.0625), wb=(4, 4, 2), inner=(65537, 4099, 0)),
+}
+HUGE_REFUSED = ((524288, 32769, 9), 4)  # 131072 x 8192 x 2 = 2^31 bricks exactly: one too many
+
+
+def huge_window(name, which, lo_w=None, step=HUGE_STEP):
+    """The window `which` ("far": ends at the last brick of every axis; "inner": strictly inside along every axis that has more bricks
+    than the window) of HUGE_GRIDS[name].  lo_w given: the grid is placed so that the window's first corner lies there (lo = lo_w -
+    step i0) instead of at the table's lo.  Returns n, B, lo, step, nb, w0 / wb (first brick, bricks per axis), i0 (first corner), m
+    (points per axis: clipped at n - 1), lo_w, ids (the window's bricks, ascending: the order of local_ids, their ids on the
+    window's own grid m)."""
+    spec = HUGE_GRIDS[name]
+    n, B, wb = spec["n"], spec["B"], spec["wb"]
+    nb = n_bricks(n, B)
+    w0 = tuple(nb[k] - wb[k] for k in range(3)) if which == "far" else spec["inner"]
+    assert all(0 <= w0[k] and w0[k] + wb[k] <= nb[k] for k in range(3)) and wb[0] * wb[1] * wb[2] <= 64
+    if which == "inner":
+        assert all(0 < w0[k] and w0[k] + wb[k] < nb[k] for k in range(3) if nb[k] > wb[k] + 1)
+    i0 = tuple(w0[k] * B for k in range(3))
+    m = tuple(min(i0[k] + wb[k] * B, n[k] - 1) - i0[k] + 1 for k in range(3))
+    if lo_w is None:
+        lo = tuple(float(v) for v in spec["lo"])
+        lo_w = tuple(lo[k] + step * i0[k] for k in range(3))  # (float64: exact)
+    else:
+        lo_w = tuple(float(v) for v in lo_w)
+        lo = tuple(lo_w[k] - step * i0[k] for k in range(3))
+    for k in range(3):  # every coordinate of the window is exact in float32, on the big grid and on the sub-grid
+        i = np.arange(i0[k], i0[k] + m[k])
+        exact = lo[k] + step * i.astype(np.float64)
+        big = F32(lo[k]) + F32(step) * i.astype(F32)
+        sub = F32(lo_w[k]) + F32(step) * np.arange(m[k], dtype=F32)
+        assert F32(lo[k]) == lo[k] and F32(lo_w[k]) == lo_w[k] and (big.astype(np.float64) == exact).all() and big.tobytes() == sub.tobytes()
+    assert n_bricks(m, B) == wb
+    local_ids = np.arange(wb[0] * wb[1] * wb[2], dtype=np.int32)
+    ids = np.array([brick_id(tuple(brick_coords(int(b), wb)[k] + w0[k] for k in range(3)), nb) for b in local_ids], np.int64)
+    assert (np.diff(ids) > 0).all() and ids[-1] < 2 ** 31
+    return dict(name=name, which=which, n=n, B=B, lo=lo, step=step, nb=nb, w0=w0, wb=wb, i0=i0, m=m, lo_w=lo_w, ids=ids.astype(np.int32),
+                local_ids=local_ids)
+
+
+def huge_magnitudes(w):
+    """Python integers: the largest corner, vertex and cell / face keys and brick id a window touches, and the grid's brick count."""
+    n, nb = w["n"], w["nb"]
+    top = [w["i0"][k] + w["m"][k] - 1 for k in range(3)]
+    corner = (top[2] * n[1] + top[1]) * n[0] + top[0]
+    cell = ((top[2] - 1) * (n[1] - 1) + top[1] - 1) * (n[0] - 1) + top[0] - 1
+    return dict(corner=corner, vertex_key=8 * corner + 6, face_key=16 * cell + 11, brick_id=int(w["ids"][-1]), bricks=nb[0] * nb[1] * nb[2])
+
+
+def window_sphere(w):
+    """[mz, my, mx] float32 of the window's sub-grid: radius - distance to a centre near the window's middle, evaluated in float64 at
+    the corners' world positions.  The inside corners keep two planes away from the window's faces: every crossing edge lies at least
+    one cell inside the window."""
+    m, step = w["m"], w["step"]
+    off = (0.13, -0.21, 0.07)
+    r = ((min(m) - 1) / 2.0 - 1.3) * step
+    ax = [w["lo_w"][k] + step * np.arange(m[k], dtype=np.float64) for k in range(3)]
+    c = [w["lo_w"][k] + step * ((m[k] - 1) / 2.0 + off[k]) for k in range(3)]
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    g = (r - np.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2)).astype(F32)
+    ins = np.argwhere(g > 0)
+    assert len(ins) > 0 and (ins >= 2).all() and (ins <= np.array(g.shape) - 3).all()
+    return g

@@ -207,6 +207,68 @@ def test_mesh_torus_empty_and_open(rt):
     assert len(f) > 0 and (cnt == 1).any() and cnt.max() == 2
 
 
+def test_dense_mesher_at_its_cap(rt):
+    """1025^3 = 1 076 890 625 grid points (mesh.resolution=1024 on a cubic box; about 31 GB of device memory): 2^30 lies in the plane
+    z = 1022 of this grid, so the corners of the planes z >= 1022 are the ones whose offset 2 i into the [N,2] vertex scan needs more than
+    31 bits.  The surface is a sphere of radius 9.3 cells near the far corner whose top lies between the planes z = 1022 and 1023: the
+    edges its cap crosses are owned by corners of the plane z = 1022, past 2^30 (asserted below in Python integers), and every crossing
+    edge keeps two cells away from the grid's faces along x and y and one along z.  step = 2^-6 and lo = -2^9 make every coordinate
+    exact, so the 33^3 sub-grid at the far corner with lo translated by 992 steps has the same points bit for bit: the big grid's
+    mesh must be the sub-grid's -- the restatement's (faces identical, vertices at test_mesh_matches_the_restatement's bar) and the
+    dense kernels' own (bit for bit; vertex and face order is lexicographic in (z, y, x) on both sides) -- unmasked and masked."""
+    h = rt.host()
+    N, Wn, step = 1025, 33, 2.0 ** -6
+    i0 = N - Wn
+    lo, lo_w = [-512.0] * 3, [-512.0 + step * i0] * 3
+    centre, radius = (1007.3, 1006.6, 1013.2), 9.3  # in cells
+    big, sub = mr.grid_points(lo, step, (N,) * 3), mr.grid_points(lo_w, step, (Wn,) * 3)
+    for k in range(3):  # lo + step (i0 + l) and lo_w + step l are the same floats, and exact
+        assert big[k][i0:].tobytes() == sub[k].tobytes()
+        assert (big[k].astype(np.float64) == lo[k] + step * np.arange(N)).all()
+    torch.cuda.reset_peak_memory_stats()
+    grid = torch.empty((N, N, N), dtype=torch.float32, device="cuda")
+    ax = torch.arange(N, dtype=torch.float64, device="cuda")
+    dxy = ((ax - centre[1]) ** 2)[:, None] + ((ax - centre[0]) ** 2)[None, :]
+    for z0 in range(0, N, 64):  # the signed distance in world units, positive inside; float64 in slabs of 64 planes
+        dz = ((ax[z0:z0 + 64] - centre[2]) ** 2)[:, None, None]
+        grid[z0:z0 + 64] = (step * (radius - torch.sqrt(dz + dxy[None]))).to(torch.float32)
+    del dxy, dz
+    assert int((grid[:i0] > 0).sum()) == 0 and int((grid[:, :i0] > 0).sum()) == 0 and int((grid[:, :, :i0] > 0).sum()) == 0  # all in the window
+    g_sub = grid[i0:, i0:, i0:].contiguous().cpu().numpy()
+    ins = g_sub > 0
+    at = np.argwhere(ins) + i0  # (z, y, x) of the inside corners: every crossing edge has one of them and a neighbour
+    assert at.min() >= i0 + 2 and at[:, 1:].max() <= N - 4 and at[:, 0].max() == N - 3 == 1022
+    past = 0  # crossing edges whose owner corner (the lower endpoint) has an index above 2^30
+    for o in mr.EDGE_OFFSETS:
+        d = (o & 1, (o >> 1) & 1, (o >> 2) & 1)
+        a, b = ins[:Wn - d[2], :Wn - d[1], :Wn - d[0]], ins[d[2]:, d[1]:, d[0]:]
+        for z, y, x in np.argwhere(a != b) + i0:
+            past += ((int(z) * N + int(y)) * N + int(x)) > 2 ** 30
+    assert past > 100 and N ** 3 - 1 > 2 ** 30 and (N - 1) ** 3 == 2 ** 30
+    try:
+        v, f = h.mesh_from_grid(grid, 0.0, lo, step)
+        rv, rf = mr.marching_tets(g_sub, 0.0, lo_w, step)
+        v, f = v.cpu().numpy(), f.cpu().numpy()
+        assert len(rf) > 1000 and f.shape == rf.shape and (f == rf).all()
+        assert v.shape == rv.shape and np.abs(v - rv).max() <= 1e-6 * step * max(1.0, np.abs(rv).max())
+        d_sub = torch.from_numpy(g_sub).cuda()
+        sv, sf = h.mesh_from_grid(d_sub, 0.0, lo_w, step)
+        assert f.dtype == np.int32 and f.tobytes() == sf.cpu().numpy().tobytes() and v.tobytes() == sv.cpu().numpy().tobytes()
+        # the masked mesher: valid on the far-corner window only (here every face lies in it: the unmasked mesh again)
+        valid = torch.zeros((N, N, N), dtype=torch.uint8, device="cuda")
+        valid[i0:, i0:, i0:] = 1
+        mv, mf = h.mesh_from_grid_masked(grid, valid, lo, step, 0.0)
+        smv, smf = h.mesh_from_grid_masked(d_sub, torch.ones((Wn,) * 3, dtype=torch.uint8, device="cuda"), lo_w, step, 0.0)
+        mv, mf = mv.cpu().numpy(), mf.cpu().numpy()
+        assert mf.tobytes() == smf.cpu().numpy().tobytes() and mv.tobytes() == smv.cpu().numpy().tobytes()
+        assert mf.tobytes() == f.tobytes() and mv.tobytes() == v.tobytes()
+        print("dense mesher at 1025^3: %d vertices, %d faces, %d crossing edges owned past 2^30; peak device memory %.1f GB"
+              % (len(v), len(f), past, torch.cuda.max_memory_allocated() / 1e9))
+    finally:
+        grid = valid = d_sub = ax = None
+        torch.cuda.empty_cache()
+
+
 def test_extraction_has_no_effect_on_training(rt, fox_state):
     st = fox_state
     rng = np.random.default_rng(5)

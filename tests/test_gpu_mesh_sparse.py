@@ -1,7 +1,8 @@
 """Sparse meshing on bricks on the MI355X (csrc/octree.hip, host/RendererQuery.cpp): the bodies of tests/test_mesh_sparse_cpu.py against the
 device through host.* and capi.*; the 129^3 sphere; runner.extract_mesh_sparse against runner.extract_mesh on the fox scene, bit for bit,
 in one batch and in several; a grid above the dense path's cap against the dense mesher on point queries; extract_mesh_attrs(...,
-sparse=); no effect on training; the launcher's mesh.sparse."""
+sparse=); no effect on training; the launcher's mesh.sparse.  Indices past 32 bits: windows of virtual grids with corner indices above
+2^36 and brick ids up to the last one below 2^31, f2n_brick_mark over 2^31 - 262144 bricks, extract_mesh_sparse at res 8192."""
 import os
 import sys
 
@@ -54,6 +55,86 @@ def test_kernel_cases_on_the_device(impls):
         for B in (4, 8):
             cpu.check_mesh_from_bricks(impl, B)
         cpu.check_errors(impl)
+
+
+def _capi_locate():
+    """cpu.check_huge_locate's `loc` over the ctypes binding (the host layer calls f2n_oct_locate_warp_bricks inside extract_mesh_sparse only)"""
+    import types
+    from f2_nerf_amd import capi
+
+    def bricks(ids, lo, step, n, B, tree, transes):
+        w, a = capi.locate_warp_bricks(_dev(np.asarray(ids, np.int32)), lo, step, n, B, _dev(tree), _dev(transes))
+        return _np(w), _np(a)
+
+    def points(pts, tree, transes):
+        w = torch.full((len(pts), 3), 7.0, device="cuda")
+        a = torch.full((len(pts), 3), 7, dtype=torch.int32, device="cuda")
+        capi.oct_locate_warp(len(pts), _dev(np.asarray(pts, F32)), _dev(tree), _dev(transes), w, a)
+        return _np(w), _np(a)
+
+    return types.SimpleNamespace(bricks=bricks, points=points)
+
+
+@pytest.mark.parametrize("name", sorted(sr.HUGE_GRIDS))
+def test_listed_brick_kernels_on_a_huge_virtual_grid(impls, name):
+    """corner indices past 2^36, vertex keys past 2^39, brick ids up to the last one below 2^31: windows of at most 64 bricks against the
+    dense kernels on the window's sub-grid (tests/test_mesh_sparse_cpu.py)"""
+    for impl in impls:
+        cpu.check_huge_mesh_from_bricks(impl, name)
+    cpu.check_huge_locate(_capi_locate(), name)
+
+
+def test_two_to_the_31_bricks_are_refused(impls):
+    import ctypes
+    from f2_nerf_amd import capi
+    for impl in impls:
+        cpu.check_huge_errors(impl)
+    (nx, ny, nz), B = sr.HUGE_REFUSED
+    flags, tree = torch.full((8,), 7, dtype=torch.uint8, device="cuda"), _dev(cpu.fox_tree())
+    rc = capi.lib().f2n_brick_mark(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), ctypes.c_void_p(tree.data_ptr()),
+                                   (ctypes.c_float * 3)(0.0, 0.0, 0.0), ctypes.c_float(1.0), ctypes.c_int(nx), ctypes.c_int(ny), ctypes.c_int(nz),
+                                   ctypes.c_int(B), ctypes.c_void_p(flags.data_ptr()))
+    torch.cuda.synchronize()
+    assert rc == -2 and bool((flags == 7).all())  # F2N_ERR_UNSUPPORTED, nothing written
+
+
+def test_brick_mark_on_the_full_grid(rt):
+    """f2n_brick_mark over 131072 x 8191 x 2 = 2^31 - 262144 bricks (2 GiB of flags, 3.4 10^7 workgroups): step 1 and an integer lo put
+    the fox tree's live leaves into a box of fewer than 4096 bricks next to the grid's far corner; inside that box the flags are the
+    restatement's, brick by brick, and no brick outside it is flagged.  Compared on the device: only the box reaches the host."""
+    from f2_nerf_amd import capi
+    n, B, step = sr.HUGE_GRIDS["full"]["n"], sr.HUGE_GRIDS["full"]["B"], 1.0
+    lo = (72.0 - step * (n[0] - 1), 72.0 - step * (n[1] - 1), -4.0)  # (integers below 2^24: every coordinate is exact)
+    nb = sr.n_bricks(n, B)
+    assert nb == (131072, 8191, 2) and nb[0] * nb[1] * nb[2] == 2 ** 31 - 262144
+    tree = cpu.fox_tree()
+    nodes = mr.parse_nodes(tree)
+    live = (nodes["childs"] < 0).all(1) & (nodes["trans"] >= 0)
+    half = nodes["side"][live].astype(np.float64)[:, None] / 2
+    bl, bh = (nodes["center"][live] - half).min(0), (nodes["center"][live] + half).max(0)
+    # the bricks that meet the closed bounding box of the live leaves, and one more on every side
+    b0 = tuple(max(0, int(np.floor((bl[k] - lo[k]) / step / B)) - 1) for k in range(3))
+    b1 = tuple(min(nb[k] - 1, int(np.floor((bh[k] - lo[k]) / step / B)) + 1) for k in range(3))
+    assert np.prod([b1[k] - b0[k] + 1 for k in range(3)]) <= 4096 and sr.brick_id(b1, nb) > 2 ** 31 - 2 ** 20
+    want = sr.brick_mark(nodes, lo, step, n, B, b0, b1)
+    assert set(np.unique(want)) == {0, 1}
+    torch.cuda.reset_peak_memory_stats()
+    d_tree = _dev(tree)
+    for mark in (rt.host().brick_mark, capi.brick_mark):
+        flags = mark(d_tree, list(lo), step, list(n), B)
+        assert flags.dtype == torch.uint8 and tuple(flags.shape) == nb[::-1]
+        box = _np(flags[b0[2]:b1[2] + 1, b0[1]:b1[1] + 1, b0[0]:b1[0] + 1])
+        assert (box == want).all()
+        # nothing outside the box: the sum of all flags is the box's (every flag is 0 or 1; counted in slices of 2^27: a reduction over
+        # the whole tensor works on a widened copy of the 2 GiB)
+        flat = flags.view(-1)
+        parts = [flat[a:a + (1 << 27)] for a in range(0, flat.numel(), 1 << 27)]
+        assert max(int(p.max()) for p in parts) == 1 and sum(int(torch.count_nonzero(p)) for p in parts) == int(want.sum())
+        del flat, parts
+        del flags
+    print("brick_mark on %d bricks: %d of the %d in the box flagged; peak device memory %.1f GB"
+          % (nb[0] * nb[1] * nb[2], int(want.sum()), want.size, torch.cuda.max_memory_allocated() / 1e9))
+    torch.cuda.empty_cache()
 
 
 def test_sphere_129_on_bricks(rt):
@@ -126,6 +207,44 @@ def test_extract_mesh_sparse_equals_extract_mesh_on_the_fox(rt, fox_runner, fox_
     assert parts["stats"]["batches"] >= 4 and {k: v for k, v in parts["stats"].items() if k != "batches"} == {k: v for k, v in st.items() if k != "batches"}
     assert _same(parts["verts"], dv) and _same(parts["faces"], df)
     assert runner.density_slab_points == slab
+
+
+# res 8192 with a power-of-two step: 8193 x 8193 x 65 = 4 363 096 385 grid points, more than 2^32.  tests/mesh_sparse_ref.brick_mark flags
+# 5379 of its 512 x 512 x 4 bricks of 16^3 cells on the fox tree (computed on the CPU over the bricks around the live leaves).
+RES_8192_BOX = ([-512.0, -512.0, -4.0], [512.0, 512.0, 4.0])
+
+
+def test_extract_mesh_sparse_at_res_8192(rt, fox_runner, fox_state, fox_level):
+    """runner.extract_mesh_sparse on a grid of more than 2^32 points against runner.extract_mesh on the bounding window of the flagged
+    bricks (the same step, lo translated by whole steps: exact), bit for bit; the stats carry the grid and the brick count unharmed"""
+    from f2_nerf_amd import capi
+    runner, h = fox_runner, rt.host()
+    (lo, hi), res, B = RES_8192_BOX, 8192, 16
+    step, nx, ny, nz = h.grid_spec(lo, hi, res, 8192)
+    n = (nx, ny, nz)
+    assert step == 0.125 and n == (8193, 8193, 65) and nx * ny * nz > 2 ** 32
+    nb = sr.n_bricks(n, B)
+    flags = _np(capi.brick_mark(_dev(np.asarray(fox_state["tree_nodes"], np.uint8).reshape(-1)), lo, step, n, B))
+    assert 1 <= int(flags.sum()) <= 20000, int(flags.sum())
+    at = np.argwhere(flags)  # (bz, by, bx)
+    w0, w1 = at.min(0)[::-1], at.max(0)[::-1]
+    i0 = [int(w0[k]) * B for k in range(3)]
+    i1 = [min((int(w1[k]) + 1) * B, n[k] - 1) for k in range(3)]
+    lo_w, hi_w = [lo[k] + step * i0[k] for k in range(3)], [lo[k] + step * i1[k] for k in range(3)]
+    res_w = max(i1[k] - i0[k] for k in range(3))
+    assert res_w <= 1024 and h.grid_spec(lo_w, hi_w, res_w)[0] == step and tuple(h.grid_spec(lo_w, hi_w, res_w)[1:]) == tuple(i1[k] - i0[k] + 1 for k in range(3))
+    torch.cuda.reset_peak_memory_stats()
+    m = runner.extract_mesh_sparse(lo, hi, res, fox_level, B)
+    st = m["stats"]
+    dv, df = runner.extract_mesh(lo_w, hi_w, res_w, fox_level)
+    print("res 8192, B %d: %r; %d vertices, %d faces; window %r..%r; peak device memory %.1f GB"
+          % (B, st, len(dv), len(df), i0, i1, torch.cuda.max_memory_allocated() / 1e9))
+    assert len(df) > 1000 and m["faces"].dtype == torch.int32 and m["verts"].dtype == torch.float32
+    # (tens of millions of vertices and faces: compared where they are)
+    assert torch.equal(m["faces"], df) and torch.equal(m["verts"].view(torch.int32), dv.view(torch.int32))
+    assert st["grid"] == n and st["bricks"] == nb[0] * nb[1] * nb[2] == 512 * 512 * 4 and st["active_bricks"] == int(flags.sum())
+    assert 0 < st["meshed_bricks"] <= st["active_bricks"]
+    assert st["points_evaluated"] == _expected_points(flags, n, B) and 0 < st["points_nonempty"] <= st["points_evaluated"]
 
 
 def test_extract_mesh_sparse_refuses(fox_runner, fox_level):

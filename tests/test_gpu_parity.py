@@ -259,6 +259,43 @@ def test_segment_scan(hip):
     assert int(tot.item()) == 0  # empty input
 
 
+def test_segment_scan_past_2_to_30_elements(hip):
+    """n = 2^30 + 4097: from element 2^30 on the offset 2 i into start_end needs more than 31 bits (the 64-bit instantiation that
+    f2n_segment_scan_ex picks for n > 2^29), and the last chunk is ragged (one element).  Counts in {0, 1} drawn on the device, so the
+    total fits int32; checked on the device in slices of 2^27 with a carried offset -- nothing of size n reaches the host.  About
+    13 GB of device memory (counts 4.3 GB, start_end 8.6 GB), released at the end."""
+    import ctypes
+    n = (1 << 30) + 4097
+    assert ctypes.c_int(n).value == n and 2 * (n - 1) > 0x7fffffff and (n - 1) % 4096 == 0  # (the binding's int holds n as it is)
+    piece = 1 << 27
+    torch.cuda.reset_peak_memory_stats()
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(11)
+    counts = torch.empty(n, dtype=torch.int32, device=DEV)
+    for a in range(0, n, piece):
+        counts[a:a + piece] = torch.randint(0, 2, (min(piece, n - a),), dtype=torch.int32, device=DEV, generator=gen)
+    se = torch.full((n, 2), -1, dtype=torch.int32, device=DEV)
+    tot = torch.full((1,), -1, dtype=torch.int32, device=DEV)
+    try:
+        hip.segment_scan(n, counts, se, tot)
+        carry = total = 0
+        for a in range(0, n, piece):
+            c = counts[a:a + piece]
+            end = torch.cumsum(c, 0, dtype=torch.int32) + carry
+            assert bool((se[a:a + piece, 1] == end).all()), a
+            assert bool((se[a:a + piece, 0] == end - c).all()), a
+            carry = int(end[-1])
+            total += int(c.sum())
+            del end
+        assert carry == total and int(tot.item()) == total and (1 << 28) < total < (1 << 30)
+        assert int(se[n - 1, 1]) == total and int(se[1 << 30, 1]) - int(se[(1 << 30) - 1, 1]) == int(counts[1 << 30])
+        print("segment scan of %d elements: total %d; peak device memory %.1f GB" % (n, total, torch.cuda.max_memory_allocated() / 1e9))
+    finally:
+        c = end = None  # (views of counts)
+        del counts, se, tot
+        torch.cuda.empty_cache()
+
+
 def test_segment_scan_and_flags_write_their_host_mirror(hip):
     """f2n_segment_scan_ex / f2n_nonfinite_flags_ex: the launch that produces a count (or the finiteness flags) also writes
     the host's copy into mapped host memory -- what the host reads behind an event instead of queueing a copy."""

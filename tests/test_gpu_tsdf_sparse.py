@@ -1,7 +1,8 @@
 """Sparse TSDF fusion on bricks on the MI355X (csrc/dataset.hip, csrc/octree.hip, host/RendererQuery.cpp): the bodies of
 tests/test_tsdf_sparse_cpu.py against the device through host.* and capi.*; the C entry points' error codes; mesh.fuse_tsdf_sparse against
 mesh.fuse_tsdf + host.mesh_from_grid_masked on the fox scene, bit for bit, in one batch and in several; no effect on training; the
-launcher's tsdf.sparse."""
+launcher's tsdf.sparse.  Indices past 32 bits: windows of virtual grids with corner indices above 2^36 and brick ids up to the last one
+below 2^31; f2n_tsdf_brick_mark over more bricks than it launches workgroups."""
 import ctypes
 import os
 import sys
@@ -16,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import mesh_sparse_ref as sr  # noqa: E402
 import tsdf_ref as tr  # noqa: E402
+import tsdf_sparse_ref as ts  # noqa: E402
 import test_tsdf_sparse_cpu as cpu  # noqa: E402
 from test_gpu_tsdf import _fox_options  # noqa: E402
 
@@ -71,6 +73,56 @@ def test_flagged_bricks_give_the_dense_mesh(impl, fox_state, name, B):
 
 def test_value_errors(impl, fox_state):
     cpu.check_value_errors(impl, fox_state)
+
+
+@pytest.mark.parametrize("name", sorted(sr.HUGE_GRIDS))
+def test_listed_brick_kernels_on_a_huge_virtual_grid(impl, fox_state, name):
+    """corner indices past 2^36, brick ids up to the last one below 2^31: the masked brick mesher and the brick integration over windows
+    of at most 64 bricks against the dense kernels on the window's sub-grid (tests/test_tsdf_sparse_cpu.py)"""
+    cpu.check_huge_masked_mesher(impl, name)
+    cpu.check_huge_integrate_bricks(impl, fox_state, name)
+
+
+def test_two_to_the_31_bricks_are_refused(impl, fox_state):
+    from f2_nerf_amd import capi
+    cpu.check_huge_value_errors(impl, fox_state)
+    (nx, ny, nz), B = sr.HUGE_REFUSED
+    w, c, big = cpu.huge_tsdf_case(fox_state, "full", "inner")
+    d = dict(poses=_dev(c["poses"]), intri=_dev(c["intri"]), dist=_dev(c["dist"]), depth=_dev(c["depth"]), conf=_dev(c["conf"]),
+             flags=torch.full((8,), 7, dtype=torch.uint8, device="cuda"), ids=_dev(w["ids"][:2]),
+             S=torch.full((2, 125), 7.0, device="cuda"), W=torch.full((2, 125), 7.0, device="cuda"))
+    assert _raw(capi.lib(), big, d, nx=nx, ny=ny, nz=nz, B=B) == (cpu.UNSUPPORTED, cpu.UNSUPPORTED)
+    torch.cuda.synchronize()
+    assert (d["flags"] == 7).all() and (d["S"] == 7).all() and (d["W"] == 7).all()  # nothing was written
+    assert _raw(capi.lib(), big, d, "integrate", B=B) == 0 and (d["W"] != 7).any()  # the full grid, 2^31 - 262144 bricks, is accepted
+
+
+def test_brick_mark_where_a_workgroup_takes_several_bricks(impl, fox_state):
+    """n = (524288, 97, 9), B = 4: 131072 x 24 x 2 = 6 291 456 bricks, six for every workgroup of f2n_tsdf_brick_mark's 2^20.  Two views of
+    tsdf_ref.synthetic_case see the last 8 bricks along x only: the case is built on the window's own grid (32 x 97 x 9 points, a
+    power-of-two step, lo a multiple of it) and every depth that could put a hit at or below the window's second plane is removed
+    (a hit needs |p - o| <= D + trunc, and |p - o| >= o_x - p_x).  Inside the window the flags are the restatement's; outside all zero."""
+    n, B, wbx = (524288, 97, 9), 4, 8
+    nb = sr.n_bricks(n, B)
+    assert nb == (131072, 24, 2) and nb[0] * nb[1] * nb[2] == 6 * 2 ** 20
+    i0 = (nb[0] - wbx) * B
+    c = tr.synthetic_case(fox_state, dims=(n[0] - i0, n[1], n[2]), n_views=2, pow2=True)
+    step, trunc = float(c["step"]), float(c["trunc"])
+    lo = (float(c["lo"][0]) - step * i0, float(c["lo"][1]), float(c["lo"][2]))
+    x_big = F32(lo[0]) + F32(step) * np.arange(i0, n[0]).astype(F32)
+    x_sub = c["lo"][0] + c["step"] * np.arange(n[0] - i0, dtype=F32)
+    assert F32(lo[0]) == lo[0] and x_big.tobytes() == x_sub.tobytes() and (x_big.astype(np.float64) == lo[0] + step * np.arange(i0, n[0])).all()
+    depth = c["depth"].copy()
+    for v in range(len(depth)):
+        limit = (float(c["poses"][v, 0, 3]) - (float(c["lo"][0]) + step)) - trunc - 1e-3
+        depth[v][np.isfinite(depth[v]) & (depth[v] > limit)] = 0.0
+    c = dict(c, depth=depth)
+    want = ts.brick_mark(c, B)
+    assert want.shape == (nb[2], nb[1], wbx) and set(np.unique(want)) == {0, 1}
+    flags = impl.mark(dict(c, nx=n[0], lo=np.array(lo, F32)), B)
+    assert flags.dtype == np.uint8 and flags.shape == nb[::-1]
+    assert (flags[:, :, -wbx:] == want).all() and int(flags[:, :, :-wbx].sum()) == 0
+    print("tsdf_brick_mark on %d bricks: %d of the window's %d flagged" % (flags.size, int(want.sum()), want.size))
 
 
 # ---- the C entry points themselves -------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 (csrc/host/RendererQuery.cpp BrickMark, MeshFromBricks) under the wavefront emulator (tests/wave_emul), against the numpy restatement
 of tests/mesh_sparse_ref.py and against the dense kernels' own output (f2n_mesh_count -> f2n_mesh_emit), bit for bit.  The checks are
 functions of an `impl` (brick_mark, mesh_from_bricks, mesh_from_grid on numpy arrays): tests/test_gpu_mesh_sparse.py runs them on the
-device through host.* and capi.*."""
+device through host.* and capi.*.  The check_huge_* bodies run the listed-brick kernels on windows of virtual grids whose corner indices,
+keys and brick ids need more than 32 bits (tests/mesh_sparse_ref.py, HUGE_GRIDS)."""
 import ctypes
 import os
 import sys
@@ -148,6 +149,102 @@ def check_errors(impl):
         impl.brick_mark(fox_tree(), lo, step, (1 << 19, 1 << 19, 1 << 19), 4)
 
 
+# ---- virtual grids whose indices need more than 32 bits (tests/mesh_sparse_ref.py, HUGE_GRIDS) -----------------------------------
+_HUGE = {}
+
+
+def huge_case(name, which):
+    """(window, its dense sub-grid of an analytic sphere, the rows of its bricks, the restatement's mesh of the sub-grid): built once"""
+    if (name, which) not in _HUGE:
+        w = sr.huge_window(name, which)
+        g = sr.window_sphere(w)
+        rv, rf = mr.marching_tets(g, 0.0, w["lo_w"], w["step"])
+        values = sr.brick_values(g, w["local_ids"], w["B"])  # (NaN where a corner does not exist: never read)
+        for a in (g, values, rv, rf):
+            a.setflags(write=False)
+        _HUGE[(name, which)] = (w, g, values, rv, rf)
+    return _HUGE[(name, which)]
+
+
+def check_huge_magnitudes(name):
+    """what the grids were chosen for, in Python integers"""
+    far, inner = (sr.huge_magnitudes(sr.huge_window(name, which)) for which in ("far", "inner"))
+    n, B = sr.HUGE_GRIDS[name]["n"], sr.HUGE_GRIDS[name]["B"]
+    assert far["corner"] == n[0] * n[1] * n[2] - 1 and far["brick_id"] == far["bricks"] - 1  # the far window ends at the last corner
+    for m in (far, inner):
+        assert m["corner"] > 2 ** 36 and m["vertex_key"] > 2 ** 39 and m["face_key"] > 2 ** 39
+    if name == "wide16":
+        assert far["bricks"] == 2 ** 25 and far["brick_id"] > 2 ** 24 and inner["brick_id"] > 2 ** 24
+    if name == "full":  # the most bricks the entry points accept along x and z, and a clipped last brick along x
+        assert far["bricks"] == 131072 * 8191 * 2 == 2 ** 31 - 262144 and far["brick_id"] == 2 ** 31 - 262145 and inner["brick_id"] > 2 ** 30
+        assert (n[0] - 1) % B == 3 and sr.huge_window(name, "far")["m"][0] == 4 * B
+    (bad_n, bad_B) = sr.HUGE_REFUSED
+    assert int(np.prod([int(v) for v in sr.n_bricks(bad_n, bad_B)], dtype=object)) == 2 ** 31
+
+
+def check_huge_mesh_from_bricks(impl, name):
+    """mesh_from_bricks over a window of a huge virtual grid = mesh_from_grid on the window's dense sub-grid with the translated lo, bit
+    for bit (the translation is exact; vertex and face order is lexicographic in (z, y, x) on both sides) -- with the list ascending
+    and shuffled, in one batch and in three; and the dense mesh is the restatement's."""
+    check_huge_magnitudes(name)
+    for which in ("far", "inner"):
+        w, g, values, rv, rf = huge_case(name, which)
+        n, B, lo, step = w["n"], w["B"], w["lo"], w["step"]
+        dv, df = impl.mesh_from_grid(np.array(g), 0.0, w["lo_w"], step)  # (a copy: the cached grid is read-only)
+        assert len(df) > 0 and df.dtype == np.int32 and same_bits(df, rf)
+        assert dv.shape == rv.shape and np.abs(dv - rv).max() <= 1e-6 * step * max(1.0, np.abs(rv).max())
+        ids = w["ids"]
+        mixed = np.random.default_rng(B).permutation(len(ids))
+        third = -(-len(ids) // 3)
+        for order, batch in ((np.arange(len(ids)), 0), (mixed, 0), (np.arange(len(ids)), third), (mixed, third)):
+            v, f = impl.mesh_from_bricks(values[order], ids[order], n, lo, step, 0.0, B, batch)
+            assert f.dtype == np.int32 and same_bits(f, df), (name, which, batch)
+            assert v.dtype == F32 and same_bits(v, dv), (name, which, batch)
+
+
+# the first corner of a window of each grid inside the fox scene, where live and dead leaves of 4 to 16 steps meet (found on the CPU
+# with mesh_ref.locate; the checks below assert that both kinds of point are there)
+LOCATE_LO_W = {"wide16": (-0.4375, -0.6875, 0.3125), "wide8": (0.375, 0.375, -0.3125), "full": (0.6875, -0.3125, -0.125)}
+
+
+def fox_transes():
+    return np.array(np.load(os.path.join(ROOT, "tests", "golden", "fox_state.npz"))["pers_trans"], np.uint8).reshape(-1)
+
+
+def check_huge_locate(loc, name):
+    """loc.bricks(ids, lo, step, n, B, tree, transes) / loc.points(pts, tree, transes) -> (warped [m,3], anchors [m,3]): the rows of
+    f2n_oct_locate_warp_bricks are f2n_oct_locate_warp's on the explicit corner coordinates; a corner beyond n - 1 is an empty point"""
+    tree, transes = fox_tree(), fox_transes()
+    nodes = mr.parse_nodes(tree)
+    for which in ("far", "inner"):
+        w = sr.huge_window(name, which, lo_w=LOCATE_LO_W[name])
+        n, B, step = w["n"], w["B"], w["step"]
+        order = np.random.default_rng(7).permutation(len(w["ids"]))
+        warped, anchors = loc.bricks(w["ids"][order], w["lo"], step, n, B, tree, transes)
+        idx, ex = (np.stack(a) for a in zip(*(sr.brick_corner_indices(int(b), w["m"], B) for b in w["local_ids"][order])))
+        pts = (np.array(w["lo_w"])[None, None] + step * idx).astype(F32).reshape(-1, 3)  # (exact)
+        ex = ex.reshape(-1)
+        assert (~ex).any() == (name == "full" and which == "far")  # (the clipped last brick along x)
+        rw, ra = loc.points(pts, tree, transes)
+        assert warped.shape == rw.shape and anchors.shape == ra.shape and anchors.dtype == np.int32 and warped.dtype == F32
+        assert same_bits(anchors[ex], ra[ex]) and same_bits(warped[ex], rw[ex])
+        assert (anchors[~ex] == np.array([-1, -1, 0])).all() and (warped[~ex] == 0).all()
+        empty = ra[ex, 0] < 0
+        assert 0 < empty.sum() < ex.sum(), (name, which, int(empty.sum()))
+        for j in np.random.default_rng(8).choice(np.flatnonzero(ex), 40, replace=False):  # (the oracle's own footing)
+            assert tuple(anchors[j, :2]) == mr.locate(nodes, pts[j])
+
+
+def check_huge_errors(impl):
+    """exactly 2^31 bricks: refused before anything is allocated or launched"""
+    n, B = sr.HUGE_REFUSED
+    w, g, values, rv, rf = huge_case("full", "inner")
+    with pytest.raises(ValueError):
+        impl.brick_mark(fox_tree(), w["lo"], w["step"], n, B)
+    with pytest.raises(ValueError):
+        impl.mesh_from_bricks(np.array(values), w["ids"], n, w["lo"], w["step"], 0.0, B, 0)
+
+
 # ---- the emulator ------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emul():
@@ -245,3 +342,41 @@ def test_errors(impl, emul):
     assert emul_brick_mark(emul, tree, (0, 0, 0), 1.0, (9, 9, 9), 5, np.zeros(8, np.uint8))[0] == -1        # F2N_ERR_INVALID_ARG
     assert emul_brick_mark(emul, tree, (0, 0, 0), 1.0, (9, 1, 9), 4, np.zeros(8, np.uint8))[0] == -1
     assert emul_brick_mark(emul, tree, (0, 0, 0), 1.0, (1 << 19,) * 3, 4, np.zeros(8, np.uint8))[0] == -2   # F2N_ERR_UNSUPPORTED
+
+
+def emul_locate(L):
+    """f2n_oct_locate_warp_bricks / f2n_oct_locate_warp themselves, on host arrays"""
+    def out(m):
+        return np.full((m, 3), 7, F32), np.full((m, 3), 7, np.int32)
+
+    def bricks(ids, lo, step, n, B, tree, transes):
+        ids = np.ascontiguousarray(ids, np.int32)
+        w, a = out(len(ids) * (B + 1) ** 3)
+        assert L.f2n_oct_locate_warp_bricks(None, _lo3(lo), _f(step), _i(n[0]), _i(n[1]), _i(n[2]), _i(B), _i(len(ids)), _vp(ids), _vp(tree),
+                                            _vp(transes), _vp(w), _vp(a)) == 0
+        return w, a
+
+    def points(pts, tree, transes):
+        pts = np.ascontiguousarray(pts, F32)
+        w, a = out(len(pts))
+        assert L.f2n_oct_locate_warp(None, _i(len(pts)), _vp(pts), _vp(tree), _vp(transes), _vp(w), _vp(a)) == 0
+        return w, a
+
+    return types.SimpleNamespace(bricks=bricks, points=points)
+
+
+@pytest.mark.parametrize("name", sorted(sr.HUGE_GRIDS))
+def test_mesh_from_bricks_on_a_huge_virtual_grid(impl, name):
+    check_huge_mesh_from_bricks(impl, name)
+
+
+@pytest.mark.parametrize("name", sorted(sr.HUGE_GRIDS))
+def test_locate_warp_bricks_on_a_huge_virtual_grid(emul, name):
+    check_huge_locate(emul_locate(emul), name)
+
+
+def test_two_to_the_31_bricks_are_refused(impl, emul):
+    check_huge_errors(impl)
+    n, B = sr.HUGE_REFUSED
+    rc, flags = emul_brick_mark(emul, fox_tree(), (0, 0, 0), 1.0, n, B, np.full(8, 7, np.uint8))
+    assert rc == -2 and (flags == 7).all()  # F2N_ERR_UNSUPPORTED, nothing written

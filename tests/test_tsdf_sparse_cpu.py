@@ -2,7 +2,8 @@
 f2n_brick_mesh_count_masked / _emit_masked (csrc/octree.hip) and their host wrappers (csrc/host/RendererQuery.cpp) under the wavefront
 emulator (tests/wave_emul), against the numpy restatement of tests/tsdf_sparse_ref.py and against the dense kernels' own output
 (f2n_tsdf_integrate -> f2n_tsdf_finalize -> f2n_mesh_count_masked -> f2n_mesh_emit), bit for bit.  The checks are functions of an `impl`
-(numpy in, numpy out): tests/test_gpu_tsdf_sparse.py runs them on the device through host.* and capi.*."""
+(numpy in, numpy out): tests/test_gpu_tsdf_sparse.py runs them on the device through host.* and capi.*.  The check_huge_* bodies run the
+listed-brick kernels on windows of virtual grids whose corner indices and brick ids need more than 32 bits (tests/mesh_sparse_ref.py)."""
 import ctypes
 import os
 import sys
@@ -21,6 +22,7 @@ import mesh_sparse_ref as sr  # noqa: E402
 import tsdf_ref as tr  # noqa: E402
 import tsdf_sparse_ref as ts  # noqa: E402
 from test_tsdf_cpu import mask_cases, sphere_case  # noqa: E402
+from test_mesh_sparse_cpu import huge_case  # noqa: E402
 
 F32 = np.float32
 INVALID, UNSUPPORTED = -1, -2  # F2N_ERR_INVALID_ARG, F2N_ERR_UNSUPPORTED
@@ -222,6 +224,75 @@ def check_value_errors(impl, st):
             impl.mark(bad, 4)
         with pytest.raises(ValueError):
             impl.integrate_bricks(bad, z, z.copy(), ids, 4)
+
+
+# ---- virtual grids whose indices need more than 32 bits (tests/mesh_sparse_ref.py, HUGE_GRIDS) -----------------------------------
+def check_huge_masked_mesher(impl, name):
+    """mesh_from_bricks_masked over a window of a huge virtual grid = mesh_from_grid_masked on the window's dense sub-grid with the
+    translated lo, bit for bit -- the list ascending and shuffled, in one batch and in three; the dense masked mesh is the restatement's"""
+    for which in ("far", "inner"):
+        w, g, values, rv, rf = huge_case(name, which)
+        n, B, lo, step, m = w["n"], w["B"], w["lo"], w["step"], w["m"]
+        valid = (np.random.default_rng(len(name) + B).random(g.shape) > 0.04).astype(np.uint8)
+        ok = ts.brick_rows(valid, w["local_ids"], m, B, np.full(values.shape, 9, np.uint8))  # (9 where no corner exists: never read)
+        dv, df = impl.mesh_masked_grid(g, valid, 0.0, w["lo_w"], step)
+        assert 0 < len(df) < len(rf)  # (the mask removes faces of the sphere, not all of them)
+        mv, mf = tr.marching_tets_masked(g, 0.0, valid, w["lo_w"], step)[:2]
+        assert tr.same_bits(df, mf) and dv.shape == mv.shape and np.abs(dv - mv).max() <= 1e-6 * step * max(1.0, np.abs(mv).max())
+        ids = w["ids"]
+        mixed = np.random.default_rng(B).permutation(len(ids))
+        third = -(-len(ids) // 3)
+        for order, batch in ((np.arange(len(ids)), 0), (mixed, 0), (np.arange(len(ids)), third), (mixed, third)):
+            v, f = impl.mesh_masked_bricks(values[order], ok[order], ids[order], n, lo, step, 0.0, B, batch)
+            assert v.dtype == F32 and f.dtype == np.int32
+            assert tr.same_bits(v, dv) and tr.same_bits(f, df), (name, which, batch)
+
+
+_HUGE_TSDF = {}
+
+
+def huge_tsdf_case(st, name, which):
+    """(window, the small case that is the window's dense sub-grid, the same views on the huge grid): tsdf_ref.synthetic_case at the
+    window's size with a power-of-two step and lo a multiple of it, so that the translation to the huge grid's lo is exact"""
+    if (name, which) not in _HUGE_TSDF:
+        m = sr.huge_window(name, which)["m"]
+        c = tr.synthetic_case(st, dims=m, pow2=True)
+        w = sr.huge_window(name, which, lo_w=c["lo"], step=float(c["step"]))
+        big = dict(c, nx=w["n"][0], ny=w["n"][1], nz=w["n"][2], lo=np.array(w["lo"], F32))
+        _HUGE_TSDF[(name, which)] = (w, c, big)
+    return _HUGE_TSDF[(name, which)]
+
+
+def check_huge_integrate_bricks(impl, st, name):
+    """f2n_tsdf_integrate_bricks over a window of a huge virtual grid: the S and W rows are f2n_tsdf_integrate's on the window's dense
+    sub-grid, bit for bit; the rows of corners that do not exist are untouched"""
+    for which in ("far", "inner"):
+        w, c, big = huge_tsdf_case(st, name, which)
+        B, m = w["B"], w["m"]
+        z = np.zeros(m[::-1], F32)
+        dS, dW = impl.integrate(c, z, z.copy())  # the dense kernel on the small grid
+        assert (dW > 0).any() and (dW == 0).any()
+        sent = np.full((len(w["ids"]), (B + 1) ** 3), -7.5, F32)
+        S0 = ts.brick_rows(z, w["local_ids"], m, B, sent)  # every existing corner starts from zero, the others from a sentinel
+        assert (S0 == -7.5).any() == (name == "full" and which == "far")  # (the clipped last brick along x)
+        wantS, wantW = ts.brick_rows(dS, w["local_ids"], m, B, sent), ts.brick_rows(dW, w["local_ids"], m, B, sent)
+        for order in (np.arange(len(w["ids"])), np.random.default_rng(B).permutation(len(w["ids"]))):
+            S, W = impl.integrate_bricks(big, S0[order], S0[order], w["ids"][order], B)
+            assert tr.same_bits(S, wantS[order]) and tr.same_bits(W, wantW[order]), (name, which)
+
+
+def check_huge_value_errors(impl, st):
+    """exactly 2^31 bricks: refused before anything is allocated or launched"""
+    (nx, ny, nz), B = sr.HUGE_REFUSED
+    w, c, big = huge_tsdf_case(st, "full", "inner")
+    bad = dict(big, nx=nx, ny=ny, nz=nz)
+    z = np.zeros((len(w["ids"]), (B + 1) ** 3), F32)
+    with pytest.raises(ValueError):
+        impl.mark(bad, B)
+    with pytest.raises(ValueError):
+        impl.integrate_bricks(bad, z, z.copy(), w["ids"], B)
+    with pytest.raises(ValueError):
+        impl.mesh_masked_bricks(z, np.ones(z.shape, np.uint8), w["ids"], (nx, ny, nz), w["lo"], w["step"], 0.0, B, 0)
 
 
 # ---- impls -------------------------------------------------------------------------------------------------------------------------
@@ -435,3 +506,25 @@ def test_the_launcher_refuses_before_anything_is_rendered(tmp_path):
         with pytest.raises(ValueError):
             mesh.extract(Untouchable(), config.preset("wanjinyou", base + extra), scene, str(tmp_path), Untouchable())
     assert not os.path.exists(os.path.join(str(tmp_path), "meshes"))
+
+
+@pytest.mark.parametrize("name", sorted(sr.HUGE_GRIDS))
+def test_masked_brick_mesher_on_a_huge_virtual_grid(impl, name):
+    check_huge_masked_mesher(impl, name)
+
+
+@pytest.mark.parametrize("name", sorted(sr.HUGE_GRIDS))
+def test_brick_integration_on_a_huge_virtual_grid(impl, fox_state, name):
+    check_huge_integrate_bricks(impl, fox_state, name)
+
+
+def test_two_to_the_31_bricks_are_refused(impl, emul, fox_state):
+    check_huge_value_errors(impl, fox_state)
+    (nx, ny, nz), B = sr.HUGE_REFUSED
+    w, c, big = huge_tsdf_case(fox_state, "full", "inner")
+    flags, ids = np.full(8, 7, np.uint8), np.ascontiguousarray(w["ids"][:2])
+    S, W = np.full((2, 125), 7, F32), np.full((2, 125), 7, F32)
+    assert emul_mark(emul, big, flags, nx=nx, ny=ny, nz=nz, B=B) == UNSUPPORTED
+    assert emul_integrate_bricks(emul, big, S, W, ids, nx=nx, ny=ny, nz=nz, B=B) == UNSUPPORTED
+    assert (flags == 7).all() and (S == 7).all() and (W == 7).all()  # nothing was written
+    assert emul_integrate_bricks(emul, big, S, W, ids, B=B) == 0 and (W != 7).any()  # the full grid, 2^31 - 262144 bricks, is accepted

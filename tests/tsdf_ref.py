@@ -222,10 +222,12 @@ def axes_focus(poses):
     return np.linalg.solve(A, b)
 
 
-def synthetic_case(st, dims=(37, 21, 19), n_views=5, hw=(61, 45), seed=3, with_conf=True):
+def synthetic_case(st, dims=(37, 21, 19), n_views=5, hw=(61, 45), seed=3, with_conf=True, pow2=False):
     """A grid of dims = (nx, ny, nz) points between the fox cameras and the point they look at, long enough to reach behind some of them
     and wide enough to leave every image; depth maps around the distance of the grid's centre with zeros, negatives, NaN and +inf
-    sprinkled in, conf with zeros; a few pixels planted so that sdf == -trunc exactly and others so that sdf >= trunc."""
+    sprinkled in, conf with zeros; a few pixels planted so that sdf == -trunc exactly and others so that sdf >= trunc.  pow2: step is
+    rounded to a power of two and lo to a multiple of it before the maps are made -- the grid can then be translated by whole steps
+    without a rounding (a window of a larger grid)."""
     rng = np.random.default_rng(seed)
     nx, ny, nz = dims
     h, w = hw
@@ -239,7 +241,11 @@ def synthetic_case(st, dims=(37, 21, 19), n_views=5, hw=(61, 45), seed=3, with_c
     centre = 0.5 * (focus + eye)
     extent = 1.6 * np.linalg.norm(focus - eye)
     step = F32(extent / (nx - 1))
+    if pow2:
+        step = F32(2.0 ** np.round(np.log2(float(step))))
     lo = (centre - 0.5 * float(step) * (np.array(dims) - 1)).astype(F32)
+    if pow2:
+        lo = (np.round(lo.astype(np.float64) / float(step)) * float(step)).astype(F32)
     trunc = F32(0.0625)
     r_mid = np.linalg.norm(poses[:, :, 3].astype(np.float64) - focus[None], axis=1)
     depth = (r_mid[:, None, None] * rng.uniform(0.6, 1.1, (n_views, h, w))).astype(F32)
