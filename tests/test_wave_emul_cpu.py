@@ -28,11 +28,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "wave_emul"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import test_gpu_converged as gconv  # noqa: E402
+import test_gpu_mlp_bounds as gbound  # noqa: E402
 import test_gpu_mlp_shapes as gmlp  # noqa: E402
 import test_gpu_parity as gp  # noqa: E402
 import test_gpu_scale as gscale  # noqa: E402
 
-_GPU_MODULES = (gp, gscale, gconv, gmlp)
+_GPU_MODULES = (gp, gscale, gconv, gmlp, gbound)
 
 
 @pytest.fixture(scope="session")
@@ -176,6 +177,18 @@ _MORE = [
     # the run-combining / cost-balanced gather (every training iteration from fineness ~4 down takes it)
     (gconv, "test_balanced_gather_edge_sizes", None),
     (gconv, "test_balanced_gather_unstaged_with_many_warps", ("fineness", [4.0])),
+    # the fused MLP kernels per element against fp64 (tests/mlp_bound_ref.py), with the GPU run's own parameters
+    (gbound, "test_mlp_per_element", None),
+    (gbound, "test_mlp_zero_column_and_dead_unit_are_exact", None),
+    (gbound, "test_mlp_samples_without_dy_contribute_nothing", None),
+    (gbound, "test_mlp_rows_past_n_are_neither_read_nor_written", None),
+    (gbound, "test_shade_per_element", None),
+    (gbound, "test_shade_lds_and_global_embedding_paths_agree", None),
+    (gbound, "test_shade_samples_without_drgb_contribute_nothing", None),
+    (gbound, "test_shade_rows_past_n_are_neither_read_nor_written", None),
+    (gbound, "test_field_per_element", None),
+    (gbound, "test_field_binned_per_element", ("rows_past_n", [False])),  # (the route starts at 32768 samples: one run of them here)
+    (gbound, "test_field_rows_past_n_are_neither_read_nor_written", None),
 ]
 for _mod, _name, _params in _MORE:
     globals()[_name] = _on_the_emulator(_name, _params, _mod)
